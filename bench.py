@@ -15,6 +15,13 @@ defaults (teb_autosize on: the bands end with 193 .. 287 poses).
                                        selection: one 16-byte-per-rank ncclAllGather inside libteb_amd.so
   --scaling strong                     ONE 256-candidate batch sharded over the ranks (BASELINE configs[3]: 32 per GPU at N = 8),
                                        selection exchange + broadcast of the winner's strip from its owner
+  --full                               also the figures beyond the headline: roofline, phase split and latency model, the sustained
+                                       segment, plan latencies, the secondary configurations, the parity checks and the CPU baseline
+                                       (--no-cpu-baseline, --no-parity-check, --latency-reps and --sustain-seconds select among them);
+                                       a plain run sets up, warms up, times the steps and prints the headline
+  --dump-outputs DIR                   after the timed steps: what the last step computed on rank 0 (bands, per-band results, the
+                                       selected index) as DIR/<name>.npy in float64; the inputs are seeded, so two builds compare
+                                       output for output
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -182,6 +189,21 @@ def noise_floor(RC, cfg, obst, via, batch, ref_pack, out_dev, B, numeric_mode=Fa
     return rr
 
 
+def dump_outputs(d, bands, res, best):
+    """What a caller of the timed step receives, as <d>/<name>.npy in float64: the optimised bands ([B, capacity] planes, zero beyond
+    each band's pose count - the device leaves stale values there), the per-band LM results and the selected band."""
+    os.makedirs(d, exist_ok=True)
+    valid = np.arange(bands.stride)[None, :] < bands.n[:, None]
+    arrays = {"pose_counts": bands.n, "best_index": np.array([best])}
+    for k in ("x", "y", "theta"):
+        arrays[k] = np.where(valid, getattr(bands, k), 0.0)
+    arrays["dt"] = np.where(np.arange(bands.stride)[None, :] < bands.n[:, None] - 1, bands.dt, 0.0)
+    for k in ("status", "lm_iterations", "lm_trials", "chi2", "cost", "lambda_"):
+        arrays[k.rstrip("_")] = getattr(res, k)
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.asarray(a, dtype=np.float64))
+
+
 def time_solver(torch, s, cfg, reps):
     """median kernel ms / wall ms per optimize over `reps` runs from the snapshot; returns (kernel_ms, wall_ms, results)."""
     ms, wall, res = [], [], None
@@ -211,7 +233,16 @@ def main():
     ap.add_argument("--parity-bands", type=int, default=16)
     ap.add_argument("--latency-reps", type=int, default=20)
     ap.add_argument("--sustain-seconds", type=float, default=12.0, help="length of the sustained segment after the timed steps (N = 1 only; 0 = off)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beyond the headline figure")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps and the headline line, nothing else
+        args.sustain_seconds = 0.0
+        args.latency_reps = 0
+        args.no_cpu_baseline = True
+        args.no_parity_check = True
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
@@ -335,8 +366,10 @@ def main():
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    clock_mhz = [s.last_shader_clock_mhz()]             # of the last timed step (read outside the timed region: a copy + a synchronisation)
     res = s.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, s.download(_abi.TebBatchHost(B, STRIDE)), res, best)
+    clock_mhz = [s.last_shader_clock_mhz()] if args.full else []   # of the last timed step (read outside the timed region: a copy + a synchronisation)
     # a sustained segment of the SAME step (>= 3 s): long enough for an external sampler (rocm-smi) to see the device busy; its
     # per-step time has to agree with the K timed steps above
     sustained = None
@@ -370,18 +403,7 @@ def main():
         value = units_all * args.steps / elapsed_max
         kms = float(np.mean(kernel_ms))
         M = len(obst)
-        # association list size for the algorithmic-byte model: measured on TEB 0 of this rank
-        s.restore()
-        dbg = s.debug_linearize(0, n, 1.0)
-        e_assoc = len(dbg["assoc_pose"])
         n_eff = float(n_after.mean())                 # pose count the iterations of this step actually worked on
-        abu = alg_bytes_per_unit(n_eff, M, e_assoc, inner)
-        alg_bytes_launch = abu * units_step
-        achieved = alg_bytes_launch / (kms * 1e-3) / 1e9
-        # HBM-side traffic per launch from the committed rocprofv3 PMC passes of THIS command (FETCH_SIZE / WRITE_SIZE in separate
-        # runs, scaled by the factors calibrated on a known 1 GiB stream; profiles/rocprof_*_summary.json). The summary records the
-        # hash of the device sources it was taken from; a summary of other sources is reported as stale, never silently reused.
-        traffic, traffic_src, traffic_note, fp64, mfma, pj, fr, fw = None, None, None, None, None, None, 2048.0, 1024.0
         src_hash = kernel_source_hash()
         # ... and to the BINARY: the library carries the hash build.py computed when it was built (teb_amd_debug_build_info). A library
         # that is older than the tree (build() is mtime-based, the .so ships prebuilt to the GPU box) shows here, and no profile is attached.
@@ -389,33 +411,6 @@ def main():
             binary_hash, binary_full_hash, binary_defines, _ = planner.TebBatchSolver.build_info()
         except Exception as e:   # noqa: BLE001
             binary_hash, binary_full_hash, binary_defines = "unreadable: %s" % str(e)[:60], "", ""
-        try:
-            import glob
-            import re as _re
-            # the newest round's summary (by its tag r<NN>[suffix], not by file time: a fresh checkout gives every file the same one)
-            cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "rocprof_r*_summary.json")),
-                           key=lambda f: (int(_re.search(r"rocprof_r(\d+)", os.path.basename(f)).group(1)), os.path.basename(f)))
-            if cands and args.tebs == 256 and n == 200 and args.scaling == "weak":
-                pj = json.load(open(cands[-1]))
-                traffic_src = os.path.basename(cands[-1])
-                if pj.get("source_hash") == src_hash and binary_hash == src_hash and pj.get("binary_hash", binary_hash) == binary_hash:
-                    cal = pj.get("calibration", {})
-                    fr = cal.get("FETCH_SIZE_bytes_per_counted_KB", 2048.0)
-                    fw = cal.get("WRITE_SIZE_bytes_per_counted_KB", 1024.0)
-                    traffic = pj["FETCH_SIZE_KB_per_launch"] * fr + pj["WRITE_SIZE_KB_per_launch"] * fw
-                    if pj.get("fp64_flop_per_launch"):   # PMC pass SQ_INSTS_VALU_*_F64 of this command (instruction counts x 64 lanes)
-                        fp64 = {"flop_per_launch": pj["fp64_flop_per_launch"], "achieved": pj["fp64_flop_per_launch"] / (kms * 1e-3) / 1e12,
-                                "peak": 78.6, "unit": "TFLOP/s", "source": traffic_src,
-                                "note": "vector fp64; peak = AMD spec, half the 157.3 TFLOP/s fp32 vector rate; the build uses "
-                                        "-ffp-contract=off outside the solve, so mul+add pairs issue as two instructions"}
-                        fp64["frac"] = fp64["achieved"] / fp64["peak"]
-                    if pj.get("mfma"):
-                        mfma = pj["mfma"]
-                else:
-                    traffic_note = ("%s was taken from other device sources or another binary (summary: sources %s, binary %s; now: sources %s, "
-                                    "loaded binary %s): not reported" % (traffic_src, pj.get("source_hash"), pj.get("binary_hash"), src_hash, binary_hash))
-        except Exception as e:   # noqa: BLE001
-            traffic_note = "profile summary unreadable: %s" % str(e)[:80]
         if args.scaling == "strong":
             wl = ("C4 strong scaling: ONE batch of %d candidate TEBs sharded over %d rank(s) (%d on rank 0) x %d poses at the start "
                   "(teb_autosize on: %d..%d after the step on rank 0), %d point obstacles (%d dynamic), winner strip broadcast (%d poses)"
@@ -435,96 +430,135 @@ def main():
                        "lm_trials_per_step_per_gpu": int(res.lm_trials.sum()), "jacobian_mode": "analytic (closed form)",
                        "exchange": route["note"] or exchange, "source_hash": src_hash, "binary_hash": binary_hash,
                        "binary_matches_sources": bool(binary_hash == src_hash), "binary_variant_defines": binary_defines},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
-                         "frac": achieved / 8000.0, "traffic": traffic, "traffic_unit": "bytes/launch",
-                         "traffic_source": traffic_src,
-                         "kernel": "teb_optimize_kernel", "kernel_ms": kms,
-                         "shader_clock_mhz": {"mean": float(np.mean(clock_mhz)), "min": float(np.min(clock_mhz)), "max": float(np.max(clock_mhz)),
-                                              "what": "cycle counter / 100 MHz real-time counter between entry and exit of the kernel's first workgroup, "
-                                                      "last timed step + one sample per 50 steps of the sustained segment: boxes of the pool sustain 2.05 - 2.4 GHz under this load; kernel_ms x clock = cycles"},
-                         "kernel_mcycles": kms * float(np.mean(clock_mhz)) * 1e-3,
-                         "alg_bytes_per_unit": abu, "alg_bytes_per_launch": alg_bytes_launch},
         }
-        if sustained:
-            sustained["agrees_with_timed_steps_within_3_percent"] = bool(abs(sustained["ms_per_step"] / out["ms_per_step"] - 1.0) <= 0.03)
-            out["sustained"] = sustained
-        # dependency-latency model (primitive latencies measured on this chip x chain lengths of one LM iteration, see latency_model)
-        try:
-            import glob
-            pr = sorted(glob.glob(os.path.join(ROOT, "profiles", "latency_probe_r*.json")))
-            if pr:
-                probe = json.load(open(pr[-1]))["workgroups_256"]
-                tr_per_it = float(res.lm_trials.sum()) / max(1.0, float(res.lm_iterations.sum()))
-                lm = latency_model(probe, int(round(float(n_after.max()))), tr_per_it, e_assoc / max(1.0, n_eff), 0.3)
-                # the launch ends with its slowest band: its LM iterations x the model against the kernel's cycles at the clock the probe ran at
-                clock_hz = 1e6 * float(np.mean(clock_mhz)) if clock_mhz and np.mean(clock_mhz) > 0 else 2.06e9   # measured on the timed steps (roofline.shader_clock_mhz)
-                its = int(res.lm_iterations.max())
-                model_ms = 1e3 * its * lm["cycles_per_lm_iteration"] / clock_hz
-                lm.update({"lm_iterations_of_a_band": its, "model_ms_per_launch": model_ms, "kernel_ms": kms, "achieved_over_model": kms / model_ms,
-                           "shader_clock_hz": clock_hz, "source": os.path.basename(pr[-1]),
-                           "note": "critical path only (dependent-instruction chains of the longest band at one wave per SIMD, unbounded issue width, "
-                                   "no LDS / L2 contention, autoResize and association left out): what remains between it and the kernel is issue "
-                                   "bandwidth (fp64 at 16 lanes / cycle / SIMD), LDS pipe sharing between the four waves and barrier skew"})
-                out["roofline"]["latency_model"] = lm
-        except Exception as e:   # noqa: BLE001
-            out["roofline"]["latency_model"] = {"error": str(e)[:200]}
-        # phase split measured on the PRODUCT kernel (teb_amd_set_phase_log: s_memtime at the phase boundaries, lane 0 of every band's
-        # workgroup), one extra launch outside the timed region; the same launch with the log off beside it
-        try:
-            s.set_phase_log(True)
-            k_on = []
-            for _ in range(5):
-                s.restore(); torch.cuda.synchronize()
-                hp.optimizeAllTEBs(inner, outer); s.synchronize()
-                k_on.append(float(s.last_kernel_ms()))
-            k_on = float(np.median(k_on))
-            plog = s.phase_log()
-            s.set_phase_log(False)
-            tot = plog[:, :7].sum(axis=1)
-            slow = int(np.argmax(plog[:, 8]))
-            share = plog[:, :7] / np.maximum(tot[:, None], 1.0)
-            out["roofline"]["phases"] = {
-                "what": "shader cycles per phase of every band's workgroup in the product kernel (include/teb_amd_debug.h: teb_amd_set_phase_log)",
-                "share_mean_of_bands": {nm: float(share[:, k].mean()) for k, nm in enumerate(planner.TebBatchSolver.PHASES)},
-                "share_slowest_band": {nm: float(share[slow, k]) for k, nm in enumerate(planner.TebBatchSolver.PHASES)},
-                "slowest_band": slow, "slowest_band_mcycles": float(plog[slow, 8]) * 1e-6, "covered": float((tot / np.maximum(plog[:, 8], 1.0)).mean()),
-                "cu_utilisation_mean_over_max": float(plog[:, 8].mean() / plog[:, 8].max()),
-                "kernel_ms_with_the_log": k_on, "kernel_ms_without": kms, "instrumented_over_product": k_on / kms}
-            # "achieved HBM GB/s for edge evaluation" (north_star): the algorithmic bytes of SURVEY 8(d) are ALL edge-phase bytes (state strips,
-            # obstacle table, association lists, the chi^2 / lambda words; the model keeps H and b in LDS, the solve moves none of them), so
-            # the edge phases' rate is those bytes over the time a CU spends in buildGraph side data + linearisation + update / error
-            # evaluation - the mean over the bands' workgroups (they run side by side, one per CU) of the three phase counters, at the shader
-            # clock measured in this run. traffic: FETCH + WRITE of the diagnostic build that runs the edge phases alone
-            # (-DTEB_AMD_DIAG_EDGE_ONLY, tools/profile.sh), per unit of THAT run, scaled to this launch's units.
-            edge_cyc = plog[:, [1, 2, 5]].sum(axis=1)
-            clk_hz = 1e6 * float(np.mean(clock_mhz))
-            t_edge = float(edge_cyc.mean()) / clk_hz
-            ee = {"bound": "hbm", "achieved": alg_bytes_launch / t_edge / 1e9, "peak": 8000.0, "unit": "GB/s",
-                  "phases": ["graph side data", "linearize", "update + evaluate"], "alg_bytes_per_launch": alg_bytes_launch,
-                  "mean_edge_phase_ms_per_band": 1e3 * t_edge, "slowest_band_edge_phase_ms": 1e3 * float(edge_cyc.max()) / clk_hz,
-                  "share_of_workgroup_cycles": float((edge_cyc / np.maximum(plog[:, 8], 1.0)).mean()),
-                  "what": "SURVEY 8(d) algorithmic bytes of the launch / mean over the bands of the shader cycles their workgroups spend in the "
-                          "edge phases (product kernel's phase log) at the measured shader clock", "traffic": None}
-            ee["frac"] = ee["achieved"] / ee["peak"]
+        if args.full:
+            # association list size for the algorithmic-byte model: measured on TEB 0 of this rank
+            s.restore()
+            dbg = s.debug_linearize(0, n, 1.0)
+            e_assoc = len(dbg["assoc_pose"])
+            abu = alg_bytes_per_unit(n_eff, M, e_assoc, inner)
+            alg_bytes_launch = abu * units_step
+            achieved = alg_bytes_launch / (kms * 1e-3) / 1e9
+            # HBM-side traffic per launch from the committed rocprofv3 PMC passes of THIS command (FETCH_SIZE / WRITE_SIZE in separate
+            # runs, scaled by the factors calibrated on a known 1 GiB stream; profiles/rocprof_*_summary.json). The summary records the
+            # hash of the device sources it was taken from; a summary of other sources is reported as stale, never silently reused.
+            traffic, traffic_src, traffic_note, fp64, mfma, pj, fr, fw = None, None, None, None, None, None, 2048.0, 1024.0
             try:
-                eo = (pj or {}).get("edge_only") if traffic is not None else None
-                if eo and eo.get("units_per_launch"):
-                    per_unit = (eo["FETCH_SIZE_KB_per_launch"] * fr + eo["WRITE_SIZE_KB_per_launch"] * fw) / eo["units_per_launch"]
-                    ee["traffic"] = per_unit * units_step
-                    ee["traffic_unit"] = "bytes/launch"
-                    ee["traffic_source"] = "%s: edge_only (FETCH + WRITE of the -DTEB_AMD_DIAG_EDGE_ONLY build, %.0f B per unit of its own run)" % (traffic_src, per_unit)
-                    ee["traffic_over_alg_bytes"] = ee["traffic"] / alg_bytes_launch
+                import glob
+                import re as _re
+                # the newest round's summary (by its tag r<NN>[suffix], not by file time: a fresh checkout gives every file the same one)
+                cands = sorted(glob.glob(os.path.join(ROOT, "profiles", "rocprof_r*_summary.json")),
+                               key=lambda f: (int(_re.search(r"rocprof_r(\d+)", os.path.basename(f)).group(1)), os.path.basename(f)))
+                if cands and args.tebs == 256 and n == 200 and args.scaling == "weak":
+                    pj = json.load(open(cands[-1]))
+                    traffic_src = os.path.basename(cands[-1])
+                    if pj.get("source_hash") == src_hash and binary_hash == src_hash and pj.get("binary_hash", binary_hash) == binary_hash:
+                        cal = pj.get("calibration", {})
+                        fr = cal.get("FETCH_SIZE_bytes_per_counted_KB", 2048.0)
+                        fw = cal.get("WRITE_SIZE_bytes_per_counted_KB", 1024.0)
+                        traffic = pj["FETCH_SIZE_KB_per_launch"] * fr + pj["WRITE_SIZE_KB_per_launch"] * fw
+                        if pj.get("fp64_flop_per_launch"):   # PMC pass SQ_INSTS_VALU_*_F64 of this command (instruction counts x 64 lanes)
+                            fp64 = {"flop_per_launch": pj["fp64_flop_per_launch"], "achieved": pj["fp64_flop_per_launch"] / (kms * 1e-3) / 1e12,
+                                    "peak": 78.6, "unit": "TFLOP/s", "source": traffic_src,
+                                    "note": "vector fp64; peak = AMD spec, half the 157.3 TFLOP/s fp32 vector rate; the build uses "
+                                            "-ffp-contract=off outside the solve, so mul+add pairs issue as two instructions"}
+                            fp64["frac"] = fp64["achieved"] / fp64["peak"]
+                        if pj.get("mfma"):
+                            mfma = pj["mfma"]
+                    else:
+                        traffic_note = ("%s was taken from other device sources or another binary (summary: sources %s, binary %s; now: sources %s, "
+                                        "loaded binary %s): not reported" % (traffic_src, pj.get("source_hash"), pj.get("binary_hash"), src_hash, binary_hash))
             except Exception as e:   # noqa: BLE001
-                ee["traffic_note"] = str(e)[:120]
-            out["roofline"]["edge_evaluation"] = ee
-        except Exception as e:   # noqa: BLE001
-            out["roofline"]["phases"] = {"error": str(e)[:200]}
-        if traffic_note:
-            out["roofline"]["traffic_note"] = traffic_note
-        if fp64:
-            out["roofline"]["valu_fp64"] = fp64
-        if mfma:
-            out["roofline"]["mfma"] = mfma
+                traffic_note = "profile summary unreadable: %s" % str(e)[:80]
+            out["roofline"] = {"bound": "hbm", "achieved": achieved, "peak": 8000.0, "unit": "GB/s",
+                               "frac": achieved / 8000.0, "traffic": traffic, "traffic_unit": "bytes/launch",
+                               "traffic_source": traffic_src,
+                               "kernel": "teb_optimize_kernel", "kernel_ms": kms,
+                               "shader_clock_mhz": {"mean": float(np.mean(clock_mhz)), "min": float(np.min(clock_mhz)), "max": float(np.max(clock_mhz)),
+                                                    "what": "cycle counter / 100 MHz real-time counter between entry and exit of the kernel's first workgroup, "
+                                                            "last timed step + one sample per 50 steps of the sustained segment: MI355X boards sustain 2.05 - 2.4 GHz under this load; kernel_ms x clock = cycles"},
+                               "kernel_mcycles": kms * float(np.mean(clock_mhz)) * 1e-3,
+                               "alg_bytes_per_unit": abu, "alg_bytes_per_launch": alg_bytes_launch}
+            if sustained:
+                sustained["agrees_with_timed_steps_within_3_percent"] = bool(abs(sustained["ms_per_step"] / out["ms_per_step"] - 1.0) <= 0.03)
+                out["sustained"] = sustained
+            # dependency-latency model (primitive latencies measured on this chip x chain lengths of one LM iteration, see latency_model)
+            try:
+                import glob
+                pr = sorted(glob.glob(os.path.join(ROOT, "profiles", "latency_probe_r*.json")))
+                if pr:
+                    probe = json.load(open(pr[-1]))["workgroups_256"]
+                    tr_per_it = float(res.lm_trials.sum()) / max(1.0, float(res.lm_iterations.sum()))
+                    lm = latency_model(probe, int(round(float(n_after.max()))), tr_per_it, e_assoc / max(1.0, n_eff), 0.3)
+                    # the launch ends with its slowest band: its LM iterations x the model against the kernel's cycles at the clock the probe ran at
+                    clock_hz = 1e6 * float(np.mean(clock_mhz)) if clock_mhz and np.mean(clock_mhz) > 0 else 2.06e9   # measured on the timed steps (roofline.shader_clock_mhz)
+                    its = int(res.lm_iterations.max())
+                    model_ms = 1e3 * its * lm["cycles_per_lm_iteration"] / clock_hz
+                    lm.update({"lm_iterations_of_a_band": its, "model_ms_per_launch": model_ms, "kernel_ms": kms, "achieved_over_model": kms / model_ms,
+                               "shader_clock_hz": clock_hz, "source": os.path.basename(pr[-1]),
+                               "note": "critical path only (dependent-instruction chains of the longest band at one wave per SIMD, unbounded issue width, "
+                                       "no LDS / L2 contention, autoResize and association left out): what remains between it and the kernel is issue "
+                                       "bandwidth (fp64 at 16 lanes / cycle / SIMD), LDS pipe sharing between the four waves and barrier skew"})
+                    out["roofline"]["latency_model"] = lm
+            except Exception as e:   # noqa: BLE001
+                out["roofline"]["latency_model"] = {"error": str(e)[:200]}
+            # phase split measured on the PRODUCT kernel (teb_amd_set_phase_log: s_memtime at the phase boundaries, lane 0 of every band's
+            # workgroup), one extra launch outside the timed region; the same launch with the log off beside it
+            try:
+                s.set_phase_log(True)
+                k_on = []
+                for _ in range(5):
+                    s.restore(); torch.cuda.synchronize()
+                    hp.optimizeAllTEBs(inner, outer); s.synchronize()
+                    k_on.append(float(s.last_kernel_ms()))
+                k_on = float(np.median(k_on))
+                plog = s.phase_log()
+                s.set_phase_log(False)
+                tot = plog[:, :7].sum(axis=1)
+                slow = int(np.argmax(plog[:, 8]))
+                share = plog[:, :7] / np.maximum(tot[:, None], 1.0)
+                out["roofline"]["phases"] = {
+                    "what": "shader cycles per phase of every band's workgroup in the product kernel (include/teb_amd_debug.h: teb_amd_set_phase_log)",
+                    "share_mean_of_bands": {nm: float(share[:, k].mean()) for k, nm in enumerate(planner.TebBatchSolver.PHASES)},
+                    "share_slowest_band": {nm: float(share[slow, k]) for k, nm in enumerate(planner.TebBatchSolver.PHASES)},
+                    "slowest_band": slow, "slowest_band_mcycles": float(plog[slow, 8]) * 1e-6, "covered": float((tot / np.maximum(plog[:, 8], 1.0)).mean()),
+                    "cu_utilisation_mean_over_max": float(plog[:, 8].mean() / plog[:, 8].max()),
+                    "kernel_ms_with_the_log": k_on, "kernel_ms_without": kms, "instrumented_over_product": k_on / kms}
+                # "achieved HBM GB/s for edge evaluation" (north_star): the algorithmic bytes of SURVEY 8(d) are ALL edge-phase bytes (state strips,
+                # obstacle table, association lists, the chi^2 / lambda words; the model keeps H and b in LDS, the solve moves none of them), so
+                # the edge phases' rate is those bytes over the time a CU spends in buildGraph side data + linearisation + update / error
+                # evaluation - the mean over the bands' workgroups (they run side by side, one per CU) of the three phase counters, at the shader
+                # clock measured in this run. traffic: FETCH + WRITE of the diagnostic build that runs the edge phases alone
+                # (-DTEB_AMD_DIAG_EDGE_ONLY, tools/profile.sh), per unit of THAT run, scaled to this launch's units.
+                edge_cyc = plog[:, [1, 2, 5]].sum(axis=1)
+                clk_hz = 1e6 * float(np.mean(clock_mhz))
+                t_edge = float(edge_cyc.mean()) / clk_hz
+                ee = {"bound": "hbm", "achieved": alg_bytes_launch / t_edge / 1e9, "peak": 8000.0, "unit": "GB/s",
+                      "phases": ["graph side data", "linearize", "update + evaluate"], "alg_bytes_per_launch": alg_bytes_launch,
+                      "mean_edge_phase_ms_per_band": 1e3 * t_edge, "slowest_band_edge_phase_ms": 1e3 * float(edge_cyc.max()) / clk_hz,
+                      "share_of_workgroup_cycles": float((edge_cyc / np.maximum(plog[:, 8], 1.0)).mean()),
+                      "what": "SURVEY 8(d) algorithmic bytes of the launch / mean over the bands of the shader cycles their workgroups spend in the "
+                              "edge phases (product kernel's phase log) at the measured shader clock", "traffic": None}
+                ee["frac"] = ee["achieved"] / ee["peak"]
+                try:
+                    eo = (pj or {}).get("edge_only") if traffic is not None else None
+                    if eo and eo.get("units_per_launch"):
+                        per_unit = (eo["FETCH_SIZE_KB_per_launch"] * fr + eo["WRITE_SIZE_KB_per_launch"] * fw) / eo["units_per_launch"]
+                        ee["traffic"] = per_unit * units_step
+                        ee["traffic_unit"] = "bytes/launch"
+                        ee["traffic_source"] = "%s: edge_only (FETCH + WRITE of the -DTEB_AMD_DIAG_EDGE_ONLY build, %.0f B per unit of its own run)" % (traffic_src, per_unit)
+                        ee["traffic_over_alg_bytes"] = ee["traffic"] / alg_bytes_launch
+                except Exception as e:   # noqa: BLE001
+                    ee["traffic_note"] = str(e)[:120]
+                out["roofline"]["edge_evaluation"] = ee
+            except Exception as e:   # noqa: BLE001
+                out["roofline"]["phases"] = {"error": str(e)[:200]}
+            if traffic_note:
+                out["roofline"]["traffic_note"] = traffic_note
+            if fp64:
+                out["roofline"]["valu_fp64"] = fp64
+            if mfma:
+                out["roofline"]["mfma"] = mfma
 
         # ---- parity of THIS run against the oracle (checker only, outside the timed region): a spread of bands of the headline batch,
         #      same closed-form mode, thread per TEB
@@ -674,7 +708,8 @@ def main():
                     lat["hcp_plan_tick"]["reference_code_cpu_ms_per_tick"] = 1e3 * (time.perf_counter() - t1) / ticks   # oracle/_ref, one thread
             except Exception as e:   # noqa: BLE001
                 lat["hcp_plan_tick"]["reference_code_cpu_ms_per_tick"] = str(e)[:120]
-        out["plan_latency"] = lat
+        if args.full:
+            out["plan_latency"] = lat
 
         # ---- secondary numbers (kernel time per optimizeAllTEBs of the other BASELINE configurations at full size, defaults):
         #      C4 with autoResize off (every band keeps 200 poses), the headline in the reference's own Jacobian mode (g2o central

@@ -10,6 +10,8 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(HERE, "golden"))
+import ref_replay  # noqa: E402
 from feasibility_cases import feasibility_case, FOOTPRINTS  # noqa: E402
 from oracle import oracle_py, ref_py  # noqa: E402
 from oracle.oracle_py import Costmap  # noqa: E402
@@ -41,12 +43,12 @@ def test_footprint_cost_known_answers():
     assert oracle_py.footprint_cost(cm, 3.0, 2.0, 0.0, big) == 0.0
 
 
-@pytest.mark.skipif(not ref_py.available(), reason="oracle/_ref not built (needs /root/reference)")
 @pytest.mark.parametrize("seed", range(60))
 def test_oracle_equals_reference_code(seed):
     batch, cm, fp, inscribed, ang, look, dist = feasibility_case(seed)
     got = oracle_py.is_trajectory_feasible(batch, 0, cm, fp, inscribed, ang, look, dist)
-    want = ref_py.is_trajectory_feasible(batch, 0, cm, fp, inscribed, ang, look, dist)
+    live = ref_py if ref_py.available() and not os.environ.get("TEB_REF_GOLDEN_ONLY") else None
+    want = ref_replay.reference("f4_feasibility", seed, live).is_trajectory_feasible(batch, 0, cm, fp, inscribed, ang, look, dist)   # recorded without oracle/_ref
     assert got == want, (seed, got, want)
 
 

@@ -31,6 +31,7 @@ from teb_local_planner_amd.config import TebConfig  # noqa: E402
 
 sys.path.insert(0, os.path.join(HERE, "golden"))
 import make_ref_golden as G  # noqa: E402
+import ref_replay  # noqa: E402
 
 
 def _ref():
@@ -113,10 +114,8 @@ def test_autoresize_matches_reference_implementation(oracle):
 
 
 def test_reference_unit_tests_on_reference_implementation():
-    """test/teb_basics.cpp:5-67 executed on the reference's TimedElasticBand itself."""
-    r = _ref()
-    if r is None:
-        pytest.skip("libteb_ref.so not available")
+    """test/teb_basics.cpp:5-67 executed on the reference's TimedElasticBand itself (its recorded outputs without oracle/_ref)."""
+    r = ref_replay.reference("unit_tests", 0, _ref())
     dt = 0.1; hyst = dt / 3.
     for last, mid in ((dt + 2 * hyst, None), (dt - 2 * hyst, None), (dt - 2 * hyst, dt + 2 * hyst)):
         d = np.full(10, dt); d[9] = last
@@ -290,11 +289,9 @@ def test_f3_h_signatures_and_equivalence_match_reference(oracle, mode):
 @pytest.mark.parametrize("seed", range(40))
 def test_f1_f2_randomized_strip_functions_are_bit_equal_to_reference_code(oracle, seed):
     """Random start / goal / plan / path / pruning / read-out inputs: the oracle's initTrajectoryToGoal x3, updateAndPruneTEB,
-    getVelocityCommand / Profile / FullTrajectory against the reference's own code (needs oracle/_ref)."""
+    getVelocityCommand / Profile / FullTrajectory against the reference's own code (its recorded outputs without oracle/_ref)."""
     from random_strip_cases import random_strip_case, band_for_readout
-    r = _ref()
-    if r is None:
-        pytest.skip("oracle/_ref not available: the committed vectors (ref_f1_*.npz, ref_f2_*.npz) cover the fixed cases")
+    r = ref_replay.reference("f1_f2", seed, _ref())
     c = random_strip_case(seed)
     _same_band(oracle.init_trajectory_line(*c["line"]), r.init_trajectory_line(*c["line"]))
     ref_band, yaw_seen = r.init_trajectory_plan(*c["plan"])
@@ -434,11 +431,9 @@ def test_f3_candidate_cases_cover_both_graphs_and_find_several_classes(oracle):
 @pytest.mark.parametrize("seed", range(40))
 def test_f3_randomized_candidate_generation_is_bit_equal_to_reference_code(oracle, seed):
     """Random scenes (every obstacle class, both graphs, random parameters, optional initial plan): graph, bands, getInitialPlanTEB index
-    and via-point flags of the oracle against the reference's own code run on the same inputs (needs oracle/_ref)."""
+    and via-point flags of the oracle against the reference's own code run on the same inputs (its recorded outputs without oracle/_ref)."""
     from random_explore_cases import random_explore_case
-    r = _ref()
-    if r is None:
-        pytest.skip("oracle/_ref not available: the committed vectors (ref_f3_explore.npz) cover the fixed cases")
+    r = ref_replay.reference("f3_explore", seed, _ref())
     case = random_explore_case(seed)
     ref = G.explore_reference(r, case)
     b, n_tebs, best = renew_on_host(oracle, case, slots=16)
@@ -464,11 +459,10 @@ def test_f3_randomized_candidate_generation_is_bit_equal_to_reference_code(oracl
 @pytest.mark.parametrize("mode", [2, 3])
 def test_f3_randomized_h_signatures_are_bit_equal_to_reference_code(oracle, mode, seed):
     """Random scenes of the optimiser tests (every obstacle class, moving obstacles, ragged bands): both signature classes, isValid,
-    isReasonable and the pairwise isEqual of the reference against the oracle's values and class list (needs oracle/_ref)."""
+    isReasonable and the pairwise isEqual of the reference against the oracle's values and class list (its recorded outputs without
+    oracle/_ref)."""
     from random_cases import random_case
-    r = _ref()
-    if r is None:
-        pytest.skip("oracle/_ref not available: the committed vectors (ref_f3_hsig_*.npz) cover the fixed cases")
+    r = ref_replay.reference("f3_hsig", "%d_%d" % (mode, seed), _ref())
     cfg, obst, via, batch = random_case(seed)
     want = r.h_signatures(cfg, obst, batch, mode, 1.0, 0.1)
     sig = oracle.h_signatures(cfg, obst, batch, mode, 1.0)
@@ -481,9 +475,7 @@ def test_f3_randomized_h_signatures_are_bit_equal_to_reference_code(oracle, mode
 # ---- randomised pin: every option toggled at random, whole optimizeTEB, oracle vs the reference's src/optimal_planner.cpp ----------
 @pytest.mark.parametrize("seed", range(40))
 def test_randomized_optimizeTEB_is_bit_equal_to_reference_code(oracle, seed):
-    r = _ref()
-    if r is None:
-        pytest.skip("libteb_ref.so not available")
+    r = ref_replay.reference("optimize_teb", seed, _ref())      # (its recorded outputs without oracle/_ref)
     sys.path.insert(0, HERE)
     from random_cases import random_case
     cfg, obst, via, batch = random_case(seed)

@@ -26,7 +26,7 @@ def main():
     os.makedirs(DST, exist_ok=True)
     lines = []
     tr = os.path.join(SRC, "trace", "trace_results.db")
-    lines.append("# rocprofv3 --kernel-trace --stats -- python bench.py --steps 10 --warmup 2 --no-cpu-baseline --latency-reps 0")
+    lines.append("# rocprofv3 --kernel-trace --stats -- python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-parity-check --latency-reps 0 --sustain-seconds 0")
     lines.append("# (MI355X, gfx950; durations in microseconds; the single 1-workgroup debug launch of bench.py's association probe is listed separately)")
     lines.append("%-70s %8s %14s %12s %8s" % ("kernel", "calls", "total_us", "avg_us", "pct"))
     for name, calls, total, avg, pct in q(tr, "select name,total_calls,total_duration,average,percentage from top_kernels"):

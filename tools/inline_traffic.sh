@@ -1,6 +1,6 @@
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_inl; mkdir -p $OUT; export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-parity-check --latency-reps 0"
+CMD="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-parity-check --latency-reps 0"
 cd /tmp
 export TEB_AMD_LIB=$ROOT/tools/libteb_amd_inl.so
 rocprofv3 --kernel-trace --stats -d $OUT/trace -o trace -- $CMD > $OUT/bench_trace.json 2> $OUT/trace.log

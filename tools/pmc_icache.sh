@@ -1,6 +1,6 @@
 set -u
 ROOT=$(pwd); OUT=$ROOT/gpurun_out/prof_icache; mkdir -p $OUT; export TMPDIR=/tmp
-CMD="python $ROOT/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-parity-check --latency-reps 0"
+CMD="python $ROOT/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-parity-check --latency-reps 0"
 cd /tmp
 rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE --kernel-trace -d $OUT/ic -o ic -- $CMD > /dev/null 2> $OUT/ic.log
 rocprofv3 --pmc SQ_IFETCH SQ_WAIT_INST_ANY SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_INSTS_SALU --kernel-trace -d $OUT/if -o ifetch -- $CMD > /dev/null 2> $OUT/if.log

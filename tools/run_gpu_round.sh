@@ -10,13 +10,13 @@ timeout 1500 python -m pytest tests -m gpu -q 2>&1 | grep -E "passed|failed|erro
 bash tools/profile.sh > gpurun_out/profile_sh.log 2>&1
 python tools/export_profile.py $TAG >> gpurun_out/profile_sh.log 2>&1
 python tools/phase_split.py c4on c4 c3 c2 > profiles/phase_split_$TAG.txt 2>&1
+python bench.py --full > profiles/bench_$TAG.json 2> profiles/bench_$TAG.err
 cp profiles/*_$TAG* gpurun_out/ 2>/dev/null
 for k in trace fetch write; do cp gpurun_out/prof/bench_$k.json gpurun_out/${TAG}_bench_$k.json; done
 rm -rf gpurun_out/prof
-python bench.py > gpurun_out/bench_$TAG.json 2> gpurun_out/bench_$TAG.err
 python - <<PY
 import json
-d = json.loads(open('gpurun_out/bench_$TAG.json').read().strip().splitlines()[-1])
+d = json.loads(open('profiles/bench_$TAG.json').read().strip().splitlines()[-1])
 r = d['roofline']
 print('value', d['value'], 'ms/step', d['ms_per_step'], 'kernel ms', r['kernel_ms'], 'frac', r['frac'], 'traffic', r['traffic'], r.get('traffic_note'))
 print('phases', r.get('phases', {}).get('share_mean_of_bands'))
