@@ -536,6 +536,33 @@ int  teb_amd_is_trajectory_feasible(teb_amd_handle_t* h, int32_t b, int32_t n_fo
                                     int32_t* first_infeasible);
 
 /*
+ * The costmap's point obstacles, derived on the device — TebLocalPlannerROS::updateObstacleContainerWithCostmap
+ * (src/teb_local_planner_ros.cpp:478-504; what computeVelocityCommands runs every tick when obstacles.include_costmap_obstacles, the
+ * default, and no costmap converter is configured, :343-352) on the grid of the last teb_amd_set_costmap, followed by the caller's own
+ * obstacles (what updateObstacleContainerWithCustomObstacles appends, :352), as the handle's obstacle table. The grid stays in the
+ * handle: teb_amd_is_trajectory_feasible works on it afterwards as before.
+ *   cells visited: mx = 0 .. size_x - 2 (outer loop), my = 0 .. size_y - 2 (inner loop) - the table is mx-major, the last column and
+ *                  the last row are never visited, a grid with size_x == 1 or size_y == 1 yields no cell;
+ *   cell counted:  cells[my * size_x + mx] == 254 (costmap_2d::LETHAL_OBSTACLE; 253 and 255 are not);
+ *   centre:        wx = origin_x + (mx + 0.5) * resolution, wy likewise (costmap_2d::Costmap2D::mapToWorld);
+ *   behind filter: (c, s) = (cos theta, sin theta) of robot_pose (PoseSE2::orientationUnitVec, pose_se2.h:215; std::cos / std::sin on
+ *                  the host), d = (wx - x, wy - y); the cell is skipped iff d.x * c + d.y * s < 0 AND sqrt(d.x^2 + d.y^2) >
+ *                  costmap_obstacles_behind_robot_dist (Eigen dot / norm of Vector2d: plain IEEE products and sums, correctly rounded
+ *                  sqrt). A negative distance is allowed, as in the reference (src/teb_config.cpp:338 only warns).
+ * The result is [n cell obstacles] ++ custom: every cell row TEB_AMD_OBST_POINT at the cell centre, radius 0, velocity 0, not dynamic.
+ * Afterwards the handle behaves exactly as after teb_amd_set_obstacles with that concatenated table (lists, distance path and layout,
+ * H-signature / exploration state, later teb_amd_set_config). robot_pose = (x, y, theta) of robot_pose_; custom may be NULL (no custom
+ * obstacle). *n_costmap (may be NULL) receives n - also when the call fails with TEB_AMD_ERR_CAPACITY; out_x / out_y (may be NULL)
+ * receive the first min(capacity, n) cell centres in table order (what a binding mirrors into its host ObstContainer).
+ * Errors: no costmap set or a bad custom table -> TEB_AMD_ERR_INVALID_ARG; n + custom->count > max_obstacles or more polygon vertices
+ * than max_obstacle_vertices -> TEB_AMD_ERR_CAPACITY. On every error the previous obstacle table and all that is derived from it are
+ * left as they were.
+ */
+int  teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
+                                        const teb_amd_obstacles_t* custom, int32_t* n_costmap, double* out_x, double* out_y,
+                                        int32_t capacity);
+
+/*
  * f3 (arithmetic core) — equivalence classes of the device-resident bands, as HomotopyClassPlanner::calculateEquivalenceClass
  * (homotopy_class_planner.hpp:46-62) computes them for every candidate in renewAndAnalyzeOldTebs: HSignature3d
  * (h_signature.h:281-347; one value per obstacle) when cfg.include_dynamic_obstacles, else HSignature (h_signature.h:96-188; one

@@ -62,7 +62,10 @@ class TebConfig:
             include_dynamic_obstacles=True, obstacle_poses_affected=25, legacy_obstacle_association=False,
             obstacle_association_force_inclusion_factor=1.5, obstacle_association_cutoff_factor=5.0,
             obstacle_proximity_ratio_max_vel=1.0, obstacle_proximity_lower_bound=0.0,
-            obstacle_proximity_upper_bound=0.5)
+            obstacle_proximity_upper_bound=0.5,
+            # the costmap's lethal cells as point obstacles (teb_config.h:306-307; TebBatchSolver.set_obstacles_from_costmap): read by
+            # the caller of the C-ABI, not fields of teb_amd_config_t
+            include_costmap_obstacles=True, costmap_obstacles_behind_robot_dist=1.5)
         self.optim = SimpleNamespace(
             no_inner_iterations=5, no_outer_iterations=4, optimization_activate=True, penalty_epsilon=0.05,
             weight_max_vel_x=2.0, weight_max_vel_y=2.0, weight_max_vel_theta=1.0, weight_acc_lim_x=1.0,

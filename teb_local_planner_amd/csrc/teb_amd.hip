@@ -25,6 +25,7 @@
 #include "teb_comm.hpp"
 #include "teb_rtc.hpp"
 #include "teb_feasibility.hpp"
+#include "teb_costmap_obstacles.hpp"
 
 using namespace tebamd;
 
@@ -241,6 +242,7 @@ struct teb_amd_handle {
   DevBuf<int> cm_out;
   int cm_sx = 0, cm_sy = 0;
   double cm_res = 0, cm_ox = 0, cm_oy = 0;
+  DevBuf<int> cmo_cnt;   // teb_amd_set_obstacles_from_costmap: kept cells per (column, chunk of rows), then their offsets + the total
   std::mt19937 rnd_generator;   // ProbRoadmapGraph::rnd_generator_ (graph_search.h:211): default-seeded 32-bit Mersenne twister
 };
 
@@ -827,7 +829,7 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
   if (h->pack_host) (void)hipHostFree(h->pack_host);
   h->pack_dev.free();
   h->g_adj.free();
-  h->cm_cells.free(); h->cm_fp.free(); h->cm_out.free();
+  h->cm_cells.free(); h->cm_fp.free(); h->cm_out.free(); h->cmo_cnt.free();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -913,14 +915,12 @@ int teb_amd_set_config(teb_amd_handle_t* h, const teb_amd_config_t* cfg) {
   return TEB_AMD_OK;
 }
 
-int teb_amd_set_obstacles(teb_amd_handle_t* h, const teb_amd_obstacles_t* o) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if (!o || o->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "null obstacle table");
+namespace {
+// The host side of an obstacle table (teb_amd_obstacles_t) with the centroids and bounding radii the kernels read; t.voff and the
+// vertices start at 0. Checks the arrays, not the capacities.
+int parse_obstacle_table(const teb_amd_obstacles_t* o, teb_amd_handle::HostObst& t) {
   const int M = o->count;
-  if (M > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
   if (M > 0 && (!o->type || !o->ax || !o->ay)) return fail(TEB_AMD_ERR_INVALID_ARG, "obstacle arrays missing");
-  teb_amd_handle::HostObst t;
   t.type.resize(M); t.dyn.resize(M); t.voff.assign(M + 1, 0);
   t.ax.resize(M); t.ay.resize(M); t.bx.resize(M); t.by.resize(M); t.rad.resize(M); t.vx.resize(M); t.vy.resize(M); t.cx.resize(M); t.cy.resize(M); t.brad.assign(M, 0.0);
   for (int i = 0; i < M; ++i) {
@@ -951,20 +951,47 @@ int teb_amd_set_obstacles(teb_amd_handle_t* h, const teb_amd_obstacles_t* o) {
     }
   }
   t.voff[M] = (int)t.pvx.size();
-  if ((int)t.pvx.size() > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
-  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
-  auto up_d = [&](DevBuf<double>& d, const std::vector<double>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream); };
+  return TEB_AMD_OK;
+}
+
+// Uploads the rows of t to the device table from row `first` on (voff: first .. first + M) and its vertices from 0 on.
+int upload_obstacle_rows(teb_amd_handle* h, const teb_amd_handle::HostObst& t, size_t first) {
+  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p + first, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
+  auto up_d = [&](DevBuf<double>& d, const std::vector<double>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p + first, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream); };
   HIPCHK(up_i(h->o_type, t.type)); HIPCHK(up_i(h->o_dyn, t.dyn)); HIPCHK(up_i(h->o_voff, t.voff));
   HIPCHK(up_d(h->o_ax, t.ax)); HIPCHK(up_d(h->o_ay, t.ay)); HIPCHK(up_d(h->o_bx, t.bx)); HIPCHK(up_d(h->o_by, t.by)); HIPCHK(up_d(h->o_rad, t.rad));
   HIPCHK(up_d(h->o_vx, t.vx)); HIPCHK(up_d(h->o_vy, t.vy)); HIPCHK(up_d(h->o_cx, t.cx)); HIPCHK(up_d(h->o_cy, t.cy)); HIPCHK(up_d(h->o_brad, t.brad));
-  HIPCHK(up_d(h->o_pvx, t.pvx)); HIPCHK(up_d(h->o_pvy, t.pvy));
+  if (!t.pvx.empty()) {
+    HIPCHK(hipMemcpyAsync(h->o_pvx.p, t.pvx.data(), t.pvx.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->o_pvy.p, t.pvy.data(), t.pvy.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
   HIPCHK(hipStreamSynchronize(h->stream));   // the uploads read `t`
-  h->M = M;
+  return TEB_AMD_OK;
+}
+
+// The device rows hold table t: the host mirrors take it over and everything derived from the table is derived again.
+int install_obstacles(teb_amd_handle* h, teb_amd_handle::HostObst&& t) {
+  h->M = (int)t.type.size();
   h->host_type = t.type;
   h->host_cx = t.cx; h->host_cy = t.cy;
   h->hs_prod_valid = false;
   h->hob = std::move(t);
   return commit_obstacles(h);
+}
+}  // namespace
+
+int teb_amd_set_obstacles(teb_amd_handle_t* h, const teb_amd_obstacles_t* o) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (!o || o->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "null obstacle table");
+  if (o->count > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
+  teb_amd_handle::HostObst t;
+  rc = parse_obstacle_table(o, t);
+  if (rc) return rc;
+  if ((int)t.pvx.size() > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
+  rc = upload_obstacle_rows(h, t, 0);
+  if (rc) return rc;
+  return install_obstacles(h, std::move(t));
 }
 
 int teb_amd_set_via_points(teb_amd_handle_t* h, int32_t count, const double* x, const double* y) {
@@ -1710,6 +1737,78 @@ int teb_amd_is_trajectory_feasible(teb_amd_handle_t* h, int32_t b, int32_t nf, c
   if (o) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check: more than 2^22 interpolated samples requested (inscribed radius / angular resolution too small)");
   for (int k = 0; k < count; ++k) { feasible[k] = fe[k]; if (first_infeasible) first_infeasible[k] = fi[k]; }
   return TEB_AMD_OK;
+}
+
+// updateObstacleContainerWithCostmap (kernels in teb_costmap_obstacles.hpp) + the caller's obstacles as the handle's obstacle table
+int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
+                                       const teb_amd_obstacles_t* custom, int32_t* n_costmap, double* out_x, double* out_y,
+                                       int32_t capacity) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: no costmap (teb_amd_set_costmap)");
+  if (!robot_pose || capacity < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: null pose / negative capacity");
+  if (custom && custom->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
+  teb_amd_handle::HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
+  teb_amd_obstacles_t none{};
+  rc = parse_obstacle_table(custom ? custom : &none, tc);
+  if (rc) return rc;
+  if ((int)tc.pvx.size() > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
+  const int mc = (int)tc.type.size();
+
+  // count + scan into scratch: nothing of the live table is touched before the total is known to fit
+  const int ncols = h->cm_sx - 1, nrows = h->cm_sy - 1;
+  int n = 0, chunk = 4, nchunks = 0;
+  const GridDev g{h->cm_cells.p, h->cm_sx, h->cm_sy, h->cm_res, h->cm_ox, h->cm_oy};
+  const CmoFilter f{robot_pose[0], robot_pose[1], std::cos(robot_pose[2]), std::sin(robot_pose[2]), costmap_obstacles_behind_robot_dist};
+  if (ncols > 0 && nrows > 0) {
+    // rows per lane: the smallest of 4, 8, .. 64 that keeps the lanes (= values to scan) within 64 K - a 120 x 120 grid gets 4 rows per
+    // lane (3570 lanes, 56 waves), a 1000 x 1000 grid 16 (62937 lanes); from 4096 x 4096 on the chunk stays 64 and the lanes grow
+    while (chunk < 64 && (size_t)ncols * (size_t)((nrows + chunk - 1) / chunk) > 65536) chunk *= 2;
+    nchunks = (nrows + chunk - 1) / chunk;
+    const size_t lanes = (size_t)ncols * nchunks;
+    if (h->cmo_cnt.n < lanes + 1) { h->cmo_cnt.free(); HIPCHK(h->cmo_cnt.alloc(lanes + 1)); }
+    const dim3 grid((unsigned)((lanes + kCmoThreads - 1) / kCmoThreads));
+    hipLaunchKernelGGL(costmap_obstacles_count_kernel, grid, dim3(kCmoThreads), 0, h->stream, g, f, ncols, nrows, chunk, nchunks, h->cmo_cnt.p);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(costmap_obstacles_scan_kernel, dim3(1), dim3(kCmoScanThreads), 0, h->stream, h->cmo_cnt.p, (int)lanes);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&n, h->cmo_cnt.p + lanes, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  if (n_costmap) *n_costmap = n;
+  if ((long long)n + mc > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "costmap cells + custom obstacles exceed max_obstacles");
+
+  // the cell rows on the device, the custom rows behind them from the host
+  if (n > 0) {
+    const CmoRows r{h->o_type.p, h->o_dyn.p, h->o_voff.p, h->o_ax.p, h->o_ay.p, h->o_bx.p, h->o_by.p, h->o_rad.p, h->o_vx.p, h->o_vy.p,
+                    h->o_cx.p, h->o_cy.p, h->o_brad.p};
+    const size_t lanes = (size_t)ncols * nchunks;
+    hipLaunchKernelGGL(costmap_obstacles_write_kernel, dim3((unsigned)((lanes + kCmoThreads - 1) / kCmoThreads)), dim3(kCmoThreads), 0,
+                       h->stream, g, f, ncols, nrows, chunk, nchunks, h->cmo_cnt.p, r);
+    HIPCHK(hipGetLastError());
+  }
+  rc = upload_obstacle_rows(h, tc, (size_t)n);   // (ends in a stream synchronisation)
+  if (rc) return rc;
+
+  // host mirror: the n cell centres (one copy back) ++ the custom rows, exactly what teb_amd_set_obstacles would hold
+  teb_amd_handle::HostObst t;
+  t.ax.resize(n); t.ay.resize(n);
+  if (n > 0) {
+    HIPCHK(hipMemcpyAsync(t.ax.data(), h->o_ax.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(t.ay.data(), h->o_ay.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  t.type.assign(n, TEB_AMD_OBST_POINT); t.dyn.assign(n, 0); t.voff.assign(n, 0);
+  t.bx.assign(n, 0.0); t.by.assign(n, 0.0); t.rad.assign(n, 0.0); t.vx.assign(n, 0.0); t.vy.assign(n, 0.0); t.brad.assign(n, 0.0);
+  t.cx = t.ax; t.cy = t.ay;
+  if (out_x) std::copy(t.ax.begin(), t.ax.begin() + std::min(capacity, n), out_x);
+  if (out_y) std::copy(t.ay.begin(), t.ay.begin() + std::min(capacity, n), out_y);
+  auto app = [](auto& a, const auto& b) { a.insert(a.end(), b.begin(), b.end()); };
+  app(t.type, tc.type); app(t.dyn, tc.dyn); app(t.voff, tc.voff);
+  app(t.ax, tc.ax); app(t.ay, tc.ay); app(t.bx, tc.bx); app(t.by, tc.by); app(t.rad, tc.rad); app(t.vx, tc.vx); app(t.vy, tc.vy);
+  app(t.cx, tc.cx); app(t.cy, tc.cy); app(t.brad, tc.brad);
+  t.pvx = std::move(tc.pvx); t.pvy = std::move(tc.pvy);
+  return install_obstacles(h, std::move(t));
 }
 
 namespace {

@@ -1,0 +1,99 @@
+// teb_costmap_obstacles.hpp — TebLocalPlannerROS::updateObstacleContainerWithCostmap (src/teb_local_planner_ros.cpp:478-504) on the
+// costmap grid of teb_amd_set_costmap: one PointObstacle per LETHAL_OBSTACLE cell that is not far behind the robot, written straight
+// into the rows of the handle's obstacle table, in the reference's order.
+//
+// The reference loops mx (outer) over the columns and my (inner) over the rows of a row-major grid, so the table order is transposed
+// with respect to memory. This is an order-preserving stream compaction in three launches:
+//   count: one lane per (column, chunk of rows); lanes run along mx, so a wave reads 64 neighbouring bytes of one row at a time.
+//          Each lane writes the number of kept cells of its chunk to cnt[mx * nchunks + chunk] - (column, chunk) order is table order.
+//   scan:  one workgroup turns cnt into exclusive offsets in place and appends the total (cnt[ncols * nchunks]), the only value the
+//          host reads back before it decides whether the table fits.
+//   write: each lane walks its chunk again and writes its kept cells from its offset on, in row order.
+// Both passes evaluate the one predicate below, so the counts and the writes cannot disagree.
+#pragma once
+#include "teb_feasibility.hpp"
+
+namespace tebamd {
+
+constexpr int kCmoThreads = 256;
+constexpr int kCmoScanThreads = 1024;
+
+// robot_pose_ and costmap_obstacles_behind_robot_dist; (c, s) = PoseSE2::orientationUnitVec (pose_se2.h:215), computed on the host
+// with std::cos / std::sin so that the bits are glibc's
+struct CmoFilter {
+  double rx, ry, c, s, dist;
+};
+
+// The rows of the obstacle table the write pass fills (SceneDev order of teb_amd_set_obstacles).
+struct CmoRows {
+  int *type, *dyn, *voff;
+  double *ax, *ay, *bx, *by, *rad, *vx, *vy, *cx, *cy, *brad;
+};
+
+// Cell (mx, my) becomes a point obstacle at (wx, wy). Plain IEEE products and sums (-ffp-contract=off): Eigen's dot and norm of a
+// Vector2d; sqrt is correctly rounded.
+__device__ __forceinline__ bool costmap_point_obstacle(const GridDev& g, const CmoFilter& f, int mx, int my, double& wx, double& wy) {
+  if (g.cells[(size_t)my * (size_t)g.sx + (size_t)mx] != 254) return false;   // costmap_2d::LETHAL_OBSTACLE
+  wx = g.ox + (mx + 0.5) * g.res;   // costmap_2d::Costmap2D::mapToWorld
+  wy = g.oy + (my + 0.5) * g.res;
+  const double dx = wx - f.rx, dy = wy - f.ry;
+  return !(dx * f.c + dy * f.s < 0 && sqrt(dx * dx + dy * dy) > f.dist);
+}
+
+__global__ void __launch_bounds__(kCmoThreads) costmap_obstacles_count_kernel(GridDev g, CmoFilter f, int ncols, int nrows, int chunk,
+                                                                              int nchunks, int* cnt) {
+  const size_t t = (size_t)blockIdx.x * kCmoThreads + threadIdx.x;
+  if (t >= (size_t)ncols * nchunks) return;
+  const int mx = (int)(t % ncols), ch = (int)(t / ncols);
+  const int y1 = min(ch * chunk + chunk, nrows);
+  int k = 0;
+  double wx, wy;
+  for (int my = ch * chunk; my < y1; ++my) k += costmap_point_obstacle(g, f, mx, my, wx, wy) ? 1 : 0;
+  cnt[(size_t)mx * nchunks + ch] = k;
+}
+
+// Exclusive scan of cnt[0 .. n) in place, total to cnt[n]: every thread sums one contiguous segment, the workgroup scans the segment
+// sums in LDS, every thread rewrites its segment. n is at most 64 K values up to a 2048 x 2048 grid, 262 K at 4096 x 4096.
+__global__ void __launch_bounds__(kCmoScanThreads) costmap_obstacles_scan_kernel(int* cnt, int n) {
+  __shared__ int part[kCmoScanThreads];
+  const int tid = threadIdx.x;
+  const int per = (n + kCmoScanThreads - 1) / kCmoScanThreads;
+  const int b = min(tid * per, n), e = min(b + per, n);
+  int s = 0;
+  for (int i = b; i < e; ++i) s += cnt[i];
+  part[tid] = s;
+  __syncthreads();
+  for (int d = 1; d < kCmoScanThreads; d <<= 1) {   // inclusive Hillis-Steele scan of the segment sums
+    const int v = tid >= d ? part[tid - d] : 0;
+    __syncthreads();
+    part[tid] += v;
+    __syncthreads();
+  }
+  int run = tid > 0 ? part[tid - 1] : 0;
+  for (int i = b; i < e; ++i) {
+    const int c = cnt[i];
+    cnt[i] = run;
+    run += c;
+  }
+  if (tid == kCmoScanThreads - 1) cnt[n] = part[tid];
+}
+
+__global__ void __launch_bounds__(kCmoThreads) costmap_obstacles_write_kernel(GridDev g, CmoFilter f, int ncols, int nrows, int chunk,
+                                                                              int nchunks, const int* off, CmoRows r) {
+  const size_t t = (size_t)blockIdx.x * kCmoThreads + threadIdx.x;
+  if (t >= (size_t)ncols * nchunks) return;
+  const int mx = (int)(t % ncols), ch = (int)(t / ncols);
+  const int y1 = min(ch * chunk + chunk, nrows);
+  int o = off[(size_t)mx * nchunks + ch];
+  double wx, wy;
+  for (int my = ch * chunk; my < y1; ++my) {
+    if (!costmap_point_obstacle(g, f, mx, my, wx, wy)) continue;
+    // what teb_amd_set_obstacles derives for a TEB_AMD_OBST_POINT row with radius 0, velocity 0, not dynamic, no vertices
+    r.type[o] = TEB_AMD_OBST_POINT; r.dyn[o] = 0; r.voff[o] = 0;
+    r.ax[o] = wx; r.ay[o] = wy; r.bx[o] = 0.0; r.by[o] = 0.0; r.rad[o] = 0.0; r.vx[o] = 0.0; r.vy[o] = 0.0;
+    r.cx[o] = wx; r.cy[o] = wy; r.brad[o] = 0.0;
+    ++o;
+  }
+}
+
+}  // namespace tebamd

@@ -104,6 +104,7 @@ def lib():
         L.teb_amd_hcp_params_default.restype = None
         L.teb_amd_set_costmap.argtypes = [vp, C.c_void_p, i32, i32, d, d, d]
         L.teb_amd_is_trajectory_feasible.argtypes = [vp, i32, i32, _abi.p_f64, _abi.p_f64, d, d, i32, d, _abi.p_i32, _abi.p_i32]
+        L.teb_amd_set_obstacles_from_costmap.argtypes = [vp, _abi.p_f64, d, C.POINTER(_abi.Obstacles), _abi.p_i32, _abi.p_f64, _abi.p_f64, i32]
         # multi-GPU exchange
         L.teb_amd_comm_unique_id.argtypes = [C.c_char_p]
         L.teb_amd_comm_create.argtypes = [C.c_char_p, i32, i32, i32, C.POINTER(vp)]
@@ -131,7 +132,7 @@ class TebBatchSolver:
         _chk(lib().teb_amd_create_ex(C.byref(c), max_tebs, max_poses, max_obstacles, max_obstacle_vertices,
                                      max_via_points, device, C.c_void_p(stream) if stream else None,
                                      C.byref(options) if options is not None else None, C.byref(self._h)), "teb_amd_create_ex")
-        self.max_tebs, self.max_poses = max_tebs, max_poses
+        self.max_tebs, self.max_poses, self.max_obstacles = max_tebs, max_poses, max_obstacles
         self.count = 0
 
     def close(self):
@@ -408,6 +409,21 @@ class TebBatchSolver:
         cells = np.ascontiguousarray(cells, dtype=np.uint8)
         _chk(lib().teb_amd_set_costmap(self._h, cells.ctypes.data_as(C.c_void_p), cells.shape[1], cells.shape[0], float(resolution),
                                        float(origin_x), float(origin_y)), "teb_amd_set_costmap")
+
+    def set_obstacles_from_costmap(self, robot_pose, costmap_obstacles_behind_robot_dist, custom=None):
+        """updateObstacleContainerWithCostmap (reference src/teb_local_planner_ros.cpp:478-504) on the grid of the last set_costmap,
+        followed by the custom ObstacleTable (or None), as the obstacle table. Returns (n, xs, ys): the number of cell obstacles and
+        their centres in table order."""
+        pose = _abi.f64([float(v) for v in robot_pose[:3]])
+        cap = max(int(self.max_obstacles), 1)
+        n = C.c_int32(0)
+        xs = np.zeros(cap); ys = np.zeros(cap)
+        _chk(lib().teb_amd_set_obstacles_from_costmap(self._h, _abi._ptr(pose, C.c_double), float(costmap_obstacles_behind_robot_dist),
+                                                      C.byref(custom.freeze()) if custom is not None else None, C.byref(n),
+                                                      _abi._ptr(xs, C.c_double), _abi._ptr(ys, C.c_double), cap),
+             "teb_amd_set_obstacles_from_costmap")
+        self._n_obst = n.value + (len(custom) if custom is not None else 0)
+        return n.value, xs[:n.value].copy(), ys[:n.value].copy()
 
     def is_trajectory_feasible(self, b, footprint, inscribed_radius, min_resolution_collision_check_angular=3.141592653589793,
                                look_ahead_idx=-1, feasibility_check_lookahead_distance=-1.0):
