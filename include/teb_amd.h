@@ -563,6 +563,42 @@ int  teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot
                                         int32_t capacity);
 
 /*
+ * The costmap's lethal cells as a few convex obstacles, converted on the device — what computeVelocityCommands runs instead of the
+ * point loop when obstacles.costmap_converter_plugin is set (teb_config.h:139; src/teb_local_planner_ros.cpp:345-349):
+ * updateObstacleContainerWithCostmapConverter (:506-549) over the polygons a converter makes from the grid of the last
+ * teb_amd_set_costmap, followed by the caller's own obstacles (:352), as the handle's obstacle table. The conversion rule:
+ *   cells kept:  exactly those teb_amd_set_obstacles_from_costmap keeps (same visit domain, value 254 only, same behind filter; a
+ *                distance of +inf switches the filter off);
+ *   tiles:       T = tile_cells (1 .. 64); tile (tx, ty) covers mx in [tx*T, tx*T + T), my in [ty*T, ty*T + T), clipped to the visit
+ *                domain; components are the 8-connected kept cells of one tile (they never cross a tile border, which bounds the
+ *                over-approximation: a hull of whole rows of walls would cover the room between them);
+ *   row:         the convex hull of a component's cell indices (mx, my), Andrew's monotone chain on integers with strict turns only
+ *                (no vertex collinear with its neighbours): 1 vertex -> TEB_AMD_OBST_POINT; 2 -> TEB_AMD_OBST_LINE from the
+ *                lexicographically smallest to the largest (mx, my); 3 or more -> TEB_AMD_OBST_POLYGON, counter-clockwise from the
+ *                lexicographically smallest vertex, no repeated closing vertex (the reference's 1 / 2 / more vertices cases);
+ *   vertex:      cell (mx, my) at (origin_x + (mx + 0.5) * resolution, origin_y + (my + 0.5) * resolution), the point route's bits;
+ *                radius 0, velocity 0, not dynamic; centroids and bounding radii as teb_amd_set_obstacles derives them;
+ *   order:       tiles tx outer, ty inner (the point route's cell order); inside a tile by the smallest (mx, my) cell of the
+ *                component; then the custom rows.
+ * With T = 1 the table is the one teb_amd_set_obstacles_from_costmap makes; every kept cell centre lies in the closed hull of its row.
+ * Afterwards the handle behaves exactly as after teb_amd_set_obstacles with [converted rows] ++ custom (lists, distance path and
+ * layout, H-signature / exploration state, later teb_amd_set_config). robot_pose = (x, y, theta); custom may be NULL.
+ * *n_obstacles and *n_points (each may be NULL) receive the number of converted rows and of their vertices (every row's, ObstacleMsg
+ * style) - also when the call fails with TEB_AMD_ERR_CAPACITY. out_offset [capacity_obstacles + 1], out_x / out_y [capacity_points]
+ * (may be NULL) receive the converted rows as a polygon list - row i has the vertices out_offset[i] .. out_offset[i + 1] - 1 - what a
+ * binding mirrors into its host ObstContainer; they are written only when n_obstacles <= capacity_obstacles and n_points <=
+ * capacity_points.
+ * Errors: no costmap set, tile_cells outside 1 .. 64, a negative capacity, a null pose or a bad custom table -> TEB_AMD_ERR_INVALID_ARG;
+ * converted rows + custom->count > max_obstacles, or converted polygon vertices + custom polygon vertices > max_obstacle_vertices ->
+ * TEB_AMD_ERR_CAPACITY. On every error the previous obstacle table and all that is derived from it are left as they were.
+ */
+int  teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const double* robot_pose,
+                                                 double costmap_obstacles_behind_robot_dist, int32_t tile_cells,
+                                                 const teb_amd_obstacles_t* custom, int32_t* n_obstacles, int32_t* n_points,
+                                                 int32_t* out_offset, double* out_x, double* out_y, int32_t capacity_obstacles,
+                                                 int32_t capacity_points);
+
+/*
  * f3 (arithmetic core) — equivalence classes of the device-resident bands, as HomotopyClassPlanner::calculateEquivalenceClass
  * (homotopy_class_planner.hpp:46-62) computes them for every candidate in renewAndAnalyzeOldTebs: HSignature3d
  * (h_signature.h:281-347; one value per obstacle) when cfg.include_dynamic_obstacles, else HSignature (h_signature.h:96-188; one

@@ -181,6 +181,27 @@ class ObstacleTable:
             verts = verts[:-1]
         return self._add(OBST_POLYGON, verts=verts, vel=vel)
 
+    @classmethod
+    def from_polygon_list(cls, offset, xs, ys):
+        """Rows from a polygon list (ObstacleMsg style: row i has the vertices offset[i] .. offset[i + 1] - 1, taken as given) as
+        updateObstacleContainerWithCostmapConverter turns them into obstacles (reference src/teb_local_planner_ros.cpp:506-549):
+        1 vertex a point, 2 a line, more a polygon; radius 0, velocity 0, not dynamic."""
+        off = np.asarray(offset, np.int64)
+        xs, ys = np.asarray(xs, np.float64), np.asarray(ys, np.float64)
+        n = len(off) - 1
+        k = np.diff(off)
+        first, second = off[:-1], np.minimum(off[:-1] + 1, max(len(xs) - 1, 0))
+        line, poly = k == 2, k > 2
+        t = cls()
+        t.type = np.where(k == 1, OBST_POINT, np.where(line, OBST_LINE, OBST_POLYGON)).tolist()
+        t.ax, t.ay = np.where(poly, 0.0, xs[first]).tolist(), np.where(poly, 0.0, ys[first]).tolist()
+        t.bx, t.by = np.where(line, xs[second], 0.0).tolist(), np.where(line, ys[second], 0.0).tolist()
+        t.radius, t.vx, t.vy, t.dynamic = [0.0] * n, [0.0] * n, [0.0] * n, [0] * n
+        take = np.repeat(poly, k)   # the vertices of the polygon rows
+        t.vert_x, t.vert_y = xs[:len(take)][take].tolist(), ys[:len(take)][take].tolist()
+        t.vert_offset = [0] + np.cumsum(np.where(poly, k, 0)).tolist()
+        return t
+
     def __len__(self):
         return len(self.type)
 

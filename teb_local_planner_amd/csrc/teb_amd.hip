@@ -26,6 +26,7 @@
 #include "teb_rtc.hpp"
 #include "teb_feasibility.hpp"
 #include "teb_costmap_obstacles.hpp"
+#include "teb_costmap_polygons.hpp"
 
 using namespace tebamd;
 
@@ -243,6 +244,10 @@ struct teb_amd_handle {
   int cm_sx = 0, cm_sy = 0;
   double cm_res = 0, cm_ox = 0, cm_oy = 0;
   DevBuf<int> cmo_cnt;   // teb_amd_set_obstacles_from_costmap: kept cells per (column, chunk of rows), then their offsets + the total
+  // teb_amd_set_obstacles_from_costmap_polygons: rows / vertices / polygon vertices per block (then their offsets + totals), and the
+  // converted rows (first-vertex offsets, vertex coordinates) before the host builds the table from them
+  DevBuf<int> cmp_cnt, cmp_off;
+  DevBuf<double> cmp_x, cmp_y;
   std::mt19937 rnd_generator;   // ProbRoadmapGraph::rnd_generator_ (graph_search.h:211): default-seeded 32-bit Mersenne twister
 };
 
@@ -830,6 +835,7 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
   h->pack_dev.free();
   h->g_adj.free();
   h->cm_cells.free(); h->cm_fp.free(); h->cm_out.free(); h->cmo_cnt.free();
+  h->cmp_cnt.free(); h->cmp_off.free(); h->cmp_x.free(); h->cmp_y.free();
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -1808,6 +1814,109 @@ int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_
   app(t.ax, tc.ax); app(t.ay, tc.ay); app(t.bx, tc.bx); app(t.by, tc.by); app(t.rad, tc.rad); app(t.vx, tc.vx); app(t.vy, tc.vy);
   app(t.cx, tc.cx); app(t.cy, tc.cy); app(t.brad, tc.brad);
   t.pvx = std::move(tc.pvx); t.pvy = std::move(tc.pvy);
+  return install_obstacles(h, std::move(t));
+}
+
+// The converter slot of computeVelocityCommands (updateObstacleContainerWithCostmapConverter, src/teb_local_planner_ros.cpp:506-549)
+// fed by the device: the costmap's lethal cells as convex points / lines / polygons (kernels in teb_costmap_polygons.hpp) + the
+// caller's obstacles as the handle's obstacle table
+int teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
+                                                int32_t tile_cells, const teb_amd_obstacles_t* custom, int32_t* n_obstacles,
+                                                int32_t* n_points, int32_t* out_offset, double* out_x, double* out_y,
+                                                int32_t capacity_obstacles, int32_t capacity_points) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  const char* fn = "teb_amd_set_obstacles_from_costmap_polygons: ";
+  if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "no costmap (teb_amd_set_costmap)");
+  if (!robot_pose || capacity_obstacles < 0 || capacity_points < 0)
+    return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null pose / negative capacity");
+  if (tile_cells < 1 || tile_cells > kCmpMaxTile) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "tile_cells outside 1 .. 64");
+  if (custom && custom->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
+  teb_amd_handle::HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
+  teb_amd_obstacles_t none{};
+  rc = parse_obstacle_table(custom ? custom : &none, tc);
+  if (rc) return rc;
+  const int mc = (int)tc.type.size();
+
+  // count + scan over blocks into scratch; the host reads the three totals back and decides whether the table fits
+  const int ncols = h->cm_sx - 1, nrows = h->cm_sy - 1, T = tile_cells;
+  int tot[3] = {0, 0, 0};   // rows, vertices, polygon vertices
+  const GridDev g{h->cm_cells.p, h->cm_sx, h->cm_sy, h->cm_res, h->cm_ox, h->cm_oy};
+  const CmoFilter f{robot_pose[0], robot_pose[1], std::cos(robot_pose[2]), std::sin(robot_pose[2]), costmap_obstacles_behind_robot_dist};
+  CmpGeom q{ncols, nrows, T, kCmpSlots / (T * T), 0, 0};
+  int nblk = 0;
+  if (ncols > 0 && nrows > 0) {
+    q.nty = (nrows + T - 1) / T;
+    q.nby = (q.nty + q.k - 1) / q.k;
+    const long long nb = (long long)((ncols + T - 1) / T) * q.nby;
+    if (nb > (1 << 30)) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "grid too large");
+    nblk = (int)nb;
+    const size_t need = 3 * ((size_t)nblk + 1);
+    if (h->cmp_cnt.n < need) { h->cmp_cnt.free(); HIPCHK(h->cmp_cnt.alloc(need)); }
+    hipLaunchKernelGGL(costmap_polygons_count_kernel, dim3((unsigned)nblk), dim3(kCmpThreads), 0, h->stream, g, f, q, nblk, h->cmp_cnt.p);
+    HIPCHK(hipGetLastError());
+    for (int a = 0; a < 3; ++a) {
+      int* c = h->cmp_cnt.p + (size_t)a * (nblk + 1);
+      hipLaunchKernelGGL(costmap_obstacles_scan_kernel, dim3(1), dim3(kCmoScanThreads), 0, h->stream, c, nblk);
+      HIPCHK(hipGetLastError());
+      HIPCHK(hipMemcpyAsync(&tot[a], c + nblk, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  const int nr = tot[0], nv = tot[1];
+  if (n_obstacles) *n_obstacles = nr;
+  if (n_points) *n_points = nv;
+  if ((long long)nr + mc > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "converted costmap rows + custom obstacles exceed max_obstacles");
+  if ((long long)tot[2] + (long long)tc.pvx.size() > h->max_verts)
+    return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
+
+  // the converted rows into scratch and back: first-vertex offsets and vertex coordinates (world), in table order
+  std::vector<int> off(nr + 1, nv);
+  std::vector<double> px(nv), py(nv);
+  if (nr > 0) {
+    if (h->cmp_off.n < (size_t)nr) { h->cmp_off.free(); HIPCHK(h->cmp_off.alloc(nr)); }
+    if (h->cmp_x.n < (size_t)nv) { h->cmp_x.free(); h->cmp_y.free(); HIPCHK(h->cmp_x.alloc(nv)); HIPCHK(h->cmp_y.alloc(nv)); }
+    const CmpOut o{h->cmp_off.p, h->cmp_x.p, h->cmp_y.p};
+    hipLaunchKernelGGL(costmap_polygons_write_kernel, dim3((unsigned)nblk), dim3(kCmpThreads), 0, h->stream, g, f, q, nblk, h->cmp_cnt.p, o);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(off.data(), h->cmp_off.p, nr * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(px.data(), h->cmp_x.p, nv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(py.data(), h->cmp_y.p, nv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+
+  // as an obstacle table (1 vertex: point, 2: line, more: polygon; radius 0, velocity 0, not dynamic) through teb_amd_set_obstacles'
+  // parse, so that centroids and bounding radii are the same code; then the custom rows behind it
+  std::vector<int> type(nr), voff(nr + 1, 0);
+  std::vector<double> ax(nr), ay(nr), bx(nr, 0.0), by(nr, 0.0), pgx, pgy;
+  for (int i = 0; i < nr; ++i) {
+    const int k0 = off[i], k = off[i + 1] - k0;
+    type[i] = k == 1 ? TEB_AMD_OBST_POINT : k == 2 ? TEB_AMD_OBST_LINE : TEB_AMD_OBST_POLYGON;
+    ax[i] = k <= 2 ? px[k0] : 0.0; ay[i] = k <= 2 ? py[k0] : 0.0;   // a polygon is its vertices (ObstacleTable.add_polygon)
+    if (k == 2) { bx[i] = px[k0 + 1]; by[i] = py[k0 + 1]; }
+    if (k >= 3) { pgx.insert(pgx.end(), px.begin() + k0, px.begin() + k0 + k); pgy.insert(pgy.end(), py.begin() + k0, py.begin() + k0 + k); }
+    voff[i + 1] = (int)pgx.size();
+  }
+  teb_amd_obstacles_t ct{};
+  ct.count = nr; ct.type = type.data(); ct.ax = ax.data(); ct.ay = ay.data(); ct.bx = bx.data(); ct.by = by.data();
+  ct.vert_offset = voff.data(); ct.vert_x = pgx.data(); ct.vert_y = pgy.data();
+  teb_amd_handle::HostObst t;
+  rc = parse_obstacle_table(&ct, t);
+  if (rc) return rc;
+  const int shift = (int)t.pvx.size();
+  auto app = [](auto& a, const auto& b) { a.insert(a.end(), b.begin(), b.end()); };
+  t.voff.pop_back();
+  for (int v : tc.voff) t.voff.push_back(v + shift);
+  app(t.type, tc.type); app(t.dyn, tc.dyn);
+  app(t.ax, tc.ax); app(t.ay, tc.ay); app(t.bx, tc.bx); app(t.by, tc.by); app(t.rad, tc.rad); app(t.vx, tc.vx); app(t.vy, tc.vy);
+  app(t.cx, tc.cx); app(t.cy, tc.cy); app(t.brad, tc.brad); app(t.pvx, tc.pvx); app(t.pvy, tc.pvy);
+  if (out_offset && out_x && out_y && nr <= capacity_obstacles && nv <= capacity_points) {
+    std::copy(off.begin(), off.end(), out_offset);
+    std::copy(px.begin(), px.end(), out_x);
+    std::copy(py.begin(), py.end(), out_y);
+  }
+  rc = upload_obstacle_rows(h, t, 0);
+  if (rc) return rc;
   return install_obstacles(h, std::move(t));
 }
 

@@ -30,12 +30,17 @@ struct CmoRows {
   double *ax, *ay, *bx, *by, *rad, *vx, *vy, *cx, *cy, *brad;
 };
 
+// costmap_2d::Costmap2D::mapToWorld: the centre of cell (mx, my) (also the vertices of teb_costmap_polygons.hpp)
+__device__ __forceinline__ void costmap_cell_centre(const GridDev& g, int mx, int my, double& wx, double& wy) {
+  wx = g.ox + (mx + 0.5) * g.res;
+  wy = g.oy + (my + 0.5) * g.res;
+}
+
 // Cell (mx, my) becomes a point obstacle at (wx, wy). Plain IEEE products and sums (-ffp-contract=off): Eigen's dot and norm of a
 // Vector2d; sqrt is correctly rounded.
 __device__ __forceinline__ bool costmap_point_obstacle(const GridDev& g, const CmoFilter& f, int mx, int my, double& wx, double& wy) {
   if (g.cells[(size_t)my * (size_t)g.sx + (size_t)mx] != 254) return false;   // costmap_2d::LETHAL_OBSTACLE
-  wx = g.ox + (mx + 0.5) * g.res;   // costmap_2d::Costmap2D::mapToWorld
-  wy = g.oy + (my + 0.5) * g.res;
+  costmap_cell_centre(g, mx, my, wx, wy);
   const double dx = wx - f.rx, dy = wy - f.ry;
   return !(dx * f.c + dy * f.s < 0 && sqrt(dx * dx + dy * dy) > f.dist);
 }
