@@ -31,9 +31,12 @@ HEADERS = ["teb_device.hpp", "teb_comm.hpp", "teb_feasibility.hpp", "teb_costmap
 #   -DTEB_AMD_SOLVE_CSR everywhere   : headline + 3.2 %.
 # Neither is within the 0.5 % the verdict set for shipping it, so the kinds every default user launches (defaults / wide / generic-shape
 # defaults) keep the cheap call, the kinds off the defaults keep -DTEB_AMD_SOLVE_CSR (UNIT_FLAGS below), and the net under all of them
-# is tests/test_gpu_every_instantiation.py: EVERY pre-built (layout, Jacobian mode, kind) is launched once, on the configuration paths
-# that faulted before - the fault is deterministic at the first solve, so a unit whose register allocation moved into it fails the
-# GPU test suite of its build, not a robot. Kernels compiled at run time take the plain convention (csrc/teb_rtc.hpp).
+# is tests/test_gpu_every_instantiation.py: EVERY pre-built (layout, Jacobian mode, kind) is launched on the configuration's own schedule,
+# on the configuration paths that faulted before, and its bands are compared - every specialised kind bit for bit with its generic twin
+# (a -DTEB_AMD_SOLVE_CSR unit), every run with helpers bit for bit with the same scene without, every case with the CPU oracle. So a unit
+# whose register allocation moved into the miscompile fails the GPU test suite of its build whether it faults at the first solve or
+# returns finite, wrong poses; tests/test_instantiation_table.py keeps the tool's cases in step with _units() and UNIT_FLAGS. Kernels
+# compiled at run time take the plain convention (csrc/teb_rtc.hpp).
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off"]
 
 # Per-unit flags of the product. -DTEB_AMD_POINTS_KEEP_GENERIC on the point-like band-layout instantiation (the headline's kernel): it
