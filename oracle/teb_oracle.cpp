@@ -551,6 +551,19 @@ struct SignedVel {  // v = dist/dt * fast_sigmoid(100 * deltaS . (cos th_a, sin 
   double dv[7];
 };
 
+// k' of the arc-length factor k = angle_diff / (2 sin h), h = angle_diff / 2: (sin h - h cos h) / (2 sin^2 h), the numerator from its series
+// below |h| = 0.25 (the subtraction loses 3 / h^2 of its digits); the twin of arc_factor_slope in csrc/teb_edges.hpp, term for term
+inline double arc_factor_slope(double h, double sh, double ch) {
+  double num;
+  if (std::fabs(h) < 0.25) {
+    const double z = h * h;
+    num = h * z * (1.0 / 3 + z * (-1.0 / 30 + z * (1.0 / 840 + z * (-1.0 / 45360 + z * (1.0 / 3991680 + z * (-1.0 / 518918400))))));
+  } else {
+    num = sh - h * ch;
+  }
+  return num / (2 * sh * sh);
+}
+
 inline void signed_velocity(const teb_amd_config_t& c, double xa, double ya, double tha, double xb, double yb,
                             double thb, double dt, SignedVel& o, bool want_grad) {
   double dx = xb - xa, dy = yb - ya;
@@ -577,7 +590,7 @@ inline void signed_velocity(const teb_amd_config_t& c, double xa, double ya, dou
   if (arc) {
     double h = angle_diff / 2, sh = std::sin(h), ch = std::cos(h);
     k = angle_diff / (2 * sh);
-    kp = 1.0 / (2 * sh) - angle_diff * ch / (4 * sh * sh);
+    kp = arc_factor_slope(h, sh, ch);
     if (k < 0) { k = -k; kp = -kp; }  // fabs
   }
   // d(dist)/d(...)

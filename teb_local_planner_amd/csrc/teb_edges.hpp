@@ -48,6 +48,21 @@ __device__ __forceinline__ double pen_below(double var, double a, double eps, do
 
 // v = dist/dt * fast_sigmoid(100 * deltaS.(cos th_a, sin th_a)), omega = normalize(th_b - th_a)/dt.
 // dv[7] = dv/d(xa, ya, tha, xb, yb, thb, dt) when JAC.
+// d/d(angle_diff) of the arc-length factor k = angle_diff / (2 sin h), h = angle_diff / 2:  k' = (sin h - h cos h) / (2 sin^2 h).
+// The numerator loses 3 / h^2 of its digits when the two terms are subtracted as they stand (1e-12 relative at angle_diff = 0.05, the
+// ordinary near-straight segment: tests/test_hp_linearize.py, velocity_exact_arc), so below |h| = 0.25 it is summed from its series
+// h^3 / 3 - h^5 / 30 + h^7 / 840 - ... (next term < 2e-18 of the first). oracle/teb_oracle.cpp: arc_factor_slope is the twin.
+__device__ __forceinline__ double arc_factor_slope(double h, double sh, double ch) {
+  double num;
+  if (fabs(h) < 0.25) {
+    const double z = h * h;
+    num = h * z * (1.0 / 3 + z * (-1.0 / 30 + z * (1.0 / 840 + z * (-1.0 / 45360 + z * (1.0 / 3991680 + z * (-1.0 / 518918400))))));
+  } else {
+    num = sh - h * ch;
+  }
+  return num / (2 * sh * sh);
+}
+
 template <bool JAC>
 __device__ __forceinline__ void signed_velocity(const teb_amd_config_t& c, double xa, double ya, double tha, double ca,
                                                 double sa, double xb, double yb, double thb, double dt, double& v,
@@ -73,7 +88,7 @@ __device__ __forceinline__ void signed_velocity(const teb_amd_config_t& c, doubl
     if (arc) {
       double h = angle_diff / 2, sh = sin(h), ch = cos(h);
       k = angle_diff / (2 * sh);
-      kp = 1.0 / (2 * sh) - angle_diff * ch / (4 * sh * sh);
+      kp = arc_factor_slope(h, sh, ch);
       if (k < 0) { k = -k; kp = -kp; }
     }
     double ddx = 0, ddy = 0;
