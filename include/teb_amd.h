@@ -665,6 +665,53 @@ int  teb_amd_last_shader_clock_mhz(teb_amd_handle_t* h, double* mhz);
 /* LDS bytes per workgroup and the largest pose count this build can optimise. */
 int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_poses_supported);
 
+/*
+ * ---- Fleet batches: the bands of many scenes in ONE launch -----------------------------------------------------------------------
+ * A handle can hold a SET of scenes (an obstacle table and a via-point list each) and a band -> scene map; teb_amd_optimize_batch then
+ * runs every band against its own scene, one workgroup per band, one launch. Many robots with a few candidates each fill the device
+ * the way one robot's candidates cannot. Configuration and footprint stay per handle (a homogeneous fleet).
+ *
+ * Contract: every band ends with the bits it has in a single-scene handle that holds only its scene, with the same capacities, layout
+ * and the options generic_config_path = 1, multi_cu = -1, speculative_trials = -1 - provided that handle runs the same distance path
+ * as the fleet: the point-like path iff EVERY scene and the footprint are point-like and the LDS cache of the largest scene fits,
+ * the generic one otherwise (a point-like scene inside a generic fleet equals its handle with generic_distance_path = 1).
+ *
+ *   teb_amd_set_scenes       installs n_scenes scenes (1 <= n_scenes <= max_tebs) and enters fleet mode. The fleet storage is a second
+ *                            set of device buffers, allocated at the first call and sized by the handle's capacities: sum of the rows
+ *                            <= max_obstacles, sum of the polygon vertices <= max_obstacle_vertices, sum of the via-points <=
+ *                            max_via_points. via_count NULL = no via-points; via_x / via_y hold the lists of the scenes one after the
+ *                            other. Everything is parsed and checked before the first upload: on an argument or capacity error
+ *                            (the codes of teb_amd_set_obstacles) the previous scene set stays installed. Only a device error
+ *                            during the upload itself (TEB_AMD_ERR_HIP) leaves the handle in single-scene mode, without a scene
+ *                            set. The single-scene table, its lists, its layout choice and its H-signatures are not touched.
+ *   teb_amd_set_band_scenes  scene of band 0 .. count - 1; bands >= count belong to scene 0, as every band does before the first call.
+ *                            The map belongs to the handle: it survives teb_amd_set_scenes and teb_amd_clear_scenes, and
+ *                            teb_amd_compact_bands moves its entries with the bands (the slots it frees go back to scene 0).
+ *                            teb_amd_optimize_batch returns TEB_AMD_ERR_INVALID_ARG when a band maps to a scene >= n_scenes, or when
+ *                            jacobian_mode is TEB_AMD_JACOBIAN_G2O_NUMERIC (fleet kernels exist for closed-form Jacobians).
+ *   teb_amd_clear_scenes     back to the single-scene table as it was.
+ *   teb_amd_get_scene_count  0 = single-scene mode.
+ *   teb_amd_select_best_per_scene  teb_amd_select_best over the bands of every scene: last_best / initial_plan [n_scenes] are BAND
+ *                            indices or -1 (NULL = none); best[s] = band index, -1 for a scene without bands; best_cost [n_scenes] may
+ *                            be NULL.
+ *
+ * A fleet launch has no helper workgroups, is never compiled at run time and follows the layout rules of teb_amd_optimize_batch (the
+ * optimistic layout and its repeat use the largest scene). teb_amd_set_config re-derives the lists of every scene. Everything that
+ * works on band b without the scene works unchanged (the three initialisers, update_and_prune, velocities, consumers, feasibility,
+ * results, upload / download, snapshot / restore, teb_amd_compact_bands). The calls that read or write THE scene of the handle return
+ * TEB_AMD_ERR_INVALID_ARG while scenes are set (call teb_amd_clear_scenes first): teb_amd_set_obstacles, both costmap routes,
+ * teb_amd_set_via_points, the H-signature / class filter / exploration / detour calls, teb_amd_select_best and the distributed
+ * calls (a refused rank still enters the collective and sends the unusable record, as for any other error of one rank),
+ * teb_amd_debug_linearize, teb_amd_debug_distance. Product library only (the other build variants refuse the launch).
+ */
+int  teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obstacles_t* obstacles /* [n_scenes] */,
+                        const int32_t* via_count /* [n_scenes] or NULL */, const double* via_x, const double* via_y /* concatenated */);
+int  teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_t count);
+int  teb_amd_clear_scenes(teb_amd_handle_t* h);
+int  teb_amd_get_scene_count(teb_amd_handle_t* h, int32_t* n_scenes);
+int  teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best, const int32_t* initial_plan,
+                                   int32_t* best /* [n_scenes] */, double* best_cost);
+
 #ifdef __cplusplus
 }
 #endif

@@ -285,3 +285,52 @@ class ResultsHost:
         st.cost = _ptr(self.cost, C.c_double)
         st.lambda_ = _ptr(self.lambda_, C.c_double)
         return st
+
+
+class PackedScenes:
+    """What teb_amd_set_scenes takes: n Obstacles structs in one array, the via-point counts and the via-points of the scenes one after
+    the other. Keeps the numpy arrays (and the tables' frozen arrays) alive."""
+
+    def __init__(self, obstacles, via_count, via_x, via_y, tables):
+        self.n = len(via_count)
+        self.obstacles, self.via_count, self.via_x, self.via_y = obstacles, via_count, via_x, via_y
+        self.rows = sum(len(t) for t in tables)
+        self.vertices = sum(len(t.vert_x) for t in tables)
+        self.via_points = int(via_count.sum())
+        self._tables = list(tables)
+
+
+def pack_scenes(tables, vias=None, max_tebs=None, max_obstacles=None, max_obstacle_vertices=None, max_via_points=None):
+    """The arguments of teb_amd_set_scenes for a list of ObstacleTable and a list of via-point lists ([(x, y), ...] per scene, None = no
+    via-points anywhere). Pure (no library call): shape errors raise ValueError; with the capacities of a handle given, so does a scene
+    set the handle would refuse (sum of the rows > max_obstacles, of the polygon vertices > max_obstacle_vertices, of the via-points >
+    max_via_points, more scenes than max_tebs)."""
+    tables = list(tables)
+    n = len(tables)
+    if n < 1:
+        raise ValueError("pack_scenes: needs at least one scene")
+    if vias is None:
+        vias = [[] for _ in range(n)]
+    vias = [list(v) if v is not None else [] for v in vias]
+    if len(vias) != n:
+        raise ValueError("pack_scenes: %d scenes but %d via-point lists" % (n, len(vias)))
+    for s, v in enumerate(vias):
+        for p in v:
+            if len(p) != 2:
+                raise ValueError("pack_scenes: via-point %r of scene %d is not an (x, y) pair" % (p, s))
+    for s, t in enumerate(tables):
+        if not isinstance(t, ObstacleTable):
+            raise ValueError("pack_scenes: scene %d is not an ObstacleTable" % s)
+    via_count = i32([len(v) for v in vias])
+    flat = [p for v in vias for p in v]
+    via_x = f64([p[0] for p in flat] if flat else [0.0])
+    via_y = f64([p[1] for p in flat] if flat else [0.0])
+    rows, verts = sum(len(t) for t in tables), sum(len(t.vert_x) for t in tables)
+    for what, have, cap in (("scenes", n, max_tebs), ("obstacle rows", rows, max_obstacles),
+                            ("polygon vertices", verts, max_obstacle_vertices), ("via-points", len(flat), max_via_points)):
+        if cap is not None and have > cap:
+            raise ValueError("pack_scenes: %d %s exceed the handle's capacity of %d" % (have, what, cap))
+    arr = (Obstacles * n)()
+    for s, t in enumerate(tables):
+        C.memmove(C.byref(arr, s * C.sizeof(Obstacles)), C.byref(t.freeze()), C.sizeof(Obstacles))
+    return PackedScenes(arr, via_count, via_x, via_y, tables)

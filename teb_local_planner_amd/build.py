@@ -3,7 +3,7 @@
 The host side (csrc/teb_amd.hip: C-ABI, small kernels) and every instantiation of the optimise kernel (csrc/teb_opt_inst.hip with
 -DTEB_INST_SOLVER / _JMODE / _SCENE: 3 layouts x 2 Jacobian modes x 2 scene kinds) are separate translation units compiled in
 parallel into build/<variant>/*.o and linked into one shared library. Variants:
-    product : libteb_amd.so
+    product : libteb_amd.so  (+ the six fleet units, csrc/teb_fleet_inst.hip with -DTEB_AMD_FLEET: a scene per band, FLEET_UNIT_FLAGS)
     mfma    : libteb_amd_mfma.so  (-DTEB_AMD_MFMA_SCHUR -DTEB_AMD_ANALYTIC_ONLY: the Schur update of the cyclic reduction on
               v_mfma_f64_16x16x4_f64 - SURVEY section 8 row g; exercised by tests/test_gpu_mfma_build.py)"""
 import concurrent.futures
@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libteb_amd.so")
 LIB_MFMA = os.path.join(HERE, "libteb_amd_mfma.so")
 HEADERS = ["teb_device.hpp", "teb_comm.hpp", "teb_feasibility.hpp", "teb_costmap_obstacles.hpp", "teb_costmap_polygons.hpp", "teb_geometry.hpp", "teb_edges.hpp", "teb_kernel.hpp", "teb_strip.hpp",
-           "teb_hsig.hpp", "teb_graph.hpp", "teb_opt_launch.hpp", "teb_multicu.hpp", "teb_autoresize_chain.hpp", "teb_rtc.hpp",
+           "teb_hsig.hpp", "teb_graph.hpp", "teb_opt_launch.hpp", "teb_multicu.hpp", "teb_autoresize_chain.hpp", "teb_rtc.hpp", "teb_fleet.hpp",
            os.path.join("..", "..", "include", "teb_amd.h"), os.path.join("..", "..", "include", "teb_amd_debug.h")]
 
 # -ffp-contract=off: the parity contract is against a plain IEEE mul/add restatement of the reference;
@@ -64,6 +64,12 @@ for _sv in (0, 1, 2):
         for _sk in (0, 1, 2, 3, 10, 11):
             UNIT_FLAGS.setdefault("opt_%d_%d_%d.o" % (_sv, _jm, _sk), []).append("-DTEB_AMD_SOLVE_CSR")
 
+# The fleet units (csrc/teb_fleet.hpp, csrc/teb_fleet_inst.hip): teb_optimize_kernel with a scene per band, the non-folded kinds 0, 1 in
+# the three layouts with closed-form Jacobians, product only. The generic-twin comparison does not cover them (they are compared bit for
+# bit with single-scene launches of the generic kinds, tests/test_gpu_fleet.py), so they take the plain calling convention of the solve.
+# Their own table: neither UNIT_FLAGS nor the opt_%d_%d_%d.o names know them.
+FLEET_UNIT_FLAGS = {"fleet_%d_0_%d.o" % (_sv, _sk): ["-DTEB_AMD_FLEET", "-DTEB_AMD_SOLVE_CSR"] for _sv in (0, 1, 2) for _sk in (0, 1)}
+
 VARIANTS = {
     "product": dict(lib=LIB, defines=[], jmodes=(0, 1)),
     "mfma": dict(lib=LIB_MFMA, defines=["-DTEB_AMD_MFMA_SCHUR", "-DTEB_AMD_ANALYTIC_ONLY", "-DTEB_AMD_NO_DEFAULTS_TWINS"], jmodes=(0,)),
@@ -97,6 +103,11 @@ def _units(variant, only=None):
                 stub = ["-DTEB_INST_STUB"] if ("only" in v and name not in v["only"]) else []
                 units.append((name, "teb_opt_inst.hip",
                               ["-DTEB_INST_SOLVER=%d" % sv, "-DTEB_INST_JMODE=%d" % jm, "-DTEB_INST_SCENE=%d" % sk] + stub))
+    if variant == "product":
+        for sv in (0, 1, 2):
+            for sk in (0, 1):
+                name = "fleet_%d_0_%d.o" % (sv, sk)
+                units.append((name, "teb_fleet_inst.hip", ["-DTEB_INST_SOLVER=%d" % sv, "-DTEB_INST_SCENE=%d" % sk] + FLEET_UNIT_FLAGS[name]))
     return units
 
 
@@ -107,7 +118,7 @@ KERNEL_DEPS = ["teb_opt_inst.hip", "teb_device.hpp", "teb_geometry.hpp", "teb_ed
 
 def _newest_source(files=None):
     t = 0.0
-    for f in (files or ["teb_amd.hip", "teb_opt_inst.hip"] + HEADERS):
+    for f in (files or ["teb_amd.hip", "teb_opt_inst.hip", "teb_fleet_inst.hip"] + HEADERS):
         p = os.path.join(CSRC, f)
         if os.path.exists(p):
             t = max(t, os.path.getmtime(p))
@@ -121,7 +132,7 @@ def _stale(path):
 def source_hash():
     """sha256 over the device + host sources of the library (what a committed profile is tied to)."""
     h = hashlib.sha256()
-    for f in sorted(["teb_amd.hip", "teb_opt_inst.hip"] + HEADERS):
+    for f in sorted(["teb_amd.hip", "teb_opt_inst.hip", "teb_fleet_inst.hip"] + HEADERS):
         p = os.path.join(CSRC, f)
         if os.path.exists(p):
             h.update(open(p, "rb").read())
@@ -198,20 +209,26 @@ def build(force=False, verbose=False, variant="product", jobs=None, extra_define
     os.makedirs(bdir, exist_ok=True)
     jobs = jobs or int(os.environ.get("TEB_AMD_BUILD_JOBS", "0")) or min(os.cpu_count() or 1, 8)
     newest_all, newest_kernel = _newest_source(), _newest_source(KERNEL_DEPS)
+    newest_fleet = max(newest_kernel, _newest_source(["teb_fleet_inst.hip", "teb_fleet.hpp"]))
 
     embedded = write_rtc_sources(bdir)
     src_hash, k_hash = source_hash(), kernel_hash(list(v["defines"]) + list(extra_defines), unit_flags)
 
+    units = _units(variant, only)
+    has_fleet = any(src == "teb_fleet_inst.hip" for _, src, _ in units)
+
     def compile_unit(u):
         obj, src, defs = u
         o = os.path.join(bdir, obj)
-        newest = newest_kernel if src == "teb_opt_inst.hip" else newest_all
+        newest = newest_kernel if src == "teb_opt_inst.hip" else (newest_fleet if src == "teb_fleet_inst.hip" else newest_all)
         if not force and os.path.exists(o) and os.path.getmtime(o) >= newest:
             return o
         if src == "teb_amd.hip":   # the host side carries the kernel sources for the run-time compiler (teb_rtc.hpp) and the variant's defines
             defs = defs + ["-DTEB_AMD_RTC_EMBEDDED", "-I" + os.path.dirname(embedded),
                            '-DTEB_AMD_VARIANT_DEFINES="%s"' % " ".join(list(v["defines"]) + list(extra_defines)),
                            '-DTEB_AMD_BUILD_SOURCE_HASH="%s"' % src_hash, '-DTEB_AMD_BUILD_KERNEL_HASH="%s"' % k_hash]   # read back by teb_amd_debug_build_info: ties a profile to the BINARY
+            if has_fleet:   # the library holds the fleet units: the host side may reach their accessors (csrc/teb_fleet.hpp)
+                defs = defs + ["-DTEB_AMD_HAS_FLEET_UNITS"]
         cmd = [hipcc] + HIPCC_FLAGS + v["defines"] + list(extra_defines) + defs + list(unit_flags.get(obj, [])) + ["-c", os.path.join(CSRC, src), "-o", o]
         if verbose:
             print(" ".join(cmd), flush=True)
@@ -219,7 +236,7 @@ def build(force=False, verbose=False, variant="product", jobs=None, extra_define
         return o
 
     with concurrent.futures.ThreadPoolExecutor(max_workers=jobs) as ex:
-        objs = list(ex.map(compile_unit, _units(variant, only)))
+        objs = list(ex.map(compile_unit, units))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-o", lib]
     if verbose:
         print(" ".join(cmd), flush=True)

@@ -19,6 +19,7 @@
 #define TEB_AMD_MAIN_TU   // (non-template kernels of the shared headers are defined here only)
 #include "teb_kernel.hpp"
 #include "teb_opt_launch.hpp"
+#include "teb_fleet.hpp"
 #include "teb_strip.hpp"
 #include "teb_hsig.hpp"
 #include "teb_graph.hpp"
@@ -34,6 +35,10 @@ using namespace tebamd;
 TEB_OPT_FOR_ALL(TEB_OPT_DECLARE)
 #ifdef TEB_AMD_SINGLE_TU
 TEB_OPT_FOR_ALL(TEB_OPT_DEFINE)
+#endif
+// the fleet units (teb_fleet.hpp) are part of the product library only (build.py passes -DTEB_AMD_HAS_FLEET_UNITS with them)
+#ifdef TEB_AMD_HAS_FLEET_UNITS
+TEB_FLEET_FOR_ALL(TEB_FLEET_DECLARE)
 #endif
 
 namespace {
@@ -249,6 +254,22 @@ struct teb_amd_handle {
   DevBuf<int> cmp_cnt, cmp_off;
   DevBuf<double> cmp_x, cmp_y;
   std::mt19937 rnd_generator;   // ProbRoadmapGraph::rnd_generator_ (graph_search.h:211): default-seeded 32-bit Mersenne twister
+  // fleet batches (teb_fleet.hpp, teb_amd_set_scenes): a second set of scene buffers, allocated at the first teb_amd_set_scenes and
+  // sized by the capacities of the handle; rows, vertices and via-points of the scenes one after the other
+  struct Fleet {
+    int n_scenes = 0;               // 0 = single-scene mode
+    bool allocated = false;
+    std::vector<HostObst> tabs;     // host copy of every scene's table: teb_amd_set_config re-derives the lists from them
+    std::vector<int> via_count;
+    std::vector<int> band_scene;    // [max_tebs] scene of every band (teb_amd_set_band_scenes); survives set / clear
+    int fast_points = 0;            // SCENE_POINTS: every scene and the footprint point-like and the cache of the largest scene fits
+    int max_cache = 0;              // largest n_static + n_dyn of a scene: what the LDS plans of a fleet launch are made for
+    int solver = 0;                 // layout of a fleet launch (the single-scene choice h->solver is not touched)
+    LdsPlan plan;
+    DevBuf<int> type, dyn, voff, stat, dynidx, scene_of, sel_last, sel_init, sel_idx;
+    DevBuf<double> ax, ay, bx, by, rad, vx, vy, cx, cy, brad, pvx, pvy, viax, viay, list, sel_cost;
+    DevBuf<SceneDev> scenes;
+  } fleet;
 };
 
 namespace {
@@ -257,6 +278,16 @@ int check_handle(teb_amd_handle* h) {
   if (!h) return fail(TEB_AMD_ERR_INVALID_ARG, "null handle");
   if (hipSetDevice(h->device) != hipSuccess) return fail(TEB_AMD_ERR_HIP, "hipSetDevice failed");
   return TEB_AMD_OK;
+}
+
+void fleet_free(teb_amd_handle* h) {
+  auto& F = h->fleet;
+  DevBuf<int>* ib[] = {&F.type, &F.dyn, &F.voff, &F.stat, &F.dynidx, &F.scene_of, &F.sel_last, &F.sel_init, &F.sel_idx};
+  for (auto* q : ib) q->free();
+  DevBuf<double>* db[] = {&F.ax, &F.ay, &F.bx, &F.by, &F.rad, &F.vx, &F.vy, &F.cx, &F.cy, &F.brad, &F.pvx, &F.pvy, &F.viax, &F.viay, &F.list, &F.sel_cost};
+  for (auto* q : db) q->free();
+  F.scenes.free();
+  F.allocated = false;
 }
 
 SceneDev scene_of(teb_amd_handle* h) {
@@ -352,8 +383,34 @@ std::shared_ptr<RtcKernel> rtc_lookup(const teb_amd_handle* h, const OptArgs& ar
   std::shared_ptr<RtcKernel> rk = rtc_request(key, wait, &why);
   return (rk && rk->state.load() == RtcKernel::READY) ? rk : nullptr;
 }
+// The fleet units (teb_fleet.hpp): closed-form Jacobians, SCENE_POINTS / SCENE_GENERIC. Null in the variants built without them.
+const void* fleet_kernel(int solver, int scene) {
+#ifdef TEB_AMD_HAS_FLEET_UNITS
+#define TEB_FLEET_PICK(S, P) if (solver == S && scene == P) return TEB_FLEET_KERNEL_FN(S, P)();
+  TEB_FLEET_FOR_ALL(TEB_FLEET_PICK)
+#undef TEB_FLEET_PICK
+#endif
+  (void)solver; (void)scene;
+  return nullptr;
+}
+// one workgroup per band, every band against fleet.scenes[fleet.scene_of[b]]: no helper workgroups, no run-time compilation
+hipError_t launch_fleet(teb_amd_handle* h, int grid, const BatchDev& bt, const OptArgs& a, int solver, const LdsPlan& plan) {
+  const int scene_kind = h->fleet.fast_points ? SCENE_POINTS : SCENE_GENERIC;
+  const void* k = fleet_kernel(solver, scene_kind);
+  h->last_defaults_profile = 0;
+  h->last_inst[0] = solver; h->last_inst[1] = TEB_AMD_JACOBIAN_ANALYTIC; h->last_inst[2] = -1;
+  if (!k) return hipErrorInvalidDeviceFunction;
+  h->last_inst[2] = scene_kind;
+  FleetDev fl;
+  fl.scenes = h->fleet.scenes.p; fl.scene_of = h->fleet.scene_of.p;
+  McuDev none;
+  std::memset(&none, 0, sizeof none);
+  void* params[] = {const_cast<teb_amd_config_t*>(&h->cfg), &fl, const_cast<BatchDev*>(&bt), const_cast<OptArgs*>(&a), const_cast<LdsPlan*>(&plan), &none};
+  return hipLaunchKernel(k, dim3(grid), dim3(kThreads), params, plan.total_bytes, h->stream);
+}
 hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const BatchDev& bt, const OptArgs& a, int solver, const LdsPlan& plan,
                       const McuDev* mcu = nullptr) {
+  if (h->fleet.n_scenes > 0) return launch_fleet(h, grid, bt, a, solver, plan);
   McuDev none;
   std::memset(&none, 0, sizeof none);
   const McuDev* mc = mcu ? mcu : &none;
@@ -393,6 +450,7 @@ hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const Bat
   return hipLaunchKernel(k, dim3(grid * (1 + mc->K + mc->D)), dim3(kThreads), params, plan.total_bytes, h->stream);
 }
 hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const BatchDev& bt, const OptArgs& a) {
+  if (h->fleet.n_scenes > 0) return launch_opt(h, grid, sc, bt, a, h->fleet.solver, h->fleet.plan);
   return launch_opt(h, grid, sc, bt, a, h->solver, h->plan);
 }
 
@@ -434,8 +492,7 @@ void mcu_helpers_for(teb_amd_handle* h, const OptArgs& args, int eff_solver, int
 }
 
 // largest pose capacity whose LDS plan (with the obstacle cache of this scene, if it is in use) fits
-int max_capacity_of(teb_amd_handle* h, int solver, int upto) {
-  const int ob = h->fast_points ? h->M : 0;
+int max_capacity_of(teb_amd_handle* h, int solver, int upto, int ob) {
   int S = upto;
   while (S > 8 && (size_t)make_lds_plan(S, solver, ob, h->lds_limit).total_bytes > h->lds_limit) --S;
   return (size_t)make_lds_plan(S, solver, ob, h->lds_limit).total_bytes <= h->lds_limit ? S : 0;
@@ -506,10 +563,13 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
   // launched in the fastest layout that leaves the bands 10 % room to grow (autoResize); should a band outgrow it all the same, the
   // launch is repeated from the saved strips in the handle's own layout. Results do not depend on the layout (same arithmetic up to
   // the order of the block reduction). TEB_AMD_FIXED_LAYOUT=1 switches this off.
-  int eff_solver = h->solver;
-  LdsPlan eff_plan = h->plan;
+  // fleet mode (teb_amd_set_scenes): the layout, the plan and the obstacle cache are those of the scene set (its largest scene)
+  const bool fleet = h->fleet.n_scenes > 0;
+  const int own_solver = fleet ? h->fleet.solver : h->solver;
+  int eff_solver = own_solver;
+  LdsPlan eff_plan = fleet ? h->fleet.plan : h->plan;
   bool optimistic = false;
-  if (h->solver != SOLVER_CR && !args.debug_linearize && !h->opt.fixed_layout && h->opt.layout == TEB_AMD_LAYOUT_AUTO && !h->band_ldlt) {
+  if (own_solver != SOLVER_CR && !args.debug_linearize && !h->opt.fixed_layout && h->opt.layout == TEB_AMD_LAYOUT_AUTO && !h->band_ldlt) {
     int nmax = h->nmax_known;
     if (nmax < 0) {   // a device-side producer changed the bands since the host last saw their pose counts
       std::vector<int> n(h->B);
@@ -519,15 +579,15 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
       for (int v : n) nmax = std::max(nmax, v);
     }
     const int need = nmax + nmax / 10 + 4;   // 10 % room to grow; a band that needs more triggers the repeat below
-    const int ob = h->fast_points ? h->M : 0;
-    const int s_cr = max_capacity_of(h, SOLVER_CR, std::min(h->stride, 238));
-    const int s_band = h->solver == SOLVER_BANDG ? max_capacity_of(h, SOLVER_BAND, std::min(h->stride, 337)) : 0;
+    const int ob = fleet ? (h->fleet.fast_points ? h->fleet.max_cache : 0) : (h->fast_points ? h->M : 0);
+    const int s_cr = max_capacity_of(h, SOLVER_CR, std::min(h->stride, 238), ob);
+    const int s_band = own_solver == SOLVER_BANDG ? max_capacity_of(h, SOLVER_BAND, std::min(h->stride, 337), ob) : 0;
     if (s_cr > 0 && need <= s_cr) { eff_solver = SOLVER_CR; eff_plan = make_lds_plan(s_cr, SOLVER_CR, ob, h->lds_limit); optimistic = true; }
     else if (s_band > 0 && need <= s_band) { eff_solver = SOLVER_BAND; eff_plan = make_lds_plan(s_band, SOLVER_BAND, ob, h->lds_limit); optimistic = true; }
   }
   // multi-CU mode: helper workgroups per band (0 = none); its buffers, and the control words zeroed on the stream before the launch
   int K = 0, D = 0;
-  mcu_helpers_for(h, args, eff_solver, &K, &D);
+  if (!fleet) mcu_helpers_for(h, args, eff_solver, &K, &D);   // (a fleet launch has no helper workgroups)
   if (D > 0 && h->mcu_backoff_left > 0) { D = 0; --h->mcu_backoff_left; }   // paused after a miss: one CU per band, no wait, no repeat
   if (D > 0) {
     // distance records [B][M][4][stride]: bounded (the association list of a pose is short, but its capacity is every obstacle), and a
@@ -568,7 +628,7 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
     }
     if (int crc = copy_strips(h, Strips{h->ob_x.p, h->ob_y.p, h->ob_th.p, h->ob_dt.p, h->ob_n.p}, Strips{h->x.p, h->y.p, h->th.p, h->dt.p, h->n.p}, h->B)) return crc;
   }
-  if (h->opt.compile_for_config >= 2)   // synchronous mode: the wait for the compiler is not kernel time
+  if (h->opt.compile_for_config >= 2 && !fleet)   // synchronous mode: the wait for the compiler is not kernel time
     (void)rtc_lookup(h, args, sc, eff_solver, H > 0, profile_matches(h, args, sc), true);
   HIPCHK(hipEventRecord(h->ev0, h->stream));   // (the kernel clears its bands' overflow flags itself)
   HIPCHK(launch_opt(h, h->B, sc, bt, args, eff_solver, eff_plan, H > 0 ? &mcu : nullptr));
@@ -836,6 +896,7 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
   h->g_adj.free();
   h->cm_cells.free(); h->cm_fp.free(); h->cm_out.free(); h->cmo_cnt.free();
   h->cmp_cnt.free(); h->cmp_off.free(); h->cmp_x.free(); h->cmp_y.free();
+  fleet_free(h);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -843,46 +904,46 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
 }
 
 namespace {
-// (Re)derives everything that depends on BOTH the obstacle table held in h->hob and the configuration: the lists AddEdgesObstacles /
-// AddEdgesDynamicObstacles visit, the distance path (point-like LDS cache or generic) and the layout that goes with it.
-int commit_obstacles(teb_amd_handle* h) {
-  const auto& o = h->hob;
-  const int M = (int)o.type.size();
+// What ONE scene's kernels read beyond the rows of its table (parse_obstacle_table: the rows, centroids, bounding radii), derived from
+// the table and the configuration - the single-scene path (commit_obstacles) and every scene of a fleet (commit_fleet) call it:
+// the lists AddEdgesObstacles / AddEdgesDynamicObstacles visit, the obstacles in cache order, static_radius_zero, point-likeness.
+struct SceneLists {
   std::vector<int> st, dy;
+  std::vector<double> lo;        // [5][stride]: x, y, radius, vx, vy in cache order (static list, then dynamic list)
+  int static_radius_zero = 1;    // no circular obstacle with a radius in the static list
+  bool pointlike_rows = true;    // every row is Point / Circular
+};
+void derive_scene_lists(const teb_amd_config_t& cfg, const teb_amd_handle::HostObst& o, size_t stride, SceneLists& d) {
+  const int M = (int)o.type.size();
+  d.st.clear(); d.dy.clear();
   for (int i = 0; i < M; ++i) {
     // AddEdgesObstacles skips dynamic obstacles iff include_dynamic_obstacles (optimal_planner.cpp:496-497);
     // AddEdgesDynamicObstacles visits the dynamic ones (:658-659)
-    if (h->cfg.include_dynamic_obstacles && o.dyn[i]) dy.push_back(i); else st.push_back(i);
+    if (cfg.include_dynamic_obstacles && o.dyn[i]) d.dy.push_back(i); else d.st.push_back(i);
   }
-  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
-  HIPCHK(up_i(h->o_static, st)); HIPCHK(up_i(h->o_dynidx, dy));
-  {   // the obstacles in cache order (static list, then dynamic list): what the kernel stages into LDS, readable with scalar loads
-    const size_t mo = (size_t)(h->max_obst > 0 ? h->max_obst : 1);
-    std::vector<double> lo(5 * mo, 0.0);
-    size_t k = 0;
-    h->static_radius_zero = 1;
-    for (int oi : st) if (o.type[oi] == TEB_AMD_OBST_CIRCULAR && o.rad[oi] != 0.0) h->static_radius_zero = 0;
-    for (const std::vector<int>* lst : {&st, &dy})
-      for (int oi : *lst) {
-        lo[k] = o.ax[oi]; lo[mo + k] = o.ay[oi]; lo[2 * mo + k] = o.type[oi] == TEB_AMD_OBST_CIRCULAR ? o.rad[oi] : 0.0;
-        lo[3 * mo + k] = o.vx[oi]; lo[4 * mo + k] = o.vy[oi];
-        ++k;
-      }
-    HIPCHK(hipMemcpyAsync(h->o_list.p, lo.data(), lo.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  HIPCHK(hipStreamSynchronize(h->stream));   // host vectors go out of scope
-  h->n_static = (int)st.size(); h->n_dyn = (int)dy.size();
-  h->host_static = st;
-  h->hsig_mode = 0;   // signatures depend on the obstacle table and on include_dynamic_obstacles
-  // point-like fast path: all obstacles Point/Circular, footprint Point/Circular, and the cache fits the LDS
-  bool pointlike = (h->cfg.footprint_type == TEB_AMD_FOOTPRINT_POINT || h->cfg.footprint_type == TEB_AMD_FOOTPRINT_CIRCULAR);
-  for (int i = 0; i < M && pointlike; ++i) pointlike = (o.type[i] == TEB_AMD_OBST_POINT || o.type[i] == TEB_AMD_OBST_CIRCULAR);
+  // the obstacles in cache order (static list, then dynamic list): what the kernel stages into LDS, readable with scalar loads
+  d.lo.assign(5 * stride, 0.0);
+  size_t k = 0;
+  d.static_radius_zero = 1;
+  for (int oi : d.st) if (o.type[oi] == TEB_AMD_OBST_CIRCULAR && o.rad[oi] != 0.0) d.static_radius_zero = 0;
+  for (const std::vector<int>* lst : {&d.st, &d.dy})
+    for (int oi : *lst) {
+      d.lo[k] = o.ax[oi]; d.lo[stride + k] = o.ay[oi]; d.lo[2 * stride + k] = o.type[oi] == TEB_AMD_OBST_CIRCULAR ? o.rad[oi] : 0.0;
+      d.lo[3 * stride + k] = o.vx[oi]; d.lo[4 * stride + k] = o.vy[oi];
+      ++k;
+    }
+  d.pointlike_rows = true;
+  for (int i = 0; i < M && d.pointlike_rows; ++i) d.pointlike_rows = (o.type[i] == TEB_AMD_OBST_POINT || o.type[i] == TEB_AMD_OBST_CIRCULAR);
+}
+// The distance path and the layout that goes with it, for an obstacle cache of M entries: point-like fast path iff all obstacles are
+// Point/Circular, the footprint is Point/Circular, and the cache fits the LDS.
+int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, int M, int* solver, int* fast_points, LdsPlan* plan) {
+  bool pointlike = pointlike_rows && (h->cfg.footprint_type == TEB_AMD_FOOTPRINT_POINT || h->cfg.footprint_type == TEB_AMD_FOOTPRINT_CIRCULAR);
   if (h->opt.generic_distance_path) pointlike = false;
   // a point-like scene whose obstacle cache does not fit beside the LDS band: the band moves to HBM and the cache stays (measured,
   // 64 bands x 337 poses x 500 obstacles: 9.0 instead of 11.8 ms per step)
-  h->solver = h->solver_created;
-  if (pointlike && M > 0 && h->solver == SOLVER_BAND && h->opt.layout == TEB_AMD_LAYOUT_AUTO &&
+  *solver = h->solver_created;
+  if (pointlike && M > 0 && *solver == SOLVER_BAND && h->opt.layout == TEB_AMD_LAYOUT_AUTO &&
       (size_t)make_lds_plan(h->stride, SOLVER_BAND, M, h->lds_limit).total_bytes > h->lds_limit &&
       (size_t)make_lds_plan(h->stride, SOLVER_BANDG, M, h->lds_limit).total_bytes <= h->lds_limit) {
     if (h->hband_stride == 0) {
@@ -890,11 +951,85 @@ int commit_obstacles(teb_amd_handle* h) {
       h->Hband.free();
       HIPCHK(h->Hband.alloc((size_t)h->max_tebs * h->hband_stride));
     }
-    h->solver = SOLVER_BANDG;
+    *solver = SOLVER_BANDG;
   }
-  LdsPlan with_cache = make_lds_plan(h->stride, h->solver, M, h->lds_limit);
-  if (pointlike && M > 0 && (size_t)with_cache.total_bytes <= h->lds_limit) { h->fast_points = 1; h->plan = with_cache; }
-  else { h->fast_points = 0; h->plan = make_lds_plan(h->stride, h->solver, 0, h->lds_limit); }
+  LdsPlan with_cache = make_lds_plan(h->stride, *solver, M, h->lds_limit);
+  if (pointlike && M > 0 && (size_t)with_cache.total_bytes <= h->lds_limit) { *fast_points = 1; *plan = with_cache; }
+  else { *fast_points = 0; *plan = make_lds_plan(h->stride, *solver, 0, h->lds_limit); }
+  return TEB_AMD_OK;
+}
+// (Re)derives everything that depends on BOTH the obstacle table held in h->hob and the configuration: the lists AddEdgesObstacles /
+// AddEdgesDynamicObstacles visit, the distance path (point-like LDS cache or generic) and the layout that goes with it.
+int commit_obstacles(teb_amd_handle* h) {
+  const auto& o = h->hob;
+  const int M = (int)o.type.size();
+  SceneLists d;
+  derive_scene_lists(h->cfg, o, (size_t)(h->max_obst > 0 ? h->max_obst : 1), d);
+  auto up_i = [&](DevBuf<int>& dst, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(dst.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
+  HIPCHK(up_i(h->o_static, d.st)); HIPCHK(up_i(h->o_dynidx, d.dy));
+  HIPCHK(hipMemcpyAsync(h->o_list.p, d.lo.data(), d.lo.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // host vectors go out of scope
+  h->static_radius_zero = d.static_radius_zero;
+  h->n_static = (int)d.st.size(); h->n_dyn = (int)d.dy.size();
+  h->host_static = d.st;
+  h->hsig_mode = 0;   // signatures depend on the obstacle table and on include_dynamic_obstacles
+  return choose_scene_layout(h, d.pointlike_rows, M, &h->solver, &h->fast_points, &h->plan);
+}
+
+// Fleet mode: the lists of every scene, the SceneDev array and the layout of a fleet launch, derived from the host tables of the scene
+// set and the configuration. Every SceneDev points at its own segment of the concatenated rows (row offset ro; voff has one entry more
+// per scene, so its segment starts at ro + s), its indices are local to the segment: the kernel's arithmetic is the single-scene one.
+int commit_fleet(teb_amd_handle* h) {
+  auto& F = h->fleet;
+  const int ns = (int)F.tabs.size();
+  std::vector<int> st_all, dy_all;
+  std::vector<double> lo_all;
+  std::vector<SceneDev> sd(ns);
+  size_t ro = 0, vo = 0, wo = 0;
+  bool pointlike = true;
+  int max_cache = 0;
+  for (int s = 0; s < ns; ++s) {
+    const auto& o = F.tabs[s];
+    const size_t M = o.type.size();
+    SceneLists d;
+    derive_scene_lists(h->cfg, o, M, d);
+    st_all.resize(ro + M, 0); dy_all.resize(ro + M, 0);
+    std::copy(d.st.begin(), d.st.end(), st_all.begin() + ro);
+    std::copy(d.dy.begin(), d.dy.end(), dy_all.begin() + ro);
+    lo_all.insert(lo_all.end(), d.lo.begin(), d.lo.end());   // 5 M values: the segment of scene s starts at 5 ro
+    pointlike = pointlike && d.pointlike_rows;
+    max_cache = std::max(max_cache, (int)M);
+    SceneDev& q = sd[s];
+    q.M = (int)M;
+    q.fast_points = 0;   // set below: one distance path for the whole launch
+    q.static_radius_zero = d.static_radius_zero;
+    q.type = F.type.p + ro; q.ax = F.ax.p + ro; q.ay = F.ay.p + ro; q.bx = F.bx.p + ro; q.by = F.by.p + ro;
+    q.rad = F.rad.p + ro; q.vx = F.vx.p + ro; q.vy = F.vy.p + ro; q.cx = F.cx.p + ro; q.cy = F.cy.p + ro; q.brad = F.brad.p + ro;
+    q.dyn = F.dyn.p + ro; q.voff = F.voff.p + ro + s; q.pvx = F.pvx.p + vo; q.pvy = F.pvy.p + vo;
+    q.n_static = (int)d.st.size(); q.static_idx = F.stat.p + ro; q.n_dyn = (int)d.dy.size(); q.dyn_idx = F.dynidx.p + ro;
+    q.nvia = F.via_count[s]; q.viax = F.viax.p + wo; q.viay = F.viay.p + wo;
+    q.lox = F.list.p + 5 * ro; q.loy = q.lox + M; q.lor = q.lox + 2 * M; q.lovx = q.lox + 3 * M; q.lovy = q.lox + 4 * M;
+    ro += M; vo += o.pvx.size(); wo += (size_t)F.via_count[s];
+  }
+  int solver = 0, fast = 0;
+  LdsPlan plan;
+  if (int rc = choose_scene_layout(h, pointlike, max_cache, &solver, &fast, &plan)) return rc;
+  for (auto& q : sd) q.fast_points = fast;
+  if (ro > 0) {
+    HIPCHK(hipMemcpyAsync(F.stat.p, st_all.data(), ro * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.dynidx.p, dy_all.data(), ro * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.list.p, lo_all.data(), 5 * ro * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  HIPCHK(hipMemcpyAsync(F.scenes.p, sd.data(), (size_t)ns * sizeof(SceneDev), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // host vectors go out of scope
+  F.solver = solver; F.fast_points = fast; F.plan = plan; F.max_cache = max_cache;
+  return TEB_AMD_OK;
+}
+
+// the calls that read or write THE scene of the handle are not available while a scene set is installed (teb_amd.h, fleet batches)
+int refuse_in_fleet_mode(const teb_amd_handle* h, const char* call) {
+  if (h->fleet.n_scenes > 0)
+    return fail(TEB_AMD_ERR_INVALID_ARG, std::string(call) + ": not available while scenes are set (fleet mode); call teb_amd_clear_scenes first");
   return TEB_AMD_OK;
 }
 }  // namespace
@@ -915,6 +1050,16 @@ int teb_amd_set_config(teb_amd_handle_t* h, const teb_amd_config_t* cfg) {
       const std::string why = g_last_error;
       h->cfg = previous;
       (void)commit_obstacles(h);
+      return fail(rc, why);
+    }
+  }
+  if (lists_changed && h->fleet.n_scenes > 0) {   // fleet mode: the lists of every scene
+    rc = commit_fleet(h);
+    if (rc) {
+      const std::string why = g_last_error;
+      h->cfg = previous;
+      if (h->M > 0) (void)commit_obstacles(h);
+      (void)commit_fleet(h);
       return fail(rc, why);
     }
   }
@@ -989,6 +1134,7 @@ int install_obstacles(teb_amd_handle* h, teb_amd_handle::HostObst&& t) {
 int teb_amd_set_obstacles(teb_amd_handle_t* h, const teb_amd_obstacles_t* o) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles"))) return rc;
   if (!o || o->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "null obstacle table");
   if (o->count > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
   teb_amd_handle::HostObst t;
@@ -1003,6 +1149,7 @@ int teb_amd_set_obstacles(teb_amd_handle_t* h, const teb_amd_obstacles_t* o) {
 int teb_amd_set_via_points(teb_amd_handle_t* h, int32_t count, const double* x, const double* y) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_set_via_points"))) return rc;
   if (count < 0 || (count > 0 && (!x || !y))) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
   if (count > h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
   if (count > 0) {
@@ -1011,6 +1158,161 @@ int teb_amd_set_via_points(teb_amd_handle_t* h, int32_t count, const double* x, 
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   h->nvia = count;
+  return TEB_AMD_OK;
+}
+
+// ---- fleet batches (teb_amd.h): a set of scenes and a band -> scene map ---------------------------------------------------------------
+namespace {
+constexpr size_t kFleetPad = 8;   // elements past every fleet buffer: the segment of an empty scene at the very end still points at storage
+int fleet_allocate(teb_amd_handle* h) {
+  auto& F = h->fleet;
+  if (F.allocated) return TEB_AMD_OK;
+  const size_t Mo = (size_t)std::max(h->max_obst, 0) + kFleetPad, T = (size_t)h->max_tebs;
+  const size_t Vo = (size_t)std::max(h->max_verts, 0) + kFleetPad, Wo = (size_t)std::max(h->max_via, 0) + kFleetPad;
+  bool ok = true;
+  auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
+  A(F.type.alloc(Mo)); A(F.dyn.alloc(Mo)); A(F.voff.alloc(Mo + T)); A(F.stat.alloc(Mo)); A(F.dynidx.alloc(Mo));
+  A(F.ax.alloc(Mo)); A(F.ay.alloc(Mo)); A(F.bx.alloc(Mo)); A(F.by.alloc(Mo)); A(F.rad.alloc(Mo)); A(F.vx.alloc(Mo)); A(F.vy.alloc(Mo));
+  A(F.cx.alloc(Mo)); A(F.cy.alloc(Mo)); A(F.brad.alloc(Mo)); A(F.list.alloc(5 * Mo));
+  A(F.pvx.alloc(Vo)); A(F.pvy.alloc(Vo)); A(F.viax.alloc(Wo)); A(F.viay.alloc(Wo));
+  A(F.scenes.alloc(T)); A(F.scene_of.alloc(T)); A(F.sel_last.alloc(T)); A(F.sel_init.alloc(T)); A(F.sel_idx.alloc(T)); A(F.sel_cost.alloc(T));
+  for (int sv : {SOLVER_BAND, SOLVER_CR, SOLVER_BANDG})
+    for (int sk : {SCENE_POINTS, SCENE_GENERIC}) {
+      const void* k = fleet_kernel(sv, sk);
+      if (ok && k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit) != hipSuccess) ok = false;
+    }
+  if (F.band_scene.empty()) F.band_scene.assign(T, 0);
+  if (ok && hipMemcpy(F.scene_of.p, F.band_scene.data(), T * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) ok = false;
+  if (!ok) {
+    (void)hipGetLastError();
+    fleet_free(h);
+    return fail(TEB_AMD_ERR_HIP, "teb_amd_set_scenes: device allocation of the fleet storage failed");
+  }
+  F.allocated = true;
+  return TEB_AMD_OK;
+}
+}  // namespace
+
+int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obstacles_t* obstacles, const int32_t* via_count, const double* via_x,
+                       const double* via_y) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_scenes < 1 || !obstacles) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scenes: needs at least one scene");
+  if (n_scenes > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more scenes than max_tebs");
+  // everything is parsed and checked before the first upload: on an error the previous scene set stays installed
+  std::vector<teb_amd_handle::HostObst> tabs(n_scenes);
+  std::vector<int> vc(n_scenes, 0);
+  size_t rows = 0, verts = 0, vias = 0;
+  for (int s = 0; s < n_scenes; ++s) {
+    if (obstacles[s].count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "null obstacle table");
+    rc = parse_obstacle_table(&obstacles[s], tabs[s]);
+    if (rc) return rc;
+    rows += tabs[s].type.size(); verts += tabs[s].pvx.size();
+    if (via_count) {
+      if (via_count[s] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
+      vc[s] = via_count[s]; vias += (size_t)via_count[s];
+    }
+  }
+  if (vias > 0 && (!via_x || !via_y)) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
+  if (rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
+  if (verts > (size_t)h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
+  if (vias > (size_t)h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
+  rc = fleet_allocate(h);
+  if (rc) return rc;
+  auto& F = h->fleet;
+  // rows, vertices and via-points of the scenes one after the other (voff: M + 1 entries per scene, local to the scene's vertices)
+  teb_amd_handle::HostObst all;
+  for (int s = 0; s < n_scenes; ++s) {
+    const auto& t = tabs[s];
+    auto cat_i = [](std::vector<int>& d, const std::vector<int>& v) { d.insert(d.end(), v.begin(), v.end()); };
+    auto cat_d = [](std::vector<double>& d, const std::vector<double>& v) { d.insert(d.end(), v.begin(), v.end()); };
+    cat_i(all.type, t.type); cat_i(all.dyn, t.dyn); cat_i(all.voff, t.voff);
+    cat_d(all.ax, t.ax); cat_d(all.ay, t.ay); cat_d(all.bx, t.bx); cat_d(all.by, t.by); cat_d(all.rad, t.rad); cat_d(all.vx, t.vx); cat_d(all.vy, t.vy);
+    cat_d(all.cx, t.cx); cat_d(all.cy, t.cy); cat_d(all.brad, t.brad); cat_d(all.pvx, t.pvx); cat_d(all.pvy, t.pvy);
+  }
+  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
+  auto up_d = [&](DevBuf<double>& d, const std::vector<double>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream); };
+  // From here on the rows of the previous set are overwritten in place: whatever fails now is a HIP error, and the handle is then left
+  // in single-scene mode (n_scenes = 0) - nothing else consistent is left to return to.
+  hipError_t e = hipSuccess;
+  auto U = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  U(up_i(F.type, all.type)); U(up_i(F.dyn, all.dyn)); U(up_i(F.voff, all.voff));
+  U(up_d(F.ax, all.ax)); U(up_d(F.ay, all.ay)); U(up_d(F.bx, all.bx)); U(up_d(F.by, all.by)); U(up_d(F.rad, all.rad));
+  U(up_d(F.vx, all.vx)); U(up_d(F.vy, all.vy)); U(up_d(F.cx, all.cx)); U(up_d(F.cy, all.cy)); U(up_d(F.brad, all.brad));
+  U(up_d(F.pvx, all.pvx)); U(up_d(F.pvy, all.pvy));
+  if (vias > 0) {
+    U(hipMemcpyAsync(F.viax.p, via_x, vias * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    U(hipMemcpyAsync(F.viay.p, via_y, vias * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  }
+  U(hipStreamSynchronize(h->stream));   // the uploads read `all` and the caller's arrays
+  if (e != hipSuccess) {
+    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear();
+    return fail(TEB_AMD_ERR_HIP, std::string("teb_amd_set_scenes: upload of the scene set -> ") + hipGetErrorString(e));
+  }
+  F.tabs = std::move(tabs);
+  F.via_count = std::move(vc);
+  rc = commit_fleet(h);
+  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); return rc; }
+  F.n_scenes = n_scenes;
+  return TEB_AMD_OK;
+}
+
+int teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_t count) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (count < 0 || (count > 0 && !scene_of)) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_band_scenes: bad arguments");
+  if (count > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more bands than max_tebs");
+  for (int b = 0; b < count; ++b)
+    if (scene_of[b] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_band_scenes: negative scene index");
+  auto& F = h->fleet;
+  F.band_scene.assign((size_t)h->max_tebs, 0);   // bands >= count: scene 0
+  std::copy(scene_of, scene_of + count, F.band_scene.begin());
+  if (F.allocated) {
+    HIPCHK(hipMemcpyAsync(F.scene_of.p, F.band_scene.data(), F.band_scene.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return TEB_AMD_OK;
+}
+
+int teb_amd_clear_scenes(teb_amd_handle_t* h) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  h->fleet.n_scenes = 0;   // the single-scene table, its lists and its layout are as they were
+  h->fleet.tabs.clear(); h->fleet.via_count.clear();
+  return TEB_AMD_OK;
+}
+
+int teb_amd_get_scene_count(teb_amd_handle_t* h, int32_t* n_scenes) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (!n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, "null output");
+  *n_scenes = h->fleet.n_scenes;
+  return TEB_AMD_OK;
+}
+
+int teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best, const int32_t* initial_plan, int32_t* best, double* best_cost) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  auto& F = h->fleet;
+  if (F.n_scenes <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_select_best_per_scene: no scenes set (teb_amd_set_scenes)");
+  if (!best) return fail(TEB_AMD_ERR_INVALID_ARG, "null output");
+  if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs uploaded");
+  const int ns = F.n_scenes;
+  std::vector<int> lb(ns, -1), ip(ns, -1);
+  for (int s = 0; s < ns; ++s) {
+    if (last_best && last_best[s] < h->B) lb[s] = last_best[s];
+    if (initial_plan && initial_plan[s] < h->B) ip[s] = initial_plan[s];
+  }
+  HIPCHK(hipMemcpyAsync(F.sel_last.p, lb.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(F.sel_init.p, ip.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  hipLaunchKernelGGL(select_best_per_scene_kernel, dim3(ns), dim3(kThreads), 0, h->stream, h->cost.p, F.scene_of.p, h->B, F.sel_last.p, F.sel_init.p,
+                     h->cfg.selection_cost_hysteresis, h->cfg.selection_prefer_initial_plan, F.sel_cost.p, F.sel_idx.p);
+  HIPCHK(hipGetLastError());
+  std::vector<double> cst(ns);
+  HIPCHK(hipMemcpyAsync(best, F.sel_idx.p, ns * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(cst.data(), F.sel_cost.p, ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // (lb / ip / cst are read and written until here)
+  if (best_cost) std::copy(cst.begin(), cst.end(), best_cost);
   return TEB_AMD_OK;
 }
 
@@ -1143,9 +1445,24 @@ int teb_amd_optimize_batch(teb_amd_handle_t* h, int32_t inner, int32_t outer, in
   int rc = check_handle(h);
   if (rc) return rc;
   if (inner < 0 || outer < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "negative iteration count");
+  const bool fleet = h->fleet.n_scenes > 0;
+  if (fleet) {   // fleet mode (teb_amd_set_scenes): every band against its own scene, in one launch
+#ifndef TEB_AMD_HAS_FLEET_UNITS
+    return fail(TEB_AMD_ERR_UNSUPPORTED, "fleet launches exist in the product library only; this one is the variant built with [" TEB_AMD_VARIANT_DEFINES "]");
+#else
+    if (h->cfg.jacobian_mode != TEB_AMD_JACOBIAN_ANALYTIC)
+      return fail(TEB_AMD_ERR_INVALID_ARG, "fleet launches need jacobian_mode TEB_AMD_JACOBIAN_ANALYTIC");
+    for (int b = 0; b < h->B; ++b)
+      if (h->fleet.band_scene[b] >= h->fleet.n_scenes) {
+        char buf[160];
+        std::snprintf(buf, sizeof buf, "band %d maps to scene %d, but %d scenes are set (teb_amd_set_band_scenes)", b, h->fleet.band_scene[b], h->fleet.n_scenes);
+        return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+      }
+#endif
+  }
   OptArgs a;
   std::memset(&a, 0, sizeof a);
-  a.inner = inner; a.outer = outer; a.compute_cost = compute_cost; a.no_near_cache = h->opt.no_near_cache != 0; a.band_ldlt = h->solver == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
+  a.inner = inner; a.outer = outer; a.compute_cost = compute_cost; a.no_near_cache = h->opt.no_near_cache != 0; a.band_ldlt = (fleet ? h->fleet.solver : h->solver) == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
   a.obst_scale = obst_cost_scale; a.via_scale = viapoint_cost_scale; a.alt_time = alternative_time_cost;
   if (h->iter_log_on) { a.iter_log = h->iter_log.p; a.iter_log_cap = TEB_AMD_ITERATION_LOG_ROWS; }
   if (h->phase_log_on) a.phase_log = h->phase_log.p;
@@ -1257,6 +1574,7 @@ int teb_amd_get_results(teb_amd_handle_t* h, teb_amd_results_t* out) {
 int teb_amd_select_best(teb_amd_handle_t* h, int32_t last_best, int32_t initial_plan, int32_t* best, double* best_cost) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_select_best"))) return rc;
   if (!best) return fail(TEB_AMD_ERR_INVALID_ARG, "null output");
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs uploaded");
   if (last_best >= h->B) last_best = -1;
@@ -1331,6 +1649,7 @@ int teb_amd_select_best_distributed(teb_amd_handle_t* h, teb_amd_comm_t* c, int3
   int local = TEB_AMD_OK;
   std::string why;
   if (check_handle(h)) { local = TEB_AMD_ERR_INVALID_ARG; why = "bad handle"; }
+  else if (h->fleet.n_scenes > 0) { local = TEB_AMD_ERR_INVALID_ARG; why = "not available while scenes are set (fleet mode); call teb_amd_clear_scenes first"; }
   else if (!best_global) { local = TEB_AMD_ERR_INVALID_ARG; why = "null output"; }
   else if (c->device != h->device) { local = TEB_AMD_ERR_INVALID_ARG; why = "communicator and handle live on different devices"; }
   (void)hipSetDevice(c->device);
@@ -1375,6 +1694,7 @@ int teb_amd_broadcast_band(teb_amd_handle_t* h, teb_amd_comm_t* c, int32_t owner
   int local = TEB_AMD_OK;
   std::string why;
   if (check_handle(h)) { local = TEB_AMD_ERR_INVALID_ARG; why = "bad handle"; }
+  else if (h->fleet.n_scenes > 0) { local = TEB_AMD_ERR_INVALID_ARG; why = "not available while scenes are set (fleet mode); call teb_amd_clear_scenes first"; }
   else if (!n || !x || !y || !theta || !dt || capacity < 2) { local = TEB_AMD_ERR_INVALID_ARG; why = "null output / capacity < 2"; }
   else if (owner_rank < 0 || owner_rank >= c->world) { local = TEB_AMD_ERR_INVALID_ARG; why = "owner_rank out of range"; }
   else if (c->rank == owner_rank && (local_index < 0 || local_index >= h->B)) { local = TEB_AMD_ERR_INVALID_ARG; why = "local_index out of range on the owner"; }
@@ -1751,6 +2071,7 @@ int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_
                                        int32_t capacity) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles_from_costmap"))) return rc;
   if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: no costmap (teb_amd_set_costmap)");
   if (!robot_pose || capacity < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: null pose / negative capacity");
   if (custom && custom->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
@@ -1826,6 +2147,7 @@ int teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const doubl
                                                 int32_t capacity_obstacles, int32_t capacity_points) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles_from_costmap_polygons"))) return rc;
   const char* fn = "teb_amd_set_obstacles_from_costmap_polygons: ";
   if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "no costmap (teb_amd_set_costmap)");
   if (!robot_pose || capacity_obstacles < 0 || capacity_points < 0)
@@ -1958,6 +2280,7 @@ int launch_hsig(teb_amd_handle* h, const BatchDev& bt, int B, double prescaler, 
 int teb_amd_compute_h_signatures(teb_amd_handle_t* h, double prescaler, double* values, int32_t* width) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_compute_h_signatures"))) return rc;
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
   SceneDev sc = scene_of(h);
   BatchDev bt = batch_of(h);
@@ -1979,6 +2302,7 @@ int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, in
                                        int32_t* keep, int32_t* valid, int32_t* reasonable) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_equivalence_classes"))) return rc;
   if (h->hsig_mode == 0 || h->hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures first");
   const int B = h->hsig_B, mode = h->hsig_mode, W = mode == 3 ? h->hsig_M : 2;
   const double* sig = h->hsig_host.data();
@@ -2149,6 +2473,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
                                int32_t* initial_plan_teb) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_explore_candidates"))) return rc;
   if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
   if (n_plan > 0 && (!plan_x || !plan_y || !plan_yaw)) return fail(TEB_AMD_ERR_INVALID_ARG, "null initial plan");
   if (initial_plan_teb) *initial_plan_teb = -1;
@@ -2441,6 +2766,18 @@ int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best
   } else {
     h->hsig_mode = 0;
   }
+  if (!h->fleet.band_scene.empty()) {   // the band -> scene map (teb_amd_set_band_scenes) travels with the bands; the freed slots: scene 0
+    auto& F = h->fleet;
+    std::vector<int> moved(F.band_scene.size(), 0);
+    for (int k = 0; k < K; ++k) moved[k] = F.band_scene[map[k]];
+    if (moved != F.band_scene) {
+      F.band_scene.swap(moved);
+      if (F.allocated) {
+        HIPCHK(hipMemcpyAsync(F.scene_of.p, F.band_scene.data(), F.band_scene.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+      }
+    }
+  }
   h->B = K;
   h->consumers_valid = false; h->nmax_known = -1;
   return TEB_AMD_OK;
@@ -2449,6 +2786,7 @@ int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best
 int teb_amd_filter_detours(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, int32_t best, int32_t* keep) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_detours"))) return rc;
   if (!p || !keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
   const int B = h->B;
   if (B <= 0) return TEB_AMD_OK;
@@ -2597,6 +2935,7 @@ int teb_amd_debug_linearize(teb_amd_handle_t* h, int32_t b, double weight_multip
                             double* chi2, int32_t* assoc_pose, int32_t* assoc_obst, int32_t assoc_cap, int32_t* assoc_count) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_debug_linearize"))) return rc;
   if (b < 0 || b >= h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
   // run the kernel in debug mode on TEB b only: temporarily view the batch as starting at b
   OptArgs a;
@@ -2670,6 +3009,7 @@ int teb_amd_debug_distance(teb_amd_handle_t* h, int32_t nq, const int32_t* obst_
                            const double* theta, const int32_t* spatio_temporal, const double* t, double* dist, double* grad) {
   int rc = check_handle(h);
   if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_debug_distance"))) return rc;
   if (nq <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "nq <= 0");
   for (int q = 0; q < nq; ++q) if (obst_index[q] < 0 || obst_index[q] >= h->M) return fail(TEB_AMD_ERR_INVALID_ARG, "obstacle index out of range");
   DevBuf<int> d_oi, d_st; DevBuf<double> d_x, d_y, d_th, d_t, d_dist, d_grad;

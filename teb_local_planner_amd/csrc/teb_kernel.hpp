@@ -2992,8 +2992,13 @@ enum { SCENE_POINTS = 0, SCENE_GENERIC = 1, SCENE_POINTS_SMALL = 2, SCENE_GENERI
        SCENE_POINTS_CUSTOM = 12, SCENE_POINTS_SMALL_CUSTOM = 13, SCENE_GENERIC_CUSTOM = 14, SCENE_GENERIC_SMALL_CUSTOM = 15 };
 template <int SOLVER, int JMODE, int SCENE>
 __global__ void __launch_bounds__(kThreads)
+#ifdef TEB_AMD_FLEET   // fleet units (teb_fleet_inst.hip): a scene per band, picked below once the band index is known
+teb_optimize_kernel(const teb_amd_config_t c, const FleetDev fl, const BatchDev bt, const OptArgs args,
+                    const LdsPlan plan, const McuDev mc) {
+#else
 teb_optimize_kernel(const teb_amd_config_t c, const SceneDev sc, const BatchDev bt, const OptArgs args,
                     const LdsPlan plan, const McuDev mc) {
+#endif
   extern __shared__ __attribute__((aligned(16))) double lds_base[];
   constexpr bool FAST = SCENE == SCENE_POINTS || SCENE == SCENE_POINTS_SMALL || SCENE == SCENE_POINTS_DEFAULTS || SCENE == SCENE_POINTS_SMALL_DEFAULTS ||
                         SCENE == SCENE_POINTS_WIDE || SCENE == SCENE_POINTS_SMALL_WIDE || SCENE == SCENE_POINTS_LIGHT || SCENE == SCENE_POINTS_SMALL_LIGHT ||
@@ -3025,6 +3030,7 @@ teb_optimize_kernel(const teb_amd_config_t c, const SceneDev sc, const BatchDev 
   static_assert(SCENE != SCENE_POINTS_LIGHT && SCENE != SCENE_POINTS_SMALL_LIGHT, "*_LIGHT kinds need -DTEB_AMD_PROFILE_LIGHT");
 #endif
   static_assert(!MCU || JMODE == TEB_AMD_JACOBIAN_ANALYTIC, "the small-batch kinds exist for closed-form Jacobians");
+#ifndef TEB_AMD_FLEET   // (a fleet launch has no helper workgroups)
   if constexpr (MCU) {
     if (mc.K + mc.D > 0 && (int)blockIdx.x >= bt.B) {   // workgroups B .. B (1 + K + D) - 1: helpers of band (x - B) / (K + D)
       const int per = mc.K + mc.D;
@@ -3037,7 +3043,12 @@ teb_optimize_kernel(const teb_amd_config_t c, const SceneDev sc, const BatchDev 
       return;
     }
   }
+#endif
   const int b = blockIdx.x, tid = threadIdx.x, S = bt.stride;
+#ifdef TEB_AMD_FLEET   // uniform over the workgroup: the record arrives through scalar loads; nothing is written
+  static_assert(!MCU, "fleet units are built for the kinds without helper workgroups");
+  const SceneDev sc = fl.scenes[fl.scene_of[b]];
+#endif
   if (b == 0 && tid == 0) { bt.clk[0] = clock64(); bt.clk[1] = wall_clock64(); }   // shader clock of this launch (a slow box is not a regression)
   const Lds l = carve(lds_base, plan, SOLVER == SOLVER_BANDG ? args.Hband + (size_t)b * args.hband_stride : nullptr, SOLVER == SOLVER_BANDG);
   McuMaster mm;

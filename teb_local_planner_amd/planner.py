@@ -114,6 +114,12 @@ def lib():
         L.teb_amd_comm_destroy.restype = None
         L.teb_amd_select_best_distributed.argtypes = [vp, vp, i32, i32, i32, _abi.p_i32, _abi.p_f64, _abi.p_i32]
         L.teb_amd_broadcast_band.argtypes = [vp, vp, i32, i32, i32, _abi.p_i32, _abi.p_f64, _abi.p_f64, _abi.p_f64, _abi.p_f64]
+        if hasattr(L, "teb_amd_set_scenes"):   # fleet batches (absent from the older builds tools/ compares against through TEB_AMD_LIB)
+            L.teb_amd_set_scenes.argtypes = [vp, i32, C.POINTER(_abi.Obstacles), _abi.p_i32, _abi.p_f64, _abi.p_f64]
+            L.teb_amd_set_band_scenes.argtypes = [vp, _abi.p_i32, i32]
+            L.teb_amd_clear_scenes.argtypes = [vp]
+            L.teb_amd_get_scene_count.argtypes = [vp, _abi.p_i32]
+            L.teb_amd_select_best_per_scene.argtypes = [vp, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_f64]
         _LIB = L
     return _LIB
 
@@ -164,6 +170,40 @@ class TebBatchSolver:
         vy = _abi.f64([v[1] for v in via]) if via else _abi.f64([0.0])
         _chk(lib().teb_amd_set_via_points(self._h, len(via), _abi._ptr(vx, C.c_double), _abi._ptr(vy, C.c_double)),
              "teb_amd_set_via_points")
+
+    # -- fleet batches: a set of scenes and a band -> scene map (include/teb_amd.h) ------------------------
+    def set_scenes(self, tables, vias=None):
+        """Installs one scene per entry of `tables` (ObstacleTable) with its via-points ([(x, y), ...] per scene or None) and enters
+        fleet mode: optimize() then runs every band against the scene set_band_scenes gave it, in one launch."""
+        p = _abi.pack_scenes(tables, vias)
+        _chk(lib().teb_amd_set_scenes(self._h, p.n, p.obstacles, _abi._ptr(p.via_count, C.c_int32), _abi._ptr(p.via_x, C.c_double),
+                                      _abi._ptr(p.via_y, C.c_double)), "teb_amd_set_scenes")
+
+    def set_band_scenes(self, scene_of):
+        a = _abi.i32(scene_of)
+        _chk(lib().teb_amd_set_band_scenes(self._h, _abi._ptr(a, C.c_int32), len(a)), "teb_amd_set_band_scenes")
+
+    def clear_scenes(self):
+        _chk(lib().teb_amd_clear_scenes(self._h), "teb_amd_clear_scenes")
+
+    def scene_count(self):
+        n = C.c_int32(0)
+        _chk(lib().teb_amd_get_scene_count(self._h, C.byref(n)), "teb_amd_get_scene_count")
+        return n.value
+
+    def select_best_per_scene(self, last_best=None, initial_plan=None):
+        """(best [n_scenes] band indices, -1 for a scene without bands; scaled costs [n_scenes]). last_best / initial_plan: band index
+        per scene or -1, None = none."""
+        ns = self.scene_count()
+        best = np.full(max(ns, 1), -1, np.int32); cost = np.zeros(max(ns, 1))
+        lb = None if last_best is None else _abi.i32(last_best)
+        ip = None if initial_plan is None else _abi.i32(initial_plan)
+        for a in (lb, ip):
+            if a is not None and len(a) != ns:
+                raise ValueError("select_best_per_scene: %d entries for %d scenes" % (len(a), ns))
+        _chk(lib().teb_amd_select_best_per_scene(self._h, _abi._ptr(lb, C.c_int32), _abi._ptr(ip, C.c_int32), _abi._ptr(best, C.c_int32),
+                                                 _abi._ptr(cost, C.c_double)), "teb_amd_select_best_per_scene")
+        return best[:ns].copy(), cost[:ns].copy()
 
     # -- state ---------------------------------------------------------------------------------------
     def upload(self, batch):
@@ -752,6 +792,102 @@ class TebOptimalPlanner:
         s.set_costmap(costmap.cells, costmap.resolution, costmap.origin_x, costmap.origin_y)
         return s.is_trajectory_feasible(0, footprint_spec, inscribed_radius, self.cfg_.trajectory.min_resolution_collision_check_angular,
                                         look_ahead_idx, feasibility_check_lookahead_distance)[0]
+
+
+class TebFleetPlanner:
+    """TebOptimalPlanner over a homogeneous fleet: one band per robot on ONE handle, every robot with its own obstacles and via-points
+    (a scene each, teb_amd_set_scenes), all bands optimised in one launch. Configuration and footprint are the fleet's. Robot r is band r
+    and scene r. Each robot's band ends with the bits of a single-scene handle that holds only its scene with the options
+    generic_config_path = 1, multi_cu = -1 (no helper workgroups) and speculative_trials = -1, the same max_poses and the distance path
+    of the fleet (include/teb_amd.h, fleet batches). A default TebOptimalPlanner of that robot runs a kernel folded on the TebConfig
+    defaults, and on scenes that are not point-like it may use helper workgroups: it gives the same bits only as far as those kinds
+    equal the generic one - they are held to that for point scenes (tests/test_gpu_fleet.py); for generic scenes DESIGN.md section 8
+    lists an open defect of the distance helpers, so compare against a handle with the options above."""
+
+    def __init__(self, cfg, n_robots, max_poses=None, max_obstacles=256, max_obstacle_vertices=256, max_via_points=64, device=0, options=None):
+        self.cfg_ = cfg
+        self.n_robots = int(n_robots)
+        self.max_poses = max_poses or min(cfg.trajectory.max_samples + 1, _abi.MAX_POSES)
+        self.teb_ = _abi.TebBatchHost(self.n_robots, self.max_poses)
+        self.device = device
+        self._solver = TebBatchSolver(cfg, self.n_robots, self.max_poses, max(max_obstacles, 1), max(max_obstacle_vertices, 1),
+                                      max(max_via_points, 1), device=device, options=options)
+        self._solver.set_band_scenes(list(range(self.n_robots)))
+        self._resident = [False] * self.n_robots
+        self.optimized_ = np.zeros(self.n_robots, bool)
+        self.last_results = None
+
+    @property
+    def solver(self):
+        return self._solver
+
+    def teb(self):
+        return self.teb_
+
+    def clearPlanner(self, r=None):
+        """clearPlanner() of robot r (None: of every robot): its next plan() initialises a new band."""
+        for k in (range(self.n_robots) if r is None else [r]):
+            self.teb_.n[k] = 0
+            self._resident[k] = False
+            self.optimized_[k] = False
+
+    def plan(self, starts, goals, start_vels=None, obstacles_per_robot=None, via_per_robot=None, free_goal_vel=False):
+        """plan(start, goal, start_vel, free_goal_vel) of every robot (src/optimal_planner.cpp:292-320): per band the warm start on the
+        resident band or initTrajectoryToGoal, exactly as TebOptimalPlanner.plan decides it, then ONE optimize over the fleet.
+        starts / goals: [n_robots] (x, y, theta); start_vels: [n_robots] (vx, vy, omega) or None entries; obstacles_per_robot:
+        [n_robots] ObstacleTable; via_per_robot: [n_robots] [(x, y), ...]. Returns [n_robots] bool (optimizeTEB's return)."""
+        import math
+        s, t, r = self._solver, self.cfg_.trajectory, self.cfg_.robot
+        R = self.n_robots
+        if len(starts) != R or len(goals) != R:
+            raise ValueError("TebFleetPlanner.plan: %d starts / %d goals for %d robots" % (len(starts), len(goals), R))
+        obstacles_per_robot = list(obstacles_per_robot) if obstacles_per_robot is not None else [_abi.ObstacleTable() for _ in range(R)]
+        via_per_robot = list(via_per_robot) if via_per_robot is not None else [[] for _ in range(R)]
+        for k in range(R):
+            start, goal = starts[k], goals[k]
+            n = int(self.teb_.n[k])
+            warm = False
+            if self._resident[k] and n > 0:
+                gx, gy, gth = self.teb_.x[k, n - 1], self.teb_.y[k, n - 1], self.teb_.theta[k, n - 1]
+                d = math.hypot(goal[0] - gx, goal[1] - gy)
+                a = abs((goal[2] - gth + math.pi) % (2 * math.pi) - math.pi)      # fabs(g2o::normalize_theta(...))
+                warm = d < t.force_reinit_new_goal_dist and a < t.force_reinit_new_goal_angular
+            if warm:
+                s.update_and_prune(start, goal, t.min_samples, b=k)                 # updateAndPruneTEB on the device
+            else:
+                s.init_trajectory_line(k, start, goal, 0, r.max_vel_x, t.min_samples, t.allow_init_with_backwards_motion)
+            self._resident[k] = True
+            if start_vels is not None and start_vels[k] is not None:
+                self.teb_.has_vel_start[k] = 1
+                self.teb_.vel_start[k] = start_vels[k]
+            self.teb_.has_vel_goal[k] = 0 if free_goal_vel else 1
+            s.set_velocity_start(self.teb_.vel_start[k], bool(self.teb_.has_vel_start[k]), b=k)
+            s.set_velocity_goal(self.teb_.vel_goal[k], bool(self.teb_.has_vel_goal[k]), b=k)
+        s.set_config(self.cfg_)
+        s.set_scenes(obstacles_per_robot, via_per_robot)
+        o = self.cfg_.optim
+        if not o.optimization_activate:
+            return np.zeros(R, bool)
+        self.optimized_[:] = False
+        s.optimize(o.no_inner_iterations, o.no_outer_iterations)
+        res = s.results()
+        s.download(self.teb_)               # host copy for teb() / the next warm-start test; the bands themselves stay on the device
+        self.last_results = res
+        self.optimized_ = res.status[:R] == _abi.TEB_OK
+        return self.optimized_.copy()
+
+    def getVelocityCommands(self, look_ahead_poses=None):
+        """[(ok, vx, vy, omega)] of every robot: getVelocityCommand on its resident band."""
+        t = self.cfg_.trajectory
+        la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
+        out = []
+        for k in range(self.n_robots):
+            ok, v = self._solver.velocity_command(k, la, t.prevent_look_ahead_poses_near_goal)
+            out.append((ok, float(v[0]), float(v[1]), float(v[2])))
+        return out
+
+    def pose_counts(self):
+        return self._solver.pose_counts()
 
 
 class HomotopyClassPlanner:
