@@ -5,8 +5,10 @@ module. Every derivative is the central-difference quotient of the residual at d
 ~ 1e-80 / 1e-30 = 1e-50), so what comes out is the true derivative to ~ 1e-50 wherever the residual is smooth. The one documented
 exception (cases with kink_delta set) uses delta = 1e-9, the quotient the reference planner's numeric differentiation forms.
 
-The list of edges (which poses with which obstacle / via-point) is integer work tested bit-exact elsewhere and is passed in as
-`irec` (the records of oracle.edges()); every residual, weight, time stamp and derivative is recomputed here.
+The list of edges (which poses with which obstacle / via-point) is integer work and is passed in as `irec` (the records of
+oracle.edges()); every residual, weight, time stamp and derivative is recomputed here. The decisions behind that list - thresholds,
+ties, arg-mins - have an exact reference of their own, tests/hp_association.py, which holds the oracle and the device to it on scenes
+built ON the thresholds (tests/test_hp_association.py, tests/test_gpu_hp_association.py).
 
 Branch margins. A closed form and this reference agree only while both evaluate the same branch of every piecewise definition, so the
 reference records how far each of the following is from its switch point, in the quantity's own unit: penalty arguments from their
@@ -14,7 +16,9 @@ thresholds, |.| arguments from 0, segment parameters u from 0 and 1, the runner-
 that name the same pair of closest points are one feature, not rivals), the two-circle front / rear choice, the holonomic min()
 choices and vt^2 - v^2 from 0, angle differences from 0 (exact arc length, car-like) and from +-pi, ||dS|| from 0. A margin below
 MARGIN = 1e-7 raises BranchMarginError: 1e-7 is 1e8 x fp64 rounding at these magnitudes, so an fp64 implementation takes the same
-branch. No row is ever dropped.
+branch. No row is ever dropped. linearize(exempt=...) leaves NAMED (edge, penalty argument) pairs out of that check for the cases
+that sit on a threshold by construction: accepted only when the argument is exact in fp64 and at least 4 ulp from its switch point
+(_check_exempt) - delta = 1e-30 then stays on one side, and so does any fp64 implementation. The default is unchanged.
 """
 import hashlib
 
@@ -52,10 +56,15 @@ class _Ctx:
         self.margin, self.what, self.on = INF, "", True
         self.allow_exact_zero = allow_exact_zero   # the documented kink: |x| and angle_diff may be EXACTLY 0 (a straight stretch)
         self.args = None   # a list: every kinked function then logs (name, argument, lower switch point, upper switch point)
+        self.exempt = ()   # names of penalty arguments of the CURRENT edge whose distance from their switch points is not noted (linearize: exempt)
 
     def arg(self, what, var, lo, hi):
         if self.args is not None:
             self.args.append((what, var, lo, hi))
+
+    def threshold(self, what, suffix, m):
+        if what not in self.exempt:
+            self.note(what + suffix, m)
 
     def note(self, what, m):
         if self.on and m < self.margin:
@@ -79,7 +88,7 @@ def _interval(cx, what, var, a, eps):
     """var kept inside (-a, a): returns (penalty, side)."""
     lo, hi = -a + eps, a - eps
     cx.arg(what, var, lo, hi)
-    cx.note(what + " from its lower threshold", abs(var - lo)); cx.note(what + " from its upper threshold", abs(var - hi))
+    cx.threshold(what, " from its lower threshold", abs(var - lo)); cx.threshold(what, " from its upper threshold", abs(var - hi))
     if var < lo:
         return -var - (a - eps), -1
     if var <= hi:
@@ -90,7 +99,7 @@ def _interval(cx, what, var, a, eps):
 def _interval2(cx, what, var, a, b, eps):
     lo, hi = a + eps, b - eps
     cx.arg(what, var, lo, hi)
-    cx.note(what + " from its lower threshold", abs(var - lo)); cx.note(what + " from its upper threshold", abs(var - hi))
+    cx.threshold(what, " from its lower threshold", abs(var - lo)); cx.threshold(what, " from its upper threshold", abs(var - hi))
     if var < lo:
         return -var + (a + eps), -1
     if var <= hi:
@@ -100,7 +109,7 @@ def _interval2(cx, what, var, a, b, eps):
 
 def _below(cx, what, var, a, eps):
     cx.arg(what, var, a + eps, None)
-    cx.note(what + " from its threshold", abs(var - (a + eps)))
+    cx.threshold(what, " from its threshold", abs(var - (a + eps)))
     if var >= a + eps:
         return mpf(0), 0
     return -var + (a + eps), -1
@@ -538,8 +547,41 @@ def switch_arguments(cfg, obst, via, batch, b, wm, irec, only=None):
         return out
 
 
-def linearize(cfg, obst, via, batch, b, wm, irec, kink_delta=None):
+EXEMPT_ULPS = 4
+
+
+def _check_exempt(g, rec, names):
+    """An exempted penalty argument must be EXACT in fp64 (every operation rounded to 53 bits gives the 80-digit value, switch points
+    included) and lie at least EXEMPT_ULPS ulp (of the smaller of the two numbers) from each switch point: an fp64 implementation then
+    holds the same argument on the same side, and delta = 1e-30 stays on that side too."""
+    ty, var, fixed, val, aux = g.edge(rec)
+    logs = []
+    for prec in (None, 53):
+        cx = _Ctx(False)
+        cx.on, cx.args = False, []
+        with (mpmath.workprec(prec) if prec else mpmath.workdps(DPS)):
+            _RESIDUAL[ty](cx, g.P, list(val), aux)
+        logs.append(cx.args)
+    seen = set()
+    for (w, v, lo, hi), (w64, v64, lo64, hi64) in zip(*logs):
+        if w not in names:
+            continue
+        seen.add(w)
+        if not (w == w64 and v == v64 and lo == lo64 and hi == hi64):
+            raise BranchMarginError("exempted argument '%s' is not exact in fp64: %s" % (w, mpmath.nstr(v, 25)))
+        for thr in (lo, hi):
+            if thr is not None:
+                ulp = float(np.spacing(min(abs(float(v)), abs(float(thr)))))
+                if abs(v - thr) < EXEMPT_ULPS * ulp:
+                    raise BranchMarginError("exempted argument '%s' is %s from its switch point: less than %d ulp" % (w, mpmath.nstr(abs(v - thr), 5), EXEMPT_ULPS))
+    if seen != set(names):
+        raise BranchMarginError("exempted arguments %s are not evaluated by this edge" % sorted(set(names) - seen))
+
+
+def linearize(cfg, obst, via, batch, b, wm, irec, kink_delta=None, exempt=None):
     """The reference linearisation of band b. irec: the edge records of oracle.edges() (only their integer part is read).
+    exempt: {(index into irec, name of a penalty argument)} - pairs left out of the MARGIN check on the distance from their switch points
+    (cases that sit ON a threshold by construction, tests/hp_association.py); each is accepted only under _check_exempt.
     Returns dict(H {(a, c): mpf, a >= c}, b [4n] mpf, chi2 [4] mpf, rows {(type, row): [rows, non-zero, side +, side -]},
     ring_only / inside (inflated static obstacle rows), margin, margin_what, n)."""
     with mpmath.workdps(DPS):
@@ -549,9 +591,15 @@ def linearize(cfg, obst, via, batch, b, wm, irec, kink_delta=None):
         cx = _Ctx(kink_delta is not None)
         H, bv, chi2 = {}, [mpf(0)] * (4 * n), [mpf(0)] * 4
         rows, ring_only, inside = {}, 0, 0
-        for rec in irec:
+        by_edge = {}
+        for e, name in (exempt or ()):
+            by_edge.setdefault(int(e), set()).add(name)
+        for e, rec in enumerate(irec):
             ty, var, fixed, val, aux = g.edge(rec)
             fun, w = _RESIDUAL[ty], P.weights[ty]
+            cx.exempt = by_edge.get(e, ())
+            if cx.exempt:
+                _check_exempt(g, rec, cx.exempt)
             cx.on = True
             base = fun(cx, P, val, aux)
             cx.on = False
