@@ -28,6 +28,7 @@
 #include "teb_feasibility.hpp"
 #include "teb_costmap_obstacles.hpp"
 #include "teb_costmap_polygons.hpp"
+#include "teb_scene_store.hpp"
 
 using namespace tebamd;
 
@@ -56,55 +57,6 @@ int fail(int code, const std::string& msg) {
     if (_e != hipSuccess)                                                                              \
       return fail(TEB_AMD_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(_e));               \
   } while (0)
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    n = count;
-    if (count == 0) count = 1;
-    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-  }
-  void free() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-};
-
-// PolygonObstacle::calcCentroid (reference src/obstacles.cpp:56-121) — product-side implementation
-void polygon_centroid(const double* vx, const double* vy, int n, double& cx, double& cy) {
-  if (n <= 0) { cx = cy = std::numeric_limits<double>::quiet_NaN(); return; }
-  if (n == 1) { cx = vx[0]; cy = vy[0]; return; }
-  if (n == 2) { cx = 0.5 * (vx[0] + vx[1]); cy = 0.5 * (vy[0] + vy[1]); return; }
-  double A = 0;
-  for (int i = 0; i < n - 1; ++i) A += vx[i] * vy[i + 1] - vx[i + 1] * vy[i];
-  A += vx[n - 1] * vy[0] - vx[0] * vy[n - 1];
-  A *= 0.5;
-  if (A != 0) {
-    cx = 0; cy = 0;
-    for (int i = 0; i < n - 1; ++i) {
-      double aux = vx[i] * vy[i + 1] - vx[i + 1] * vy[i];
-      cx += (vx[i] + vx[i + 1]) * aux;
-      cy += (vy[i] + vy[i + 1]) * aux;
-    }
-    double aux = vx[n - 1] * vy[0] - vx[0] * vy[n - 1];
-    cx += (vx[n - 1] + vx[0]) * aux;
-    cy += (vy[n - 1] + vy[0]) * aux;
-    cx /= (6 * A);
-    cy /= (6 * A);
-    return;
-  }
-  int ic = 0, jc = 0;
-  double md = 0;
-  for (int i = 0; i < n; ++i)
-    for (int j = i + 1; j < n; ++j) {
-      double d = std::sqrt((vx[j] - vx[i]) * (vx[j] - vx[i]) + (vy[j] - vy[i]) * (vy[j] - vy[i]));
-      if (d > md) { md = d; ic = i; jc = j; }
-    }
-  cx = 0.5 * (vx[ic] + vx[jc]);
-  cy = 0.5 * (vy[ic] + vy[jc]);
-}
 
 // K9: selectBestTeb on the resident cost array (src/homotopy_class_planner.cpp:564-667)
 __global__ void select_best_kernel(const double* cost, int count, int last_best, int initial_plan, double hyst,
@@ -152,6 +104,15 @@ __global__ void distance_kernel(const teb_amd_config_t c, const SceneDev sc, int
 
 }  // namespace
 
+// The distance path and the layout chosen for the tables of a scene store (choose_scene_layout).
+struct SceneLayout {
+  int solver = 0;        // SOLVER_*
+  int fast_points = 0;   // SCENE_POINTS: every table and the footprint point-like and the cache of the largest table fits the LDS
+  int max_cache = 0;     // most rows of a table: what the obstacle cache of the LDS plan is made for
+  LdsPlan plan;
+  int cache_entries() const { return fast_points ? max_cache : 0; }   // 0: generic distance path
+};
+
 struct teb_amd_handle {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -159,14 +120,12 @@ struct teb_amd_handle {
   teb_amd_config_t cfg;
   int max_tebs = 0, stride = 0, max_obst = 0, max_verts = 0, max_via = 0;
   int B = 0, M = 0, nvia = 0, n_static = 0, n_dyn = 0;
-  size_t lds_bytes = 0;
-  int solver = 0, solver_created = 0;   // solver_created: the choice of teb_amd_create; teb_amd_set_obstacles may move a band to HBM
+  int solver_created = 0;   // the layout chosen by teb_amd_create; teb_amd_set_obstacles may move a band to HBM (layout.solver)
   size_t hmat_stride = 0;
   int band_ldlt = 0;   // SOLVER_BAND: 1 = sequential banded LDL^T (teb_amd_options_t::band_ldlt), 0 = hybrid cyclic reduction
   size_t lds_limit = 0;
   int num_cus = 0;
-  LdsPlan plan;
-  int fast_points = 0;
+  SceneLayout layout;   // of the single scene
   int static_radius_zero = 0;   // every obstacle of the static list enters the LDS cache with radius 0 (no circular obstacle among them)
   int last_defaults_profile = 0;   // the last optimise launch ran a *_DEFAULTS instantiation (teb_amd_debug_last_config_profile)
   int last_inst[3] = {-1, -1, -1}; // (layout, Jacobian mode, scene kind) of the instantiation the last optimise launch ran (teb_amd_debug_last_instantiation)
@@ -175,13 +134,11 @@ struct teb_amd_handle {
   int snap_nmax = -1;      // nmax_known at the time of teb_amd_snapshot_state
   int snap_B = -1;         // B at that time (the bound covers those bands only)
   int nmax_known = -1;     // upper bound of the resident pose counts as far as the host knows it, -1 = unknown (device-side producers ran)
-  // host copy of the last obstacle table: teb_amd_set_config re-derives the static / dynamic lists from it
-  struct HostObst { std::vector<int> type, dyn, voff; std::vector<double> ax, ay, bx, by, rad, vx, vy, cx, cy, brad, pvx, pvy; } hob;
+  // the single scene (teb_scene_store.hpp): host copy of the last obstacle table - teb_amd_set_config re-derives the static / dynamic
+  // lists from it, candidate generation reads its centroids -, the static list derived from it, and its device store
+  HostObst hob;
   std::vector<int> host_static;
-  // scene
-  DevBuf<int> o_type, o_dyn, o_voff, o_static, o_dynidx;
-  DevBuf<double> o_ax, o_ay, o_bx, o_by, o_rad, o_vx, o_vy, o_cx, o_cy, o_brad, o_pvx, o_pvy, viax, viay;
-  DevBuf<double> o_list;   // [5][max_obst]: x, y, radius, vx, vy in the order of the LDS obstacle cache (SceneDev::lox ..)
+  DevSceneStore scene;
   // batch
   DevBuf<int> n, has_vs, has_vg, rotdir, via_en, status, optimized, iters, last_iters, trials, assoc_cnt, assoc, assoc_ovf, via_pose, legacy_idx;
   DevBuf<double> x, y, th, dt, vs, vg, chi2, cost, lambda, Hbackup, Hband, ob_x, ob_y, ob_th, ob_dt;   // ob_*: strips before an optimistic launch
@@ -229,9 +186,7 @@ struct teb_amd_handle {
   int consumers_la = 0, consumers_prevent = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
-  std::vector<int> host_type;
-  // candidate generation (f3): host copy of the obstacle centroids, graph + candidate scratch strips, boost-compatible generator
-  std::vector<double> host_cx, host_cy;
+  // candidate generation (f3): graph + candidate scratch strips, boost-compatible generator
   DevBuf<double> g_vx, g_vy, cand_x, cand_y, cand_th, cand_dt, cand_sig, cand_px, cand_py, tmp_x, tmp_y, tmp_th, tmp_dt, tmp_vs, tmp_vg,
       tmp_chi2, tmp_cost, tmp_lambda;
   DevBuf<int> cand_n, cand_off, cand_map, tmp_n, tmp_i;
@@ -254,21 +209,25 @@ struct teb_amd_handle {
   DevBuf<int> cmp_cnt, cmp_off;
   DevBuf<double> cmp_x, cmp_y;
   std::mt19937 rnd_generator;   // ProbRoadmapGraph::rnd_generator_ (graph_search.h:211): default-seeded 32-bit Mersenne twister
-  // fleet batches (teb_fleet.hpp, teb_amd_set_scenes): a second set of scene buffers, allocated at the first teb_amd_set_scenes and
-  // sized by the capacities of the handle; rows, vertices and via-points of the scenes one after the other
+  // fleet batches (teb_fleet.hpp, teb_amd_set_scenes): the scene set - a second DevSceneStore, allocated at the first
+  // teb_amd_set_scenes and sized by the capacities of the handle, with the rows, vertices and via-points of the scenes one after the
+  // other (scene_segments) - and what a fleet launch needs beside it
   struct Fleet {
     int n_scenes = 0;               // 0 = single-scene mode
     bool allocated = false;
     std::vector<HostObst> tabs;     // host copy of every scene's table: teb_amd_set_config re-derives the lists from them
     std::vector<int> via_count;
     std::vector<int> band_scene;    // [max_tebs] scene of every band (teb_amd_set_band_scenes); survives set / clear
-    int fast_points = 0;            // SCENE_POINTS: every scene and the footprint point-like and the cache of the largest scene fits
-    int max_cache = 0;              // largest n_static + n_dyn of a scene: what the LDS plans of a fleet launch are made for
-    int solver = 0;                 // layout of a fleet launch (the single-scene choice h->solver is not touched)
-    LdsPlan plan;
-    DevBuf<int> type, dyn, voff, stat, dynidx, scene_of, sel_last, sel_init, sel_idx;
-    DevBuf<double> ax, ay, bx, by, rad, vx, vy, cx, cy, brad, pvx, pvy, viax, viay, list, sel_cost;
+    SceneLayout layout;             // of a fleet launch (the single-scene choice h->layout is not touched)
+    DevSceneStore store;
+    DevBuf<int> scene_of, sel_last, sel_init, sel_idx;
+    DevBuf<double> sel_cost;
     DevBuf<SceneDev> scenes;
+    void release() {   // the device side
+      store.free();
+      free_all(scene_of, sel_last, sel_init, sel_idx, sel_cost, scenes);
+      allocated = false;
+    }
   } fleet;
 };
 
@@ -280,29 +239,8 @@ int check_handle(teb_amd_handle* h) {
   return TEB_AMD_OK;
 }
 
-void fleet_free(teb_amd_handle* h) {
-  auto& F = h->fleet;
-  DevBuf<int>* ib[] = {&F.type, &F.dyn, &F.voff, &F.stat, &F.dynidx, &F.scene_of, &F.sel_last, &F.sel_init, &F.sel_idx};
-  for (auto* q : ib) q->free();
-  DevBuf<double>* db[] = {&F.ax, &F.ay, &F.bx, &F.by, &F.rad, &F.vx, &F.vy, &F.cx, &F.cy, &F.brad, &F.pvx, &F.pvy, &F.viax, &F.viay, &F.list, &F.sel_cost};
-  for (auto* q : db) q->free();
-  F.scenes.free();
-  F.allocated = false;
-}
-
 SceneDev scene_of(teb_amd_handle* h) {
-  SceneDev s;
-  s.M = h->M;
-  s.fast_points = h->fast_points;
-  s.static_radius_zero = h->static_radius_zero;
-  s.type = h->o_type.p; s.ax = h->o_ax.p; s.ay = h->o_ay.p; s.bx = h->o_bx.p; s.by = h->o_by.p;
-  s.rad = h->o_rad.p; s.vx = h->o_vx.p; s.vy = h->o_vy.p; s.cx = h->o_cx.p; s.cy = h->o_cy.p; s.brad = h->o_brad.p;
-  s.dyn = h->o_dyn.p; s.voff = h->o_voff.p; s.pvx = h->o_pvx.p; s.pvy = h->o_pvy.p;
-  s.n_static = h->n_static; s.static_idx = h->o_static.p; s.n_dyn = h->n_dyn; s.dyn_idx = h->o_dynidx.p;
-  s.nvia = h->nvia; s.viax = h->viax.p; s.viay = h->viay.p;
-  const size_t mo = (size_t)(h->max_obst > 0 ? h->max_obst : 1);
-  s.lox = h->o_list.p; s.loy = h->o_list.p + mo; s.lor = h->o_list.p + 2 * mo; s.lovx = h->o_list.p + 3 * mo; s.lovy = h->o_list.p + 4 * mo;
-  return s;
+  return h->scene.view(SceneSegment{}, h->M, h->nvia, h->n_static, h->n_dyn, h->static_radius_zero, h->layout.fast_points);
 }
 
 BatchDev batch_of(teb_amd_handle* h) {
@@ -395,7 +333,7 @@ const void* fleet_kernel(int solver, int scene) {
 }
 // one workgroup per band, every band against fleet.scenes[fleet.scene_of[b]]: no helper workgroups, no run-time compilation
 hipError_t launch_fleet(teb_amd_handle* h, int grid, const BatchDev& bt, const OptArgs& a, int solver, const LdsPlan& plan) {
-  const int scene_kind = h->fleet.fast_points ? SCENE_POINTS : SCENE_GENERIC;
+  const int scene_kind = h->fleet.layout.fast_points ? SCENE_POINTS : SCENE_GENERIC;
   const void* k = fleet_kernel(solver, scene_kind);
   h->last_defaults_profile = 0;
   h->last_inst[0] = solver; h->last_inst[1] = TEB_AMD_JACOBIAN_ANALYTIC; h->last_inst[2] = -1;
@@ -408,9 +346,9 @@ hipError_t launch_fleet(teb_amd_handle* h, int grid, const BatchDev& bt, const O
   void* params[] = {const_cast<teb_amd_config_t*>(&h->cfg), &fl, const_cast<BatchDev*>(&bt), const_cast<OptArgs*>(&a), const_cast<LdsPlan*>(&plan), &none};
   return hipLaunchKernel(k, dim3(grid), dim3(kThreads), params, plan.total_bytes, h->stream);
 }
+// one workgroup per band (and its helper workgroups, mcu) against the scene sc, in the layout `solver` with its LDS plan
 hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const BatchDev& bt, const OptArgs& a, int solver, const LdsPlan& plan,
                       const McuDev* mcu = nullptr) {
-  if (h->fleet.n_scenes > 0) return launch_fleet(h, grid, bt, a, solver, plan);
   McuDev none;
   std::memset(&none, 0, sizeof none);
   const McuDev* mc = mcu ? mcu : &none;
@@ -449,10 +387,6 @@ hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const Bat
   h->last_inst[2] = scene_kind;
   return hipLaunchKernel(k, dim3(grid * (1 + mc->K + mc->D)), dim3(kThreads), params, plan.total_bytes, h->stream);
 }
-hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const BatchDev& bt, const OptArgs& a) {
-  if (h->fleet.n_scenes > 0) return launch_opt(h, grid, sc, bt, a, h->fleet.solver, h->fleet.plan);
-  return launch_opt(h, grid, sc, bt, a, h->solver, h->plan);
-}
 
 // Multi-CU mode (teb_multicu.hpp): helper workgroups per band of this launch - K solver helpers (speculative LM trials, any scene kind)
 // and D distance helpers (generic scenes: association + distance records). Small batches only: one workgroup per CU (the LDS footprint
@@ -471,7 +405,7 @@ void mcu_helpers_for(teb_amd_handle* h, const OptArgs& args, int eff_solver, int
     K = h->opt.speculative_trials > 0 ? std::min((int)h->opt.speculative_trials, kMcuMaxSpec) : kMcuMaxSpec;
     K = std::max(0, std::min(K, room));
   }
-  if (h->opt.multi_cu >= 0 && !h->fast_points && !h->cfg.legacy_obstacle_association && h->M > 0) {
+  if (h->opt.multi_cu >= 0 && !h->layout.fast_points && !h->cfg.legacy_obstacle_association && h->M > 0) {
     D = std::min(room - K, 60);                               // beyond ~ 5 poses per helper the hand-off costs more than the tile
     // ... and that holds for short bands as well: at most one helper per 6 poses of the handle's capacity (round 6; until then a 60-pose
     // band could be given 60 helpers with a pose each). This is also where the one known defect of the mode lives: with 40 - 60 helpers on
@@ -556,6 +490,10 @@ static int copy_strips(teb_amd_handle_t* h, const Strips& dst, const Strips& src
 
 int launch(teb_amd_handle* h, const OptArgs& args) {
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs uploaded");
+  // What the launch runs against, decided ONCE: the single scene of the handle, or the scene set (teb_amd_set_scenes) - then the layout,
+  // the plan and the obstacle cache are those of the set (its largest scene).
+  const bool fleet = h->fleet.n_scenes > 0;
+  const SceneLayout& own = fleet ? h->fleet.layout : h->layout;
   SceneDev sc = scene_of(h);
   BatchDev bt = batch_of(h);
   // The layout of the normal matrix follows the pose capacity of the handle (blocks in LDS <= 238 poses, band in LDS <= 337, band in
@@ -563,13 +501,14 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
   // launched in the fastest layout that leaves the bands 10 % room to grow (autoResize); should a band outgrow it all the same, the
   // launch is repeated from the saved strips in the handle's own layout. Results do not depend on the layout (same arithmetic up to
   // the order of the block reduction). TEB_AMD_FIXED_LAYOUT=1 switches this off.
-  // fleet mode (teb_amd_set_scenes): the layout, the plan and the obstacle cache are those of the scene set (its largest scene)
-  const bool fleet = h->fleet.n_scenes > 0;
-  const int own_solver = fleet ? h->fleet.solver : h->solver;
-  int eff_solver = own_solver;
-  LdsPlan eff_plan = fleet ? h->fleet.plan : h->plan;
+  int eff_solver = own.solver;
+  LdsPlan eff_plan = own.plan;
+  // (a fleet launch has no helper workgroups: mcu is null then)
+  auto run = [&](int solver, const LdsPlan& plan, const McuDev* mcu) {
+    return fleet ? launch_fleet(h, h->B, bt, args, solver, plan) : launch_opt(h, h->B, sc, bt, args, solver, plan, mcu);
+  };
   bool optimistic = false;
-  if (own_solver != SOLVER_CR && !args.debug_linearize && !h->opt.fixed_layout && h->opt.layout == TEB_AMD_LAYOUT_AUTO && !h->band_ldlt) {
+  if (own.solver != SOLVER_CR && !args.debug_linearize && !h->opt.fixed_layout && h->opt.layout == TEB_AMD_LAYOUT_AUTO && !h->band_ldlt) {
     int nmax = h->nmax_known;
     if (nmax < 0) {   // a device-side producer changed the bands since the host last saw their pose counts
       std::vector<int> n(h->B);
@@ -579,9 +518,9 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
       for (int v : n) nmax = std::max(nmax, v);
     }
     const int need = nmax + nmax / 10 + 4;   // 10 % room to grow; a band that needs more triggers the repeat below
-    const int ob = fleet ? (h->fleet.fast_points ? h->fleet.max_cache : 0) : (h->fast_points ? h->M : 0);
+    const int ob = own.cache_entries();
     const int s_cr = max_capacity_of(h, SOLVER_CR, std::min(h->stride, 238), ob);
-    const int s_band = own_solver == SOLVER_BANDG ? max_capacity_of(h, SOLVER_BAND, std::min(h->stride, 337), ob) : 0;
+    const int s_band = own.solver == SOLVER_BANDG ? max_capacity_of(h, SOLVER_BAND, std::min(h->stride, 337), ob) : 0;
     if (s_cr > 0 && need <= s_cr) { eff_solver = SOLVER_CR; eff_plan = make_lds_plan(s_cr, SOLVER_CR, ob, h->lds_limit); optimistic = true; }
     else if (s_band > 0 && need <= s_band) { eff_solver = SOLVER_BAND; eff_plan = make_lds_plan(s_band, SOLVER_BAND, ob, h->lds_limit); optimistic = true; }
   }
@@ -631,7 +570,7 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
   if (h->opt.compile_for_config >= 2 && !fleet)   // synchronous mode: the wait for the compiler is not kernel time
     (void)rtc_lookup(h, args, sc, eff_solver, H > 0, profile_matches(h, args, sc), true);
   HIPCHK(hipEventRecord(h->ev0, h->stream));   // (the kernel clears its bands' overflow flags itself)
-  HIPCHK(launch_opt(h, h->B, sc, bt, args, eff_solver, eff_plan, H > 0 ? &mcu : nullptr));
+  HIPCHK(run(eff_solver, eff_plan, H > 0 ? &mcu : nullptr));
   if (H > 0 && h->mcu_trace && h->mcu_watchdog_ms > 0) {
     // diagnostic: a multi-CU launch that does not finish in time is reported with the breadcrumbs of its workgroups, and the process ends
     // (a kernel cannot be cancelled; the bounded spins of the kernel make this unreachable unless the protocol itself is broken)
@@ -669,14 +608,14 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
       if (!own_layout) {
         // helpers late, no band outgrown so far: once more in the optimistic layout - whose capacity a band may outgrow in THIS run
         // (the first one was cut short), so its flags are read as well
-        HIPCHK(launch_opt(h, h->B, sc, bt, args, eff_solver, eff_plan));
+        HIPCHK(run(eff_solver, eff_plan, nullptr));
         HIPCHK(hipMemcpyAsync(ovf.data(), h->assoc_ovf.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         for (int v : ovf) own_layout = own_layout || (v & 2);
         if (own_layout)
           if (int crc = copy_strips(h, Strips{h->x.p, h->y.p, h->th.p, h->dt.p, h->n.p}, Strips{h->ob_x.p, h->ob_y.p, h->ob_th.p, h->ob_dt.p, h->ob_n.p}, h->B)) return crc;
       }
-      if (own_layout) HIPCHK(launch_opt(h, h->B, sc, bt, args));   // ev0 stays where it was: the reported time includes the discarded launches
+      if (own_layout) HIPCHK(run(own.solver, own.plan, nullptr));   // ev0 stays where it was: the reported time includes the discarded launches
       h->mcu_last_repeated = helpers_late ? 1 : 0;
       h->nmax_known = -1;
     }
@@ -804,11 +743,10 @@ int teb_amd_create_ex(const teb_amd_config_t* cfg, int32_t max_tebs, int32_t max
   h->opt = opt;
   h->max_tebs = max_tebs; h->stride = max_poses; h->max_obst = max_obstacles; h->max_verts = max_obstacle_vertices;
   h->max_via = max_via_points;
-  h->lds_bytes = lds;
-  h->solver = solver; h->solver_created = solver;
+  h->layout.solver = solver; h->solver_created = solver;
   h->lds_limit = lds_limit;
   h->num_cus = prop.multiProcessorCount;
-  h->plan = make_lds_plan(max_poses, solver, 0, h->lds_limit);
+  h->layout.plan = make_lds_plan(max_poses, solver, 0, h->lds_limit);
   // per-band HBM buffer: the copy of H for rejected trials (SOLVER_CR, banded LDL^T) or the blocks the cyclic reduction of a
   // SOLVER_BAND handle works on (D, L, f: nb * (2 * kBlk + 8) doubles)
   h->hmat_stride = std::max(hbm_scratch_doubles(max_poses, SOLVER_BAND), hbm_scratch_doubles(max_poses, solver));   // every layout may be launched
@@ -824,12 +762,7 @@ int teb_amd_create_ex(const teb_amd_config_t* cfg, int32_t max_tebs, int32_t max
   const size_t Mo = max_obstacles > 0 ? max_obstacles : 1;
   bool ok = true;
   auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
-  A(h->o_type.alloc(Mo)); A(h->o_dyn.alloc(Mo)); A(h->o_voff.alloc(Mo + 1)); A(h->o_static.alloc(Mo)); A(h->o_dynidx.alloc(Mo));
-  A(h->o_list.alloc(5 * (size_t)Mo));
-  A(h->o_ax.alloc(Mo)); A(h->o_ay.alloc(Mo)); A(h->o_bx.alloc(Mo)); A(h->o_by.alloc(Mo)); A(h->o_rad.alloc(Mo));
-  A(h->o_vx.alloc(Mo)); A(h->o_vy.alloc(Mo)); A(h->o_cx.alloc(Mo)); A(h->o_cy.alloc(Mo)); A(h->o_brad.alloc(Mo));
-  A(h->o_pvx.alloc(max_obstacle_vertices)); A(h->o_pvy.alloc(max_obstacle_vertices));
-  A(h->viax.alloc(max_via_points)); A(h->viay.alloc(max_via_points));
+  if (!h->scene.alloc(Mo, 1, max_obstacle_vertices, max_via_points, 0)) ok = false;
   A(h->n.alloc(max_tebs)); A(h->has_vs.alloc(max_tebs)); A(h->has_vg.alloc(max_tebs)); A(h->rotdir.alloc(max_tebs));
   A(h->via_en.alloc(max_tebs)); A(h->status.alloc(max_tebs)); A(h->optimized.alloc(max_tebs)); A(h->iters.alloc(max_tebs)); A(h->last_iters.alloc(max_tebs)); A(h->trials.alloc(max_tebs));
   A(h->assoc_cnt.alloc(BS)); A(h->assoc.alloc(BS * Mo)); A(h->assoc_ovf.alloc(max_tebs)); A(h->legacy_idx.alloc((size_t)max_tebs * Mo));
@@ -872,31 +805,17 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
   if (!h) return;
   (void)hipSetDevice(h->device);
   if (h->stream) (void)hipStreamSynchronize(h->stream);
-  DevBuf<int>* ib[] = {&h->o_type, &h->o_dyn, &h->o_voff, &h->o_static, &h->o_dynidx, &h->n, &h->has_vs, &h->has_vg, &h->rotdir,
-                       &h->via_en, &h->status, &h->optimized, &h->iters, &h->last_iters, &h->trials, &h->assoc_cnt, &h->assoc, &h->assoc_ovf, &h->via_pose, &h->legacy_idx,
-                       &h->snap_n, &h->sel_idx, &h->err_flag, &h->hs_pex};
-  for (auto* q : ib) q->free();
-  DevBuf<double>* db[] = {&h->o_ax, &h->o_ay, &h->o_bx, &h->o_by, &h->o_rad, &h->o_vx, &h->o_vy, &h->o_cx, &h->o_cy, &h->o_brad, &h->o_pvx,
-                          &h->o_pvy, &h->o_list, &h->viax, &h->viay, &h->x, &h->y, &h->th, &h->dt, &h->vs, &h->vg, &h->chi2, &h->cost,
-                          &h->lambda, &h->Hbackup, &h->Hband, &h->ob_x, &h->ob_y, &h->ob_th, &h->ob_dt, &h->snap_x, &h->snap_y, &h->snap_th, &h->snap_dt, &h->dbg_H,
-                          &h->dbg_b, &h->dbg_chi2, &h->sel_cost, &h->stage_x, &h->stage_y, &h->stage_yaw, &h->out_cmd, &h->out_prof, &h->out_traj, &h->hsig, &h->hs_pre, &h->hs_pim};
-  for (auto* q : db) q->free();
-  DevBuf<double>* gb[] = {&h->g_vx, &h->g_vy, &h->cand_x, &h->cand_y, &h->cand_th, &h->cand_dt, &h->cand_sig, &h->cand_px, &h->cand_py,
-                          &h->tmp_x, &h->tmp_y, &h->tmp_th, &h->tmp_dt, &h->tmp_vs, &h->tmp_vg, &h->tmp_chi2, &h->tmp_cost, &h->tmp_lambda};
-  for (auto* q : gb) q->free();
-  DevBuf<int>* gi[] = {&h->cand_n, &h->cand_off, &h->cand_map, &h->tmp_n, &h->tmp_i};
-  for (auto* q : gi) q->free();
-  h->ob_n.free();
-  h->iter_log.free();
-  h->phase_log.free();
-  h->mcu_ctl.free(); h->mcu_pub.free(); h->mcu_items.free(); h->mcu_spec.free();
+  h->scene.free();
+  h->fleet.release();
+  free_all(h->n, h->has_vs, h->has_vg, h->rotdir, h->via_en, h->status, h->optimized, h->iters, h->last_iters, h->trials, h->assoc_cnt, h->assoc, h->assoc_ovf,
+           h->via_pose, h->legacy_idx, h->snap_n, h->sel_idx, h->err_flag, h->hs_pex, h->x, h->y, h->th, h->dt, h->vs, h->vg, h->chi2, h->cost, h->lambda,
+           h->Hbackup, h->Hband, h->ob_x, h->ob_y, h->ob_th, h->ob_dt, h->ob_n, h->snap_x, h->snap_y, h->snap_th, h->snap_dt, h->dbg_H, h->dbg_b, h->dbg_chi2,
+           h->sel_cost, h->stage_x, h->stage_y, h->stage_yaw, h->out_cmd, h->out_prof, h->out_traj, h->hsig, h->hs_pre, h->hs_pim, h->g_vx, h->g_vy, h->cand_x,
+           h->cand_y, h->cand_th, h->cand_dt, h->cand_sig, h->cand_px, h->cand_py, h->tmp_x, h->tmp_y, h->tmp_th, h->tmp_dt, h->tmp_vs, h->tmp_vg, h->tmp_chi2,
+           h->tmp_cost, h->tmp_lambda, h->cand_n, h->cand_off, h->cand_map, h->tmp_n, h->tmp_i, h->iter_log, h->phase_log, h->mcu_ctl, h->mcu_pub, h->mcu_items,
+           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cmo_cnt, h->cmp_cnt, h->cmp_off, h->cmp_x, h->cmp_y);
   if (h->mcu_trace) (void)hipHostFree(h->mcu_trace);
   if (h->pack_host) (void)hipHostFree(h->pack_host);
-  h->pack_dev.free();
-  h->g_adj.free();
-  h->cm_cells.free(); h->cm_fp.free(); h->cm_out.free(); h->cmo_cnt.free();
-  h->cmp_cnt.free(); h->cmp_off.free(); h->cmp_x.free(); h->cmp_y.free();
-  fleet_free(h);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
@@ -904,46 +823,16 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
 }
 
 namespace {
-// What ONE scene's kernels read beyond the rows of its table (parse_obstacle_table: the rows, centroids, bounding radii), derived from
-// the table and the configuration - the single-scene path (commit_obstacles) and every scene of a fleet (commit_fleet) call it:
-// the lists AddEdgesObstacles / AddEdgesDynamicObstacles visit, the obstacles in cache order, static_radius_zero, point-likeness.
-struct SceneLists {
-  std::vector<int> st, dy;
-  std::vector<double> lo;        // [5][stride]: x, y, radius, vx, vy in cache order (static list, then dynamic list)
-  int static_radius_zero = 1;    // no circular obstacle with a radius in the static list
-  bool pointlike_rows = true;    // every row is Point / Circular
-};
-void derive_scene_lists(const teb_amd_config_t& cfg, const teb_amd_handle::HostObst& o, size_t stride, SceneLists& d) {
-  const int M = (int)o.type.size();
-  d.st.clear(); d.dy.clear();
-  for (int i = 0; i < M; ++i) {
-    // AddEdgesObstacles skips dynamic obstacles iff include_dynamic_obstacles (optimal_planner.cpp:496-497);
-    // AddEdgesDynamicObstacles visits the dynamic ones (:658-659)
-    if (cfg.include_dynamic_obstacles && o.dyn[i]) d.dy.push_back(i); else d.st.push_back(i);
-  }
-  // the obstacles in cache order (static list, then dynamic list): what the kernel stages into LDS, readable with scalar loads
-  d.lo.assign(5 * stride, 0.0);
-  size_t k = 0;
-  d.static_radius_zero = 1;
-  for (int oi : d.st) if (o.type[oi] == TEB_AMD_OBST_CIRCULAR && o.rad[oi] != 0.0) d.static_radius_zero = 0;
-  for (const std::vector<int>* lst : {&d.st, &d.dy})
-    for (int oi : *lst) {
-      d.lo[k] = o.ax[oi]; d.lo[stride + k] = o.ay[oi]; d.lo[2 * stride + k] = o.type[oi] == TEB_AMD_OBST_CIRCULAR ? o.rad[oi] : 0.0;
-      d.lo[3 * stride + k] = o.vx[oi]; d.lo[4 * stride + k] = o.vy[oi];
-      ++k;
-    }
-  d.pointlike_rows = true;
-  for (int i = 0; i < M && d.pointlike_rows; ++i) d.pointlike_rows = (o.type[i] == TEB_AMD_OBST_POINT || o.type[i] == TEB_AMD_OBST_CIRCULAR);
-}
-// The distance path and the layout that goes with it, for an obstacle cache of M entries: point-like fast path iff all obstacles are
-// Point/Circular, the footprint is Point/Circular, and the cache fits the LDS.
-int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, int M, int* solver, int* fast_points, LdsPlan* plan) {
+// The distance path and the layout that goes with it, for an obstacle cache of lay.max_cache entries: point-like fast path iff all
+// obstacles are Point/Circular, the footprint is Point/Circular, and the cache fits the LDS.
+int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, SceneLayout& lay) {
+  const int M = lay.max_cache;
   bool pointlike = pointlike_rows && (h->cfg.footprint_type == TEB_AMD_FOOTPRINT_POINT || h->cfg.footprint_type == TEB_AMD_FOOTPRINT_CIRCULAR);
   if (h->opt.generic_distance_path) pointlike = false;
   // a point-like scene whose obstacle cache does not fit beside the LDS band: the band moves to HBM and the cache stays (measured,
   // 64 bands x 337 poses x 500 obstacles: 9.0 instead of 11.8 ms per step)
-  *solver = h->solver_created;
-  if (pointlike && M > 0 && *solver == SOLVER_BAND && h->opt.layout == TEB_AMD_LAYOUT_AUTO &&
+  lay.solver = h->solver_created;
+  if (pointlike && M > 0 && lay.solver == SOLVER_BAND && h->opt.layout == TEB_AMD_LAYOUT_AUTO &&
       (size_t)make_lds_plan(h->stride, SOLVER_BAND, M, h->lds_limit).total_bytes > h->lds_limit &&
       (size_t)make_lds_plan(h->stride, SOLVER_BANDG, M, h->lds_limit).total_bytes <= h->lds_limit) {
     if (h->hband_stride == 0) {
@@ -951,79 +840,67 @@ int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, int M, int* solv
       h->Hband.free();
       HIPCHK(h->Hband.alloc((size_t)h->max_tebs * h->hband_stride));
     }
-    *solver = SOLVER_BANDG;
+    lay.solver = SOLVER_BANDG;
   }
-  LdsPlan with_cache = make_lds_plan(h->stride, *solver, M, h->lds_limit);
-  if (pointlike && M > 0 && (size_t)with_cache.total_bytes <= h->lds_limit) { *fast_points = 1; *plan = with_cache; }
-  else { *fast_points = 0; *plan = make_lds_plan(h->stride, *solver, 0, h->lds_limit); }
+  LdsPlan with_cache = make_lds_plan(h->stride, lay.solver, M, h->lds_limit);
+  if (pointlike && M > 0 && (size_t)with_cache.total_bytes <= h->lds_limit) { lay.fast_points = 1; lay.plan = with_cache; }
+  else { lay.fast_points = 0; lay.plan = make_lds_plan(h->stride, lay.solver, 0, h->lds_limit); }
   return TEB_AMD_OK;
 }
-// (Re)derives everything that depends on BOTH the obstacle table held in h->hob and the configuration: the lists AddEdgesObstacles /
-// AddEdgesDynamicObstacles visit, the distance path (point-like LDS cache or generic) and the layout that goes with it.
-int commit_obstacles(teb_amd_handle* h) {
-  const auto& o = h->hob;
-  const int M = (int)o.type.size();
-  SceneLists d;
-  derive_scene_lists(h->cfg, o, (size_t)(h->max_obst > 0 ? h->max_obst : 1), d);
-  auto up_i = [&](DevBuf<int>& dst, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(dst.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
-  HIPCHK(up_i(h->o_static, d.st)); HIPCHK(up_i(h->o_dynidx, d.dy));
-  HIPCHK(hipMemcpyAsync(h->o_list.p, d.lo.data(), d.lo.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+// (Re)derives everything that depends on BOTH obstacle tables and the configuration, for the ns tables `tabs` whose rows `store` holds
+// one after the other (scene_segments; ONE table for the single scene of the handle): the lists AddEdgesObstacles /
+// AddEdgesDynamicObstacles visit and the obstacles in cache order, uploaded; the SceneDev of every table - each points at its own
+// segment with indices local to it, so the kernel's arithmetic is the single-scene one - into `scenes` and, for a fleet launch to index,
+// into `scenes_dev`; the distance path (point-like LDS cache, sized for the largest table, or generic) and the layout that goes with it
+// into `lay`; the static list of table 0 into `first_static`. Nothing is touched when the layout cannot be had.
+int commit_tables(teb_amd_handle* h, const HostObst* tabs, const int* via_count, size_t ns, DevSceneStore& store, SceneLayout& lay,
+                  std::vector<SceneDev>& scenes, DevBuf<SceneDev>* scenes_dev, std::vector<int>* first_static) {
+  const std::vector<SceneSegment> seg = scene_segments(tabs, via_count, ns);
+  SceneLists all, d;   // all: the lists of every table at its segment
+  SceneLayout chosen;
+  std::vector<int> st0;
+  bool pointlike = true;
+  scenes.assign(ns, SceneDev{});
+  for (size_t s = 0; s < ns; ++s) {
+    const size_t M = tabs[s].rows();
+    derive_scene_lists(h->cfg, tabs[s], d);
+    all.st.resize(seg[s].row + M, 0); all.dy.resize(seg[s].row + M, 0);
+    std::copy(d.st.begin(), d.st.end(), all.st.begin() + seg[s].row);
+    std::copy(d.dy.begin(), d.dy.end(), all.dy.begin() + seg[s].row);
+    all.lo.insert(all.lo.end(), d.lo.begin(), d.lo.end());   // 5 M values: planes of stride M from seg[s].list on
+    pointlike = pointlike && d.pointlike_rows;
+    chosen.max_cache = std::max(chosen.max_cache, (int)M);
+    scenes[s] = store.view(seg[s], (int)M, via_count[s], (int)d.st.size(), (int)d.dy.size(), d.static_radius_zero, 0);
+    if (s == 0) st0 = d.st;
+  }
+  if (int rc = choose_scene_layout(h, pointlike, chosen)) return rc;
+  for (auto& q : scenes) q.fast_points = chosen.fast_points;   // one distance path for the whole launch
+  HIPCHK(store.upload_lists(h->stream, all));
+  if (scenes_dev) HIPCHK(hipMemcpyAsync(scenes_dev->p, scenes.data(), ns * sizeof(SceneDev), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // host vectors go out of scope
-  h->static_radius_zero = d.static_radius_zero;
-  h->n_static = (int)d.st.size(); h->n_dyn = (int)d.dy.size();
-  h->host_static = d.st;
-  h->hsig_mode = 0;   // signatures depend on the obstacle table and on include_dynamic_obstacles
-  return choose_scene_layout(h, d.pointlike_rows, M, &h->solver, &h->fast_points, &h->plan);
+  lay = chosen;
+  if (first_static) *first_static = std::move(st0);
+  return TEB_AMD_OK;
 }
-
-// Fleet mode: the lists of every scene, the SceneDev array and the layout of a fleet launch, derived from the host tables of the scene
-// set and the configuration. Every SceneDev points at its own segment of the concatenated rows (row offset ro; voff has one entry more
-// per scene, so its segment starts at ro + s), its indices are local to the segment: the kernel's arithmetic is the single-scene one.
+// the single scene: the table held in h->hob
+int commit_obstacles(teb_amd_handle* h) {
+  std::vector<SceneDev> one;
+  if (int rc = commit_tables(h, &h->hob, &h->nvia, 1, h->scene, h->layout, one, nullptr, &h->host_static)) return rc;
+  h->static_radius_zero = one[0].static_radius_zero; h->n_static = one[0].n_static; h->n_dyn = one[0].n_dyn;
+  h->hsig_mode = 0;   // signatures depend on the obstacle table and on include_dynamic_obstacles
+  return TEB_AMD_OK;
+}
+// fleet mode: the tables of the scene set, and the SceneDev array a fleet launch indexes
 int commit_fleet(teb_amd_handle* h) {
   auto& F = h->fleet;
-  const int ns = (int)F.tabs.size();
-  std::vector<int> st_all, dy_all;
-  std::vector<double> lo_all;
-  std::vector<SceneDev> sd(ns);
-  size_t ro = 0, vo = 0, wo = 0;
-  bool pointlike = true;
-  int max_cache = 0;
-  for (int s = 0; s < ns; ++s) {
-    const auto& o = F.tabs[s];
-    const size_t M = o.type.size();
-    SceneLists d;
-    derive_scene_lists(h->cfg, o, M, d);
-    st_all.resize(ro + M, 0); dy_all.resize(ro + M, 0);
-    std::copy(d.st.begin(), d.st.end(), st_all.begin() + ro);
-    std::copy(d.dy.begin(), d.dy.end(), dy_all.begin() + ro);
-    lo_all.insert(lo_all.end(), d.lo.begin(), d.lo.end());   // 5 M values: the segment of scene s starts at 5 ro
-    pointlike = pointlike && d.pointlike_rows;
-    max_cache = std::max(max_cache, (int)M);
-    SceneDev& q = sd[s];
-    q.M = (int)M;
-    q.fast_points = 0;   // set below: one distance path for the whole launch
-    q.static_radius_zero = d.static_radius_zero;
-    q.type = F.type.p + ro; q.ax = F.ax.p + ro; q.ay = F.ay.p + ro; q.bx = F.bx.p + ro; q.by = F.by.p + ro;
-    q.rad = F.rad.p + ro; q.vx = F.vx.p + ro; q.vy = F.vy.p + ro; q.cx = F.cx.p + ro; q.cy = F.cy.p + ro; q.brad = F.brad.p + ro;
-    q.dyn = F.dyn.p + ro; q.voff = F.voff.p + ro + s; q.pvx = F.pvx.p + vo; q.pvy = F.pvy.p + vo;
-    q.n_static = (int)d.st.size(); q.static_idx = F.stat.p + ro; q.n_dyn = (int)d.dy.size(); q.dyn_idx = F.dynidx.p + ro;
-    q.nvia = F.via_count[s]; q.viax = F.viax.p + wo; q.viay = F.viay.p + wo;
-    q.lox = F.list.p + 5 * ro; q.loy = q.lox + M; q.lor = q.lox + 2 * M; q.lovx = q.lox + 3 * M; q.lovy = q.lox + 4 * M;
-    ro += M; vo += o.pvx.size(); wo += (size_t)F.via_count[s];
-  }
-  int solver = 0, fast = 0;
-  LdsPlan plan;
-  if (int rc = choose_scene_layout(h, pointlike, max_cache, &solver, &fast, &plan)) return rc;
-  for (auto& q : sd) q.fast_points = fast;
-  if (ro > 0) {
-    HIPCHK(hipMemcpyAsync(F.stat.p, st_all.data(), ro * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(F.dynidx.p, dy_all.data(), ro * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(F.list.p, lo_all.data(), 5 * ro * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  }
-  HIPCHK(hipMemcpyAsync(F.scenes.p, sd.data(), (size_t)ns * sizeof(SceneDev), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));   // host vectors go out of scope
-  F.solver = solver; F.fast_points = fast; F.plan = plan; F.max_cache = max_cache;
-  return TEB_AMD_OK;
+  std::vector<SceneDev> views;
+  return commit_tables(h, F.tabs.data(), F.via_count.data(), F.tabs.size(), F.store, F.layout, views, &F.scenes, nullptr);
+}
+// both, as far as they hold anything (teb_amd_set_config)
+int commit_all(teb_amd_handle* h) {
+  int rc = h->M > 0 ? commit_obstacles(h) : TEB_AMD_OK;
+  if (!rc && h->fleet.n_scenes > 0) rc = commit_fleet(h);
+  return rc;
 }
 
 // the calls that read or write THE scene of the handle are not available while a scene set is installed (teb_amd.h, fleet batches)
@@ -1044,87 +921,27 @@ int teb_amd_set_config(teb_amd_handle_t* h, const teb_amd_config_t* cfg) {
                              (cfg->footprint_type != h->cfg.footprint_type);
   const teb_amd_config_t previous = h->cfg;
   h->cfg = *cfg;
-  if (lists_changed && h->M > 0) {
-    rc = commit_obstacles(h);   // derives the static / dynamic lists, the distance path and the LDS plan from h->cfg
-    if (rc) {                   // "keeps its previous configuration" (teb_amd.h): put it back together with what is derived from it
-      const std::string why = g_last_error;
-      h->cfg = previous;
-      (void)commit_obstacles(h);
-      return fail(rc, why);
-    }
-  }
-  if (lists_changed && h->fleet.n_scenes > 0) {   // fleet mode: the lists of every scene
-    rc = commit_fleet(h);
-    if (rc) {
-      const std::string why = g_last_error;
-      h->cfg = previous;
-      if (h->M > 0) (void)commit_obstacles(h);
-      (void)commit_fleet(h);
-      return fail(rc, why);
-    }
+  // derives the static / dynamic lists, the distance path and the LDS plan from h->cfg: of the single scene and of every scene of a set
+  if (lists_changed && (rc = commit_all(h))) {   // "keeps its previous configuration" (teb_amd.h): put it back together with what is derived from it
+    const std::string why = g_last_error;
+    h->cfg = previous;
+    (void)commit_all(h);
+    return fail(rc, why);
   }
   return TEB_AMD_OK;
 }
 
 namespace {
-// The host side of an obstacle table (teb_amd_obstacles_t) with the centroids and bounding radii the kernels read; t.voff and the
-// vertices start at 0. Checks the arrays, not the capacities.
-int parse_obstacle_table(const teb_amd_obstacles_t* o, teb_amd_handle::HostObst& t) {
-  const int M = o->count;
-  if (M > 0 && (!o->type || !o->ax || !o->ay)) return fail(TEB_AMD_ERR_INVALID_ARG, "obstacle arrays missing");
-  t.type.resize(M); t.dyn.resize(M); t.voff.assign(M + 1, 0);
-  t.ax.resize(M); t.ay.resize(M); t.bx.resize(M); t.by.resize(M); t.rad.resize(M); t.vx.resize(M); t.vy.resize(M); t.cx.resize(M); t.cy.resize(M); t.brad.assign(M, 0.0);
-  for (int i = 0; i < M; ++i) {
-    t.type[i] = o->type[i];
-    t.ax[i] = o->ax[i]; t.ay[i] = o->ay[i];
-    t.bx[i] = o->bx ? o->bx[i] : 0; t.by[i] = o->by ? o->by[i] : 0;
-    t.rad[i] = o->radius ? o->radius[i] : 0;
-    t.vx[i] = o->vx ? o->vx[i] : 0; t.vy[i] = o->vy ? o->vy[i] : 0;
-    t.dyn[i] = o->dynamic ? (o->dynamic[i] != 0) : 0;
-    t.voff[i] = (int)t.pvx.size();
-    switch (t.type[i]) {
-      case TEB_AMD_OBST_POINT: case TEB_AMD_OBST_CIRCULAR: t.cx[i] = t.ax[i]; t.cy[i] = t.ay[i]; t.brad[i] = std::fabs(t.rad[i]); break;
-      case TEB_AMD_OBST_LINE: case TEB_AMD_OBST_PILL:
-        t.cx[i] = 0.5 * (t.ax[i] + t.bx[i]); t.cy[i] = 0.5 * (t.ay[i] + t.by[i]);
-        t.brad[i] = 0.5 * std::hypot(t.bx[i] - t.ax[i], t.by[i] - t.ay[i]) + std::fabs(t.rad[i]);
-        break;
-      case TEB_AMD_OBST_POLYGON: {
-        if (!o->vert_offset || !o->vert_x || !o->vert_y) return fail(TEB_AMD_ERR_INVALID_ARG, "polygon obstacle without vertex arrays");
-        int k0 = o->vert_offset[i], k1 = o->vert_offset[i + 1];
-        if (k1 <= k0) return fail(TEB_AMD_ERR_INVALID_ARG, "polygon obstacle without vertices");
-        for (int k = k0; k < k1; ++k) { t.pvx.push_back(o->vert_x[k]); t.pvy.push_back(o->vert_y[k]); }
-        polygon_centroid(o->vert_x + k0, o->vert_y + k0, k1 - k0, t.cx[i], t.cy[i]);
-        for (int k = k0; k < k1; ++k) t.brad[i] = std::max(t.brad[i], std::hypot(o->vert_x[k] - t.cx[i], o->vert_y[k] - t.cy[i]));
-        if (!(t.brad[i] == t.brad[i])) t.brad[i] = std::numeric_limits<double>::infinity();   // NaN centroid: never culled
-        break;
-      }
-      default: return fail(TEB_AMD_ERR_INVALID_ARG, "unknown obstacle type");
-    }
-  }
-  t.voff[M] = (int)t.pvx.size();
-  return TEB_AMD_OK;
-}
-
-// Uploads the rows of t to the device table from row `first` on (voff: first .. first + M) and its vertices from 0 on.
-int upload_obstacle_rows(teb_amd_handle* h, const teb_amd_handle::HostObst& t, size_t first) {
-  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p + first, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
-  auto up_d = [&](DevBuf<double>& d, const std::vector<double>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p + first, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream); };
-  HIPCHK(up_i(h->o_type, t.type)); HIPCHK(up_i(h->o_dyn, t.dyn)); HIPCHK(up_i(h->o_voff, t.voff));
-  HIPCHK(up_d(h->o_ax, t.ax)); HIPCHK(up_d(h->o_ay, t.ay)); HIPCHK(up_d(h->o_bx, t.bx)); HIPCHK(up_d(h->o_by, t.by)); HIPCHK(up_d(h->o_rad, t.rad));
-  HIPCHK(up_d(h->o_vx, t.vx)); HIPCHK(up_d(h->o_vy, t.vy)); HIPCHK(up_d(h->o_cx, t.cx)); HIPCHK(up_d(h->o_cy, t.cy)); HIPCHK(up_d(h->o_brad, t.brad));
-  if (!t.pvx.empty()) {
-    HIPCHK(hipMemcpyAsync(h->o_pvx.p, t.pvx.data(), t.pvx.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->o_pvy.p, t.pvy.data(), t.pvy.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  }
+// Uploads the rows of t to the device table of the single scene from row `first` on (voff: first .. first + M) and its vertices from 0 on.
+int upload_obstacle_rows(teb_amd_handle* h, const HostObst& t, size_t first) {
+  HIPCHK(h->scene.upload_rows(h->stream, t, first, first, 0));
   HIPCHK(hipStreamSynchronize(h->stream));   // the uploads read `t`
   return TEB_AMD_OK;
 }
 
-// The device rows hold table t: the host mirrors take it over and everything derived from the table is derived again.
-int install_obstacles(teb_amd_handle* h, teb_amd_handle::HostObst&& t) {
-  h->M = (int)t.type.size();
-  h->host_type = t.type;
-  h->host_cx = t.cx; h->host_cy = t.cy;
+// The device rows hold table t: the host copy takes it over and everything derived from the table is derived again.
+int install_obstacles(teb_amd_handle* h, HostObst&& t) {
+  h->M = (int)t.rows();
   h->hs_prod_valid = false;
   h->hob = std::move(t);
   return commit_obstacles(h);
@@ -1137,9 +954,8 @@ int teb_amd_set_obstacles(teb_amd_handle_t* h, const teb_amd_obstacles_t* o) {
   if ((rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles"))) return rc;
   if (!o || o->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "null obstacle table");
   if (o->count > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
-  teb_amd_handle::HostObst t;
-  rc = parse_obstacle_table(o, t);
-  if (rc) return rc;
+  HostObst t;
+  if (const char* bad = parse_obstacle_table(o, t)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
   if ((int)t.pvx.size() > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
   rc = upload_obstacle_rows(h, t, 0);
   if (rc) return rc;
@@ -1153,8 +969,7 @@ int teb_amd_set_via_points(teb_amd_handle_t* h, int32_t count, const double* x, 
   if (count < 0 || (count > 0 && (!x || !y))) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
   if (count > h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
   if (count > 0) {
-    HIPCHK(hipMemcpyAsync(h->viax.p, x, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->viay.p, y, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h->scene.upload_vias(h->stream, x, y, (size_t)count));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   h->nvia = count;
@@ -1163,18 +978,14 @@ int teb_amd_set_via_points(teb_amd_handle_t* h, int32_t count, const double* x, 
 
 // ---- fleet batches (teb_amd.h): a set of scenes and a band -> scene map ---------------------------------------------------------------
 namespace {
-constexpr size_t kFleetPad = 8;   // elements past every fleet buffer: the segment of an empty scene at the very end still points at storage
+constexpr size_t kFleetPad = 8;   // elements past every buffer of the scene set's store: the segment of an empty scene at the very end still points at storage
 int fleet_allocate(teb_amd_handle* h) {
   auto& F = h->fleet;
   if (F.allocated) return TEB_AMD_OK;
-  const size_t Mo = (size_t)std::max(h->max_obst, 0) + kFleetPad, T = (size_t)h->max_tebs;
-  const size_t Vo = (size_t)std::max(h->max_verts, 0) + kFleetPad, Wo = (size_t)std::max(h->max_via, 0) + kFleetPad;
-  bool ok = true;
+  const size_t T = (size_t)h->max_tebs;
+  // (every scene has one first-vertex offset more than rows, and there are at most T scenes)
+  bool ok = F.store.alloc((size_t)std::max(h->max_obst, 0), T, (size_t)std::max(h->max_verts, 0), (size_t)std::max(h->max_via, 0), kFleetPad);
   auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
-  A(F.type.alloc(Mo)); A(F.dyn.alloc(Mo)); A(F.voff.alloc(Mo + T)); A(F.stat.alloc(Mo)); A(F.dynidx.alloc(Mo));
-  A(F.ax.alloc(Mo)); A(F.ay.alloc(Mo)); A(F.bx.alloc(Mo)); A(F.by.alloc(Mo)); A(F.rad.alloc(Mo)); A(F.vx.alloc(Mo)); A(F.vy.alloc(Mo));
-  A(F.cx.alloc(Mo)); A(F.cy.alloc(Mo)); A(F.brad.alloc(Mo)); A(F.list.alloc(5 * Mo));
-  A(F.pvx.alloc(Vo)); A(F.pvy.alloc(Vo)); A(F.viax.alloc(Wo)); A(F.viay.alloc(Wo));
   A(F.scenes.alloc(T)); A(F.scene_of.alloc(T)); A(F.sel_last.alloc(T)); A(F.sel_init.alloc(T)); A(F.sel_idx.alloc(T)); A(F.sel_cost.alloc(T));
   for (int sv : {SOLVER_BAND, SOLVER_CR, SOLVER_BANDG})
     for (int sk : {SCENE_POINTS, SCENE_GENERIC}) {
@@ -1185,7 +996,7 @@ int fleet_allocate(teb_amd_handle* h) {
   if (ok && hipMemcpy(F.scene_of.p, F.band_scene.data(), T * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) ok = false;
   if (!ok) {
     (void)hipGetLastError();
-    fleet_free(h);
+    F.release();
     return fail(TEB_AMD_ERR_HIP, "teb_amd_set_scenes: device allocation of the fleet storage failed");
   }
   F.allocated = true;
@@ -1200,14 +1011,13 @@ int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obst
   if (n_scenes < 1 || !obstacles) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scenes: needs at least one scene");
   if (n_scenes > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more scenes than max_tebs");
   // everything is parsed and checked before the first upload: on an error the previous scene set stays installed
-  std::vector<teb_amd_handle::HostObst> tabs(n_scenes);
+  std::vector<HostObst> tabs(n_scenes);
   std::vector<int> vc(n_scenes, 0);
   size_t rows = 0, verts = 0, vias = 0;
   for (int s = 0; s < n_scenes; ++s) {
     if (obstacles[s].count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "null obstacle table");
-    rc = parse_obstacle_table(&obstacles[s], tabs[s]);
-    if (rc) return rc;
-    rows += tabs[s].type.size(); verts += tabs[s].pvx.size();
+    if (const char* bad = parse_obstacle_table(&obstacles[s], tabs[s])) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
+    rows += tabs[s].rows(); verts += tabs[s].verts();
     if (via_count) {
       if (via_count[s] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
       vc[s] = via_count[s]; vias += (size_t)via_count[s];
@@ -1221,29 +1031,14 @@ int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obst
   if (rc) return rc;
   auto& F = h->fleet;
   // rows, vertices and via-points of the scenes one after the other (voff: M + 1 entries per scene, local to the scene's vertices)
-  teb_amd_handle::HostObst all;
-  for (int s = 0; s < n_scenes; ++s) {
-    const auto& t = tabs[s];
-    auto cat_i = [](std::vector<int>& d, const std::vector<int>& v) { d.insert(d.end(), v.begin(), v.end()); };
-    auto cat_d = [](std::vector<double>& d, const std::vector<double>& v) { d.insert(d.end(), v.begin(), v.end()); };
-    cat_i(all.type, t.type); cat_i(all.dyn, t.dyn); cat_i(all.voff, t.voff);
-    cat_d(all.ax, t.ax); cat_d(all.ay, t.ay); cat_d(all.bx, t.bx); cat_d(all.by, t.by); cat_d(all.rad, t.rad); cat_d(all.vx, t.vx); cat_d(all.vy, t.vy);
-    cat_d(all.cx, t.cx); cat_d(all.cy, t.cy); cat_d(all.brad, t.brad); cat_d(all.pvx, t.pvx); cat_d(all.pvy, t.pvy);
-  }
-  auto up_i = [&](DevBuf<int>& d, const std::vector<int>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice, h->stream); };
-  auto up_d = [&](DevBuf<double>& d, const std::vector<double>& v) { return v.empty() ? hipSuccess : hipMemcpyAsync(d.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice, h->stream); };
+  HostObst all;
+  for (const HostObst& t : tabs) all.append_segment(t);
   // From here on the rows of the previous set are overwritten in place: whatever fails now is a HIP error, and the handle is then left
   // in single-scene mode (n_scenes = 0) - nothing else consistent is left to return to.
   hipError_t e = hipSuccess;
   auto U = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  U(up_i(F.type, all.type)); U(up_i(F.dyn, all.dyn)); U(up_i(F.voff, all.voff));
-  U(up_d(F.ax, all.ax)); U(up_d(F.ay, all.ay)); U(up_d(F.bx, all.bx)); U(up_d(F.by, all.by)); U(up_d(F.rad, all.rad));
-  U(up_d(F.vx, all.vx)); U(up_d(F.vy, all.vy)); U(up_d(F.cx, all.cx)); U(up_d(F.cy, all.cy)); U(up_d(F.brad, all.brad));
-  U(up_d(F.pvx, all.pvx)); U(up_d(F.pvy, all.pvy));
-  if (vias > 0) {
-    U(hipMemcpyAsync(F.viax.p, via_x, vias * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    U(hipMemcpyAsync(F.viay.p, via_y, vias * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  }
+  U(F.store.upload_rows(h->stream, all, 0, 0, 0));
+  U(F.store.upload_vias(h->stream, via_x, via_y, vias));
   U(hipStreamSynchronize(h->stream));   // the uploads read `all` and the caller's arrays
   if (e != hipSuccess) {
     F.n_scenes = 0; F.tabs.clear(); F.via_count.clear();
@@ -1462,7 +1257,7 @@ int teb_amd_optimize_batch(teb_amd_handle_t* h, int32_t inner, int32_t outer, in
   }
   OptArgs a;
   std::memset(&a, 0, sizeof a);
-  a.inner = inner; a.outer = outer; a.compute_cost = compute_cost; a.no_near_cache = h->opt.no_near_cache != 0; a.band_ldlt = (fleet ? h->fleet.solver : h->solver) == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
+  a.inner = inner; a.outer = outer; a.compute_cost = compute_cost; a.no_near_cache = h->opt.no_near_cache != 0; a.band_ldlt = (fleet ? h->fleet.layout : h->layout).solver == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
   a.obst_scale = obst_cost_scale; a.via_scale = viapoint_cost_scale; a.alt_time = alternative_time_cost;
   if (h->iter_log_on) { a.iter_log = h->iter_log.p; a.iter_log_cap = TEB_AMD_ITERATION_LOG_ROWS; }
   if (h->phase_log_on) a.phase_log = h->phase_log.p;
@@ -2075,10 +1870,9 @@ int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_
   if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: no costmap (teb_amd_set_costmap)");
   if (!robot_pose || capacity < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: null pose / negative capacity");
   if (custom && custom->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
-  teb_amd_handle::HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
+  HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
   teb_amd_obstacles_t none{};
-  rc = parse_obstacle_table(custom ? custom : &none, tc);
-  if (rc) return rc;
+  if (const char* bad = parse_obstacle_table(custom ? custom : &none, tc)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
   if ((int)tc.pvx.size() > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
   const int mc = (int)tc.type.size();
 
@@ -2107,34 +1901,27 @@ int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_
 
   // the cell rows on the device, the custom rows behind them from the host
   if (n > 0) {
-    const CmoRows r{h->o_type.p, h->o_dyn.p, h->o_voff.p, h->o_ax.p, h->o_ay.p, h->o_bx.p, h->o_by.p, h->o_rad.p, h->o_vx.p, h->o_vy.p,
-                    h->o_cx.p, h->o_cy.p, h->o_brad.p};
     const size_t lanes = (size_t)ncols * nchunks;
     hipLaunchKernelGGL(costmap_obstacles_write_kernel, dim3((unsigned)((lanes + kCmoThreads - 1) / kCmoThreads)), dim3(kCmoThreads), 0,
-                       h->stream, g, f, ncols, nrows, chunk, nchunks, h->cmo_cnt.p, r);
+                       h->stream, g, f, ncols, nrows, chunk, nchunks, h->cmo_cnt.p, h->scene.rows());
     HIPCHK(hipGetLastError());
   }
   rc = upload_obstacle_rows(h, tc, (size_t)n);   // (ends in a stream synchronisation)
   if (rc) return rc;
 
-  // host mirror: the n cell centres (one copy back) ++ the custom rows, exactly what teb_amd_set_obstacles would hold
-  teb_amd_handle::HostObst t;
-  t.ax.resize(n); t.ay.resize(n);
+  // host copy: the n cell centres (one copy back) ++ the custom rows, exactly what teb_amd_set_obstacles would hold
+  static_assert(TEB_AMD_OBST_POINT == 0, "zeroed rows are point rows");
+  HostObst t;
+  t.reset_rows(n);   // points, radius 0, velocity 0, not dynamic
   if (n > 0) {
-    HIPCHK(hipMemcpyAsync(t.ax.data(), h->o_ax.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(t.ay.data(), h->o_ay.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(t.ax.data(), h->scene.ax.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(t.ay.data(), h->scene.ay.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
-  t.type.assign(n, TEB_AMD_OBST_POINT); t.dyn.assign(n, 0); t.voff.assign(n, 0);
-  t.bx.assign(n, 0.0); t.by.assign(n, 0.0); t.rad.assign(n, 0.0); t.vx.assign(n, 0.0); t.vy.assign(n, 0.0); t.brad.assign(n, 0.0);
   t.cx = t.ax; t.cy = t.ay;
   if (out_x) std::copy(t.ax.begin(), t.ax.begin() + std::min(capacity, n), out_x);
   if (out_y) std::copy(t.ay.begin(), t.ay.begin() + std::min(capacity, n), out_y);
-  auto app = [](auto& a, const auto& b) { a.insert(a.end(), b.begin(), b.end()); };
-  app(t.type, tc.type); app(t.dyn, tc.dyn); app(t.voff, tc.voff);
-  app(t.ax, tc.ax); app(t.ay, tc.ay); app(t.bx, tc.bx); app(t.by, tc.by); app(t.rad, tc.rad); app(t.vx, tc.vx); app(t.vy, tc.vy);
-  app(t.cx, tc.cx); app(t.cy, tc.cy); app(t.brad, tc.brad);
-  t.pvx = std::move(tc.pvx); t.pvy = std::move(tc.pvy);
+  t.append(tc);
   return install_obstacles(h, std::move(t));
 }
 
@@ -2154,10 +1941,9 @@ int teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const doubl
     return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null pose / negative capacity");
   if (tile_cells < 1 || tile_cells > kCmpMaxTile) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "tile_cells outside 1 .. 64");
   if (custom && custom->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
-  teb_amd_handle::HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
+  HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
   teb_amd_obstacles_t none{};
-  rc = parse_obstacle_table(custom ? custom : &none, tc);
-  if (rc) return rc;
+  if (const char* bad = parse_obstacle_table(custom ? custom : &none, tc)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
   const int mc = (int)tc.type.size();
 
   // count + scan over blocks into scratch; the host reads the three totals back and decides whether the table fits
@@ -2222,16 +2008,9 @@ int teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const doubl
   teb_amd_obstacles_t ct{};
   ct.count = nr; ct.type = type.data(); ct.ax = ax.data(); ct.ay = ay.data(); ct.bx = bx.data(); ct.by = by.data();
   ct.vert_offset = voff.data(); ct.vert_x = pgx.data(); ct.vert_y = pgy.data();
-  teb_amd_handle::HostObst t;
-  rc = parse_obstacle_table(&ct, t);
-  if (rc) return rc;
-  const int shift = (int)t.pvx.size();
-  auto app = [](auto& a, const auto& b) { a.insert(a.end(), b.begin(), b.end()); };
-  t.voff.pop_back();
-  for (int v : tc.voff) t.voff.push_back(v + shift);
-  app(t.type, tc.type); app(t.dyn, tc.dyn);
-  app(t.ax, tc.ax); app(t.ay, tc.ay); app(t.bx, tc.bx); app(t.by, tc.by); app(t.rad, tc.rad); app(t.vx, tc.vx); app(t.vy, tc.vy);
-  app(t.cx, tc.cx); app(t.cy, tc.cy); app(t.brad, tc.brad); app(t.pvx, tc.pvx); app(t.pvy, tc.pvy);
+  HostObst t;
+  if (const char* bad = parse_obstacle_table(&ct, t)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
+  t.append(tc);
   if (out_offset && out_x && out_y && nr <= capacity_obstacles && nv <= capacity_points) {
     std::copy(off.begin(), off.end(), out_offset);
     std::copy(px.begin(), px.end(), out_x);
@@ -2282,7 +2061,6 @@ int teb_amd_compute_h_signatures(teb_amd_handle_t* h, double prescaler, double* 
   if (rc) return rc;
   if ((rc = refuse_in_fleet_mode(h, "teb_amd_compute_h_signatures"))) return rc;
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
-  SceneDev sc = scene_of(h);
   BatchDev bt = batch_of(h);
   const int M = h->M, B = h->B;
   const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;   // homotopy_class_planner.hpp:50
@@ -2573,11 +2351,11 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
     normalize(dfx, dfy);
     double min_dist = std::numeric_limits<double>::max();
     for (int o = 0; o < M; ++o) {
-      const double ox = h->host_cx[o] - sx, oy = h->host_cy[o] - sy;
+      const double ox = h->hob.cx[o] - sx, oy = h->hob.cy[o] - sy;
       const double dist = std::sqrt(ox * ox + oy * oy);
       if ((ox * dfx + oy * dfy) / dist < 0.1) continue;                     // obstacle not in front of the start
-      vx.push_back(h->host_cx[o] + nx); vy.push_back(h->host_cy[o] + ny);
-      vx.push_back(h->host_cx[o] - nx); vy.push_back(h->host_cy[o] - ny);
+      vx.push_back(h->hob.cx[o] + nx); vy.push_back(h->hob.cy[o] + ny);
+      vx.push_back(h->hob.cx[o] - nx); vy.push_back(h->hob.cy[o] - ny);
       if (p->obstacle_heading_threshold && dist < min_dist) { min_dist = dist; ga.near_u = (int)vx.size() - 2; ga.near_v = (int)vx.size() - 1; }
     }
     ga.min_dist = 0.5 * dist_to_obst;
@@ -2919,7 +2697,7 @@ int teb_amd_last_kernel_ms(teb_amd_handle_t* h, float* ms) {
 int teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_poses_supported) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if (lds_bytes) *lds_bytes = (int32_t)h->plan.total_bytes;
+  if (lds_bytes) *lds_bytes = (int32_t)h->layout.plan.total_bytes;
   if (max_poses_supported) {
     hipDeviceProp_t prop;
     HIPCHK(hipGetDeviceProperties(&prop, h->device));
@@ -2940,7 +2718,7 @@ int teb_amd_debug_linearize(teb_amd_handle_t* h, int32_t b, double weight_multip
   // run the kernel in debug mode on TEB b only: temporarily view the batch as starting at b
   OptArgs a;
   std::memset(&a, 0, sizeof a);
-  a.inner = 1; a.outer = 1; a.no_near_cache = h->opt.no_near_cache != 0; a.debug_linearize = 1; a.debug_weight_multiplier = weight_multiplier; a.band_ldlt = h->solver == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
+  a.inner = 1; a.outer = 1; a.no_near_cache = h->opt.no_near_cache != 0; a.debug_linearize = 1; a.debug_weight_multiplier = weight_multiplier; a.band_ldlt = h->layout.solver == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
   a.dbg_H = h->dbg_H.p; a.dbg_b = h->dbg_b.p; a.dbg_chi2 = h->dbg_chi2.p;
   SceneDev sc = scene_of(h);
   BatchDev bt = batch_of(h);
@@ -2959,7 +2737,7 @@ int teb_amd_debug_linearize(teb_amd_handle_t* h, int32_t b, double weight_multip
   HIPCHK(hipMemcpy(&sv_d[0], h->chi2.p + b, sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(&sv_d[1], h->cost.p + b, sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(hipMemcpy(&sv_d[2], h->lambda.p + b, sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(launch_opt(h, 1, sc, bt, a));
+  HIPCHK(launch_opt(h, 1, sc, bt, a, h->layout.solver, h->layout.plan));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(h->status.p + b, &sv_i[0], sizeof(int), hipMemcpyHostToDevice));

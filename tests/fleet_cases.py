@@ -138,15 +138,16 @@ def _sample_points(t):
     return out
 
 
-def mixed_fleet(seed, n_scenes=6, stride=96, bands=(1, 5), poses=(16, 40), clearance=0.3, replaced=None):
-    """clearance: every band starts at least that far from the outline of every obstacle of its scene - the lateral sine is drawn again
+def mixed_fleet(seed, n_scenes=6, stride=96, bands=(1, 5), poses=(16, 40), clearance=0.3, replaced=None, empty=None):
+    """empty: the scene without any obstacle (default: drawn from the seed). clearance: every band starts at least that far from the outline of every obstacle of its scene - the lateral sine is drawn again
     until it does. replaced: {scene: attempt}, see _scene_rng."""
     rng = np.random.default_rng(seed)
     cfg, base, base_via, _ = scenes.scene_small_mixed(seed=seed, footprint="polygon")
     counts = [int(rng.integers(bands[0], bands[1] + 1)) for _ in range(n_scenes)]
     scene_of = _interleave(rng, counts)
     batch = _abi.TebBatchHost(len(scene_of), stride)
-    empty = int(rng.integers(0, n_scenes))   # the scene without any obstacle
+    drawn = int(rng.integers(0, n_scenes))
+    empty = drawn if empty is None else int(empty)   # the scene without any obstacle
     tables, vias = [], []
     for s in range(n_scenes):
         g = _scene_rng(seed, s, replaced)

@@ -103,6 +103,27 @@ def test_fleet_bands_equal_single_scene_handles_bit_for_bit(kind, layout):
     assert (res.status == _abi.TEB_OK).all()
 
 
+@pytest.mark.parametrize("empty", [0, 2])
+def test_empty_scene_first_and_last_equal_single_scene_handles_bit_for_bit(empty):
+    """The scene without obstacles at a pinned place: first (every later segment starts after an empty one) and last (its segment starts
+    where the rows of the scene set end - what the padding of the set's store is for). The other two scenes hold polygons, so the
+    offsets and vertices of a scene are found at its own segment."""
+    f = fleet_cases.mixed_fleet(102, n_scenes=3, stride=LAYOUTS["cr"], empty=empty)
+    assert f.n_scenes == 3 and len(f.tables[empty]) == 0 and f.bands_of(empty)
+    with_polygons = [sc for sc in range(3) if len(f.tables[sc]) > 0 and (np.asarray(f.tables[sc].type) == _abi.OBST_POLYGON).any()]
+    assert len(with_polygons) >= 2, with_polygons
+    out, res, inst = _run_fleet(f, "cr")
+    assert tuple(inst) == (1, 0, 1), inst
+    seen = 0
+    for idx, out1, res1, inst1 in _run_single_scenes(f, "cr"):
+        assert tuple(inst1) == (1, 0, 1), inst1
+        for k, b in enumerate(idx):
+            _assert_bands_equal(out, res, b, out1, res1, k, "empty scene %d" % empty)
+            seen += 1
+    assert seen == f.batch.count
+    assert (res.status == _abi.TEB_OK).all()
+
+
 def _growing_fleet():
     """Bands that start short enough for the optimistic blocks-in-LDS layout of a 400-pose handle (whose own layout is the band in HBM)
     and that autoResize grows past it: 100 poses 0.08 m apart are 0.2 s apart at max_vel_x, dt_ref = 0.1 splits every interval and the

@@ -1,0 +1,23 @@
+"""The host part of csrc/teb_scene_store.hpp - the obstacle table the single scene and the scene set share: HostObst::append, the
+segments of a scene set, derive_scene_lists - checked by the stand-alone program tests/host/scene_table_check.cpp, compiled with the
+address and undefined-behaviour sanitizers and run as a process of its own (no GPU, no HIP)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+CXX = next((c for c in (os.environ.get("CXX"), "g++", "clang++", "c++") if c and shutil.which(c)), None)
+
+
+@pytest.mark.skipif(CXX is None, reason="needs a host C++ compiler")
+def test_scene_table_host_check(tmp_path):
+    exe = os.path.join(str(tmp_path), "scene_table_check")
+    # (the sanitizer runtimes linked statically - clang's default - so that the program does not depend on library load order)
+    static = [] if "clang" in os.path.basename(CXX) else ["-static-libasan", "-static-libubsan"]
+    subprocess.check_call([CXX, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-Wall", "-Werror"] + static
+                          + [os.path.join(HERE, "host", "scene_table_check.cpp"), "-o", exe])
+    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert run.returncode == 0, run.stdout
+    assert "scene table check ok" in run.stdout
