@@ -700,9 +700,36 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  * works on band b without the scene works unchanged (the three initialisers, update_and_prune, velocities, consumers, feasibility,
  * results, upload / download, snapshot / restore, teb_amd_compact_bands). The calls that read or write THE scene of the handle return
  * TEB_AMD_ERR_INVALID_ARG while scenes are set (call teb_amd_clear_scenes first): teb_amd_set_obstacles, both costmap routes,
- * teb_amd_set_via_points, the H-signature / class filter / exploration / detour calls, teb_amd_select_best and the distributed
- * calls (a refused rank still enters the collective and sends the unusable record, as for any other error of one rank),
- * teb_amd_debug_linearize, teb_amd_debug_distance. Product library only (the other build variants refuse the launch).
+ * teb_amd_set_via_points, teb_amd_compute_h_signatures / teb_amd_filter_equivalence_classes / teb_amd_filter_detours (their
+ * per-scene forms below take their place), teb_amd_explore_candidates (exploration per scene does not exist yet),
+ * teb_amd_select_best and the distributed calls (a refused rank still enters the collective and sends the unusable record, as for
+ * any other error of one rank), teb_amd_debug_linearize, teb_amd_debug_distance. Product library only (the other build variants
+ * refuse the launch).
+ *
+ * Equivalence classes per scene - renewAndAnalyzeOldTebs of every robot of the fleet. Valid only while scenes are set; in single-scene
+ * mode the three calls return TEB_AMD_ERR_INVALID_ARG (call teb_amd_set_scenes first).
+ *   teb_amd_compute_h_signatures_per_scene  teb_amd_compute_h_signatures of every band against its OWN scene, in one launch: a
+ *                            band's values are the bits of a single-scene handle that holds only its scene. Values lie band after
+ *                            band; band b holds offset[b + 1] - offset[b] of them: the row count of its scene when
+ *                            cfg.include_dynamic_obstacles (a scene without rows: none), else 2 = (re, im) ((0, 0) for a scene without
+ *                            rows). offset [B + 1] may be NULL. *n_values (may be NULL) always receives the total. values NULL:
+ *                            compute only. Otherwise values is written when capacity_values >= *n_values, and the call returns
+ *                            TEB_AMD_ERR_CAPACITY when not - the signatures are computed and kept for the filter call either way.
+ *                            A band that maps to a scene >= n_scenes: TEB_AMD_ERR_INVALID_ARG, as for teb_amd_optimize_batch.
+ *                            teb_amd_options_t::hsig3d_kernel pins the 3-D kernel as for the single scene.
+ *   teb_amd_filter_equivalence_classes_per_scene  the rule of teb_amd_filter_equivalence_classes over the bands of every scene in
+ *                            band order, scene by scene: best [n_scenes] (NULL = none) holds a band of scene s, visited first, or a
+ *                            negative value; a band of another scene is TEB_AMD_ERR_INVALID_ARG. Every scene remembers its own best
+ *                            class (a planner is a robot is a scene): it is kept across teb_amd_set_scenes calls with the same
+ *                            number of scenes, used only when its kind and width match the scene's signatures, and forgotten by
+ *                            teb_amd_clear_scenes or another number of scenes. keep / valid / reasonable [B], any may be NULL.
+ *                            Without valid signatures: TEB_AMD_ERR_INVALID_ARG (compute first).
+ *   teb_amd_filter_detours_per_scene  the rule of teb_amd_filter_detours scene by scene after ONE statistics launch over all bands;
+ *                            every scene has its own early-out (fewer than two kept bands, best[s] negative or not kept).
+ * The per-scene signatures, their validity and the 2-D products of the set are state of the scene set: teb_amd_set_scenes,
+ * teb_amd_set_band_scenes, teb_amd_clear_scenes, teb_amd_set_config, teb_amd_compact_bands and every call that changes the bands
+ * invalidate them. None of the three touches the single scene's state: after teb_amd_clear_scenes, teb_amd_compute_h_signatures and
+ * teb_amd_filter_equivalence_classes give what they gave before teb_amd_set_scenes, remembered best class included.
  */
 int  teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obstacles_t* obstacles /* [n_scenes] */,
                         const int32_t* via_count /* [n_scenes] or NULL */, const double* via_x, const double* via_y /* concatenated */);
@@ -711,6 +738,14 @@ int  teb_amd_clear_scenes(teb_amd_handle_t* h);
 int  teb_amd_get_scene_count(teb_amd_handle_t* h, int32_t* n_scenes);
 int  teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best, const int32_t* initial_plan,
                                    int32_t* best /* [n_scenes] */, double* best_cost);
+int  teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler, double* values, int64_t capacity_values,
+                                            int32_t* offset /* [B + 1] or NULL */, int64_t* n_values);
+int  teb_amd_filter_equivalence_classes_per_scene(teb_amd_handle_t* h, double threshold,
+                                                  const int32_t* best /* [n_scenes] band index or -1; NULL = none */,
+                                                  int32_t max_number_plans_in_current_class, int32_t* keep, int32_t* valid,
+                                                  int32_t* reasonable /* [B], any may be NULL */);
+int  teb_amd_filter_detours_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const int32_t* best /* [n_scenes] */,
+                                      int32_t* keep /* [B] in/out */);
 
 #ifdef __cplusplus
 }

@@ -223,12 +223,26 @@ struct teb_amd_handle {
     DevBuf<int> scene_of, sel_last, sel_init, sel_idx;
     DevBuf<double> sel_cost;
     DevBuf<SceneDev> scenes;
+    // equivalence classes per scene (teb_amd_compute_h_signatures_per_scene): state of the scene set, beside the single scene's
+    // (hsig_host, hs_pre .. above), which the per-scene calls never touch
+    DevBuf<double> hs_pre, hs_pim;   // 2-D: prod_l of every row of the set's store, each over the rows of its own scene
+    DevBuf<int> hs_pex, hs_off;      // hs_off [max_tebs + 1]: first value of every band in the signature buffer
+    bool hs_prod_valid = false;
+    int hsig_mode = 0, hsig_B = 0;   // 0 = no valid signatures; 2 / 3 as hsig_mode of the handle
+    std::vector<int> hsig_off;       // [hsig_B + 1]
+    std::vector<double> hsig_host;   // band after band
+    std::vector<std::vector<double>> best_class;   // [n_scenes] best_teb_eq_class_ of every scene's planner
+    std::vector<int> best_class_mode;
+    void forget_best_classes(size_t ns) { best_class.assign(ns, {}); best_class_mode.assign(ns, 0); }
     void release() {   // the device side
       store.free();
-      free_all(scene_of, sel_last, sel_init, sel_idx, sel_cost, scenes);
+      free_all(scene_of, sel_last, sel_init, sel_idx, sel_cost, scenes, hs_pre, hs_pim, hs_pex, hs_off);
       allocated = false;
     }
   } fleet;
+  // the bands, the obstacles or the configuration change: the signatures of an earlier compute call are stale, the single scene's and
+  // the scene set's alike
+  void signatures_stale() { hsig_mode = 0; fleet.hsig_mode = 0; }
 };
 
 namespace {
@@ -623,7 +637,7 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
     h->nmax_known = -1;   // asynchronous launch: autoResize may change the pose counts
   }
   h->consumers_valid = false;
-  h->hsig_mode = 0;   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
   HIPCHK(hipGetLastError());
   HIPCHK(hipEventRecord(h->ev1, h->stream));
   h->timed = true;
@@ -887,13 +901,14 @@ int commit_obstacles(teb_amd_handle* h) {
   std::vector<SceneDev> one;
   if (int rc = commit_tables(h, &h->hob, &h->nvia, 1, h->scene, h->layout, one, nullptr, &h->host_static)) return rc;
   h->static_radius_zero = one[0].static_radius_zero; h->n_static = one[0].n_static; h->n_dyn = one[0].n_dyn;
-  h->hsig_mode = 0;   // signatures depend on the obstacle table and on include_dynamic_obstacles
+  h->signatures_stale();   // signatures depend on the obstacle table and on include_dynamic_obstacles
   return TEB_AMD_OK;
 }
 // fleet mode: the tables of the scene set, and the SceneDev array a fleet launch indexes
 int commit_fleet(teb_amd_handle* h) {
   auto& F = h->fleet;
   std::vector<SceneDev> views;
+  F.hsig_mode = 0; F.hs_prod_valid = false;   // signatures depend on the tables of the set and on include_dynamic_obstacles
   return commit_tables(h, F.tabs.data(), F.via_count.data(), F.tabs.size(), F.store, F.layout, views, &F.scenes, nullptr);
 }
 // both, as far as they hold anything (teb_amd_set_config)
@@ -987,6 +1002,8 @@ int fleet_allocate(teb_amd_handle* h) {
   bool ok = F.store.alloc((size_t)std::max(h->max_obst, 0), T, (size_t)std::max(h->max_verts, 0), (size_t)std::max(h->max_via, 0), kFleetPad);
   auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
   A(F.scenes.alloc(T)); A(F.scene_of.alloc(T)); A(F.sel_last.alloc(T)); A(F.sel_init.alloc(T)); A(F.sel_idx.alloc(T)); A(F.sel_cost.alloc(T));
+  const size_t rows = (size_t)std::max(h->max_obst, 0) + kFleetPad;   // one product per row of the set's store
+  A(F.hs_pre.alloc(rows)); A(F.hs_pim.alloc(rows)); A(F.hs_pex.alloc(rows)); A(F.hs_off.alloc(T + 1));
   for (int sv : {SOLVER_BAND, SOLVER_CR, SOLVER_BANDG})
     for (int sk : {SCENE_POINTS, SCENE_GENERIC}) {
       const void* k = fleet_kernel(sv, sk);
@@ -1041,14 +1058,15 @@ int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obst
   U(F.store.upload_vias(h->stream, via_x, via_y, vias));
   U(hipStreamSynchronize(h->stream));   // the uploads read `all` and the caller's arrays
   if (e != hipSuccess) {
-    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear();
+    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0);
     return fail(TEB_AMD_ERR_HIP, std::string("teb_amd_set_scenes: upload of the scene set -> ") + hipGetErrorString(e));
   }
   F.tabs = std::move(tabs);
   F.via_count = std::move(vc);
   rc = commit_fleet(h);
-  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); return rc; }
+  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0); return rc; }
   F.n_scenes = n_scenes;
+  if (F.best_class.size() != (size_t)n_scenes) F.forget_best_classes(n_scenes);   // a remembered class belongs to a robot: kept while the fleet keeps its size
   return TEB_AMD_OK;
 }
 
@@ -1061,6 +1079,7 @@ int teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_
     if (scene_of[b] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_band_scenes: negative scene index");
   auto& F = h->fleet;
   F.band_scene.assign((size_t)h->max_tebs, 0);   // bands >= count: scene 0
+  F.hsig_mode = 0;   // per-scene signatures were computed against the previous map
   std::copy(scene_of, scene_of + count, F.band_scene.begin());
   if (F.allocated) {
     HIPCHK(hipMemcpyAsync(F.scene_of.p, F.band_scene.data(), F.band_scene.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1074,6 +1093,8 @@ int teb_amd_clear_scenes(teb_amd_handle_t* h) {
   if (rc) return rc;
   h->fleet.n_scenes = 0;   // the single-scene table, its lists and its layout are as they were
   h->fleet.tabs.clear(); h->fleet.via_count.clear();
+  h->fleet.hsig_mode = 0; h->fleet.hs_prod_valid = false;
+  h->fleet.forget_best_classes(0);
   return TEB_AMD_OK;
 }
 
@@ -1156,7 +1177,7 @@ int teb_amd_upload_tebs(teb_amd_handle_t* h, const teb_amd_teb_batch_t* bt) {
     HIPCHK(hipStreamSynchronize(h->stream));   // (the pinned buffer is reused by the next call)
     h->B = B;
     h->consumers_valid = false; h->nmax_known = nmax;
-    h->hsig_mode = 0;
+    h->signatures_stale();
     return TEB_AMD_OK;
   }
   const size_t w = (size_t)(bt->stride < h->stride ? bt->stride : h->stride) * sizeof(double);
@@ -1188,7 +1209,7 @@ int teb_amd_upload_tebs(teb_amd_handle_t* h, const teb_amd_teb_batch_t* bt) {
   HIPCHK(hipStreamSynchronize(h->stream));
   h->B = B;
   h->consumers_valid = false; h->nmax_known = nmax;
-  h->hsig_mode = 0;   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
   return TEB_AMD_OK;
 }
 
@@ -1593,7 +1614,7 @@ int finish_init(teb_amd_handle* h) {
   HIPCHK(hipMemcpyAsync(&err, h->err_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   h->consumers_valid = false; h->nmax_known = -1;
-  h->hsig_mode = 0;   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
   if (err) return fail(TEB_AMD_ERR_CAPACITY, "initTrajectoryToGoal: the band needs more poses than max_poses");
   return TEB_AMD_OK;
 }
@@ -1679,7 +1700,7 @@ int teb_amd_update_and_prune(teb_amd_handle_t* h, int32_t b, const double* new_s
                      batch_of(h), b < 0 ? 0 : b, new_start ? 1 : 0, s[0], s[1], s[2], new_goal ? 1 : 0, g[0], g[1], g[2], min_samples);
   HIPCHK(hipGetLastError());
   h->consumers_valid = false; h->nmax_known = -1;
-  h->hsig_mode = 0;   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
   return TEB_AMD_OK;
 }
 
@@ -2076,20 +2097,17 @@ int teb_amd_compute_h_signatures(teb_amd_handle_t* h, double prescaler, double* 
   return TEB_AMD_OK;
 }
 
-int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, int32_t best, int32_t max_number_plans_in_current_class,
-                                       int32_t* keep, int32_t* valid, int32_t* reasonable) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_equivalence_classes"))) return rc;
-  if (h->hsig_mode == 0 || h->hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures first");
-  const int B = h->hsig_B, mode = h->hsig_mode, W = mode == 3 ? h->hsig_M : 2;
-  const double* sig = h->hsig_host.data();
-  auto row = [&](int b) { return sig + (size_t)b * W; };
-  auto is_valid = [&](int b) { for (int k = 0; k < W; ++k) if (!std::isfinite(row(b)[k])) return false; return true; };
-  auto is_reasonable = [&](int b) { if (mode == 2) return true; for (int k = 0; k < W; ++k) if (row(b)[k] > 1.0) return false; return true; };
+namespace {
+// The class list of renewAndAnalyzeOldTebs over the bands `order` (band indices, in band order) of ONE planner: the single scene's
+// bands, or the bands of one scene of a set. row[b]: the W values of band b (mode 2 / 3). best: a band of `order` that is visited first
+// (std::iter_swap with the first band) and whose class becomes the remembered best class, or anything else for none. best_class /
+// best_class_mode: best_teb_eq_class_ of that planner. kp / vld / rsn [band index] are written for the bands of `order` only.
+void filter_class_list(int mode, int W, double threshold, int max_number_plans_in_current_class, std::vector<int> order, int best,
+                       const std::vector<const double*>& row, std::vector<double>& best_class, int& best_class_mode, int* kp, int* vld, int* rsn) {
+  auto is_valid = [&](int b) { for (int k = 0; k < W; ++k) if (!std::isfinite(row[b][k])) return false; return true; };
+  auto is_reasonable = [&](int b) { if (mode == 2) return true; for (int k = 0; k < W; ++k) if (row[b][k] > 1.0) return false; return true; };
   auto sign_of = [](double z) { return z == 0 ? 0 : (z < 0 ? -1 : 1); };
-  auto is_equal = [&](int a, int b) {   // cls[a]->isEqual(*cls[b])
-    const double* x = row(a); const double* y = row(b);
+  auto equal_rows = [&](const double* x, const double* y) {   // x->isEqual(y)
     if (mode == 2) return std::fabs(y[0] - x[0]) <= threshold && std::fabs(y[1] - x[1]) <= threshold;   // h_signature.h:196-204
     for (int i = 0; i < W; ++i) {                                                                          // h_signature.h:360-377
       if (std::fabs(y[i]) < threshold || std::fabs(x[i]) < threshold) continue;   // far-away obstacle: ignored
@@ -2097,27 +2115,18 @@ int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, in
     }
     return true;
   };
-  std::vector<int> order(B), vld(B), classes;
-  for (int b = 0; b < B; ++b) { order[b] = b; vld[b] = is_valid(b); }
-  const bool has_best = best >= 0 && best < B;
-  if (has_best) {   // best_teb_eq_class_ = calculateEquivalenceClass(best_teb_), src/homotopy_class_planner.cpp:224-227
-    std::swap(order[0], order[best]);
-    h->best_class.assign(row(best), row(best) + W); h->best_class_mode = mode;
+  auto is_equal = [&](int a, int b) { return equal_rows(row[a], row[b]); };   // cls[a]->isEqual(*cls[b])
+  std::vector<int> classes;
+  for (int b : order) { vld[b] = is_valid(b); kp[b] = 0; rsn[b] = is_reasonable(b); }
+  const auto at = std::find(order.begin(), order.end(), best);
+  if (at != order.end()) {   // best_teb_eq_class_ = calculateEquivalenceClass(best_teb_), src/homotopy_class_planner.cpp:224-227
+    std::iter_swap(order.begin(), at);
+    best_class.assign(row[best], row[best] + W); best_class_mode = mode;
   }
   // isInBestTebClass / numTebsInBestTebClass use best_teb_eq_class_, which outlives the band it was computed from (:385-410)
-  const bool have_best_class = h->best_class_mode == mode && (int)h->best_class.size() == W;
-  auto equal_to_best = [&](int b) {   // best_teb_eq_class_->isEqual(*cls[b])
-    const double* x = h->best_class.data(); const double* y = row(b);
-    if (mode == 2) return std::fabs(y[0] - x[0]) <= threshold && std::fabs(y[1] - x[1]) <= threshold;
-    for (int i = 0; i < W; ++i) {
-      if (std::fabs(y[i]) < threshold || std::fabs(x[i]) < threshold) continue;
-      if (sign_of(y[i]) != sign_of(x[i])) return false;
-    }
-    return true;
-  };
-  std::vector<int> kp(B, 0);
-  for (int k = 0; k < B; ++k) {
-    const int b = order[k];
+  const bool have_best_class = best_class_mode == mode && (int)best_class.size() == W;
+  auto equal_to_best = [&](int b) { return equal_rows(best_class.data(), row[b]); };   // best_teb_eq_class_->isEqual(*cls[b])
+  for (int b : order) {
     if (!vld[b]) continue;                                   // "Ignoring invalid H-signature"
     bool has = false;
     for (int c : classes) if (is_equal(b, c)) { has = true; break; }
@@ -2129,10 +2138,144 @@ int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, in
     }
     classes.push_back(b); kp[b] = 1;
   }
+}
+}  // namespace
+
+int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, int32_t best, int32_t max_number_plans_in_current_class,
+                                       int32_t* keep, int32_t* valid, int32_t* reasonable) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_equivalence_classes"))) return rc;
+  if (h->hsig_mode == 0 || h->hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures first");
+  const int B = h->hsig_B, mode = h->hsig_mode, W = mode == 3 ? h->hsig_M : 2;
+  std::vector<int> order(B), kp(B, 0), vld(B, 0), rsn(B, 0);
+  std::vector<const double*> row(B);
+  for (int b = 0; b < B; ++b) { order[b] = b; row[b] = h->hsig_host.data() + (size_t)b * W; }
+  filter_class_list(mode, W, threshold, max_number_plans_in_current_class, std::move(order), best, row, h->best_class, h->best_class_mode,
+                    kp.data(), vld.data(), rsn.data());
   for (int b = 0; b < B; ++b) {
     if (keep) keep[b] = kp[b];
     if (valid) valid[b] = vld[b];
-    if (reasonable) reasonable[b] = is_reasonable(b);
+    if (reasonable) reasonable[b] = rsn[b];
+  }
+  return TEB_AMD_OK;
+}
+
+// ---- equivalence classes per scene of a fleet batch (teb_amd.h, fleet batches; kernels: the fleet forms of teb_hsig.hpp) ----------
+namespace {
+int require_fleet_mode(const teb_amd_handle* h, const char* call) {
+  if (h->fleet.n_scenes <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(call) + ": no scenes set (teb_amd_set_scenes)");
+  return TEB_AMD_OK;
+}
+// every band < B maps to a scene of the set (the check of teb_amd_optimize_batch)
+int check_band_scenes(const teb_amd_handle* h, int B) {
+  for (int b = 0; b < B; ++b)
+    if (h->fleet.band_scene[b] >= h->fleet.n_scenes) {
+      char buf[160];
+      std::snprintf(buf, sizeof buf, "band %d maps to scene %d, but %d scenes are set (teb_amd_set_band_scenes)", b, h->fleet.band_scene[b], h->fleet.n_scenes);
+      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+    }
+  return TEB_AMD_OK;
+}
+// the bands of every scene, in band order
+void bands_per_scene(const teb_amd_handle* h, int B, std::vector<std::vector<int>>& of) {
+  of.assign(h->fleet.n_scenes, {});
+  for (int b = 0; b < B; ++b) of[h->fleet.band_scene[b]].push_back(b);
+}
+// best[s] is a band of scene s or negative (best NULL: none)
+int check_best_per_scene(const teb_amd_handle* h, const int32_t* best, int B, const char* call) {
+  if (!best) return TEB_AMD_OK;
+  for (int s = 0; s < h->fleet.n_scenes; ++s)
+    if (best[s] >= 0 && (best[s] >= B || h->fleet.band_scene[best[s]] != s)) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "%s: best[%d] = %d is not a band of scene %d", call, s, best[s], s);
+      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+    }
+  return TEB_AMD_OK;
+}
+}  // namespace
+
+int teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler, double* values, int64_t capacity_values, int32_t* offset,
+                                           int64_t* n_values) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_values) *n_values = 0;
+  if ((rc = require_fleet_mode(h, "teb_amd_compute_h_signatures_per_scene"))) return rc;
+  if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
+  auto& F = h->fleet;
+  const int B = h->B;
+  if ((rc = check_band_scenes(h, B))) return rc;
+  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;   // homotopy_class_planner.hpp:50
+  int widest = 0;
+  for (const HostObst& t : F.tabs) widest = std::max(widest, (int)t.rows());
+  std::vector<int> off(B + 1, 0);
+  for (int b = 0; b < B; ++b) off[b + 1] = off[b] + (mode == 3 ? (int)F.tabs[F.band_scene[b]].rows() : 2);
+  const size_t total = (size_t)off[B];
+  if (n_values) *n_values = (int64_t)total;
+  if (offset) std::copy(off.begin(), off.end(), offset);
+  F.hsig_mode = 0;
+  BatchDev bt = batch_of(h);
+  FleetHsigDev fl;
+  fl.scenes = F.scenes.p; fl.scene_of = F.scene_of.p; fl.off = F.hs_off.p;
+  double* out = h->hsig.p;   // [max_tebs * max(max_obstacles, 2)]: scratch of the launch (the single scene's signatures live in hsig_host)
+  if (mode == 3) {
+    if (total > 0) {
+      HIPCHK(hipMemcpyAsync(F.hs_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      // the rule of the single-scene launch on the total number of values; teb_amd_options_t::hsig3d_kernel pins one of the two
+      const bool wide = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE || (h->opt.hsig3d_kernel != TEB_AMD_HSIG3D_SMALL && (long long)total >= 32768);
+      if (wide)
+        hipLaunchKernelGGL(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
+                           h->stream, fl, bt, out);
+      else
+        hipLaunchKernelGGL(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
+                           h->stream, fl, bt, out);
+      HIPCHK(hipGetLastError());
+    }
+  } else {
+    if (widest > 0 && !F.hs_prod_valid) {   // the band-independent factor of A_l: once per scene set, every scene over its own rows
+      hipLaunchKernelGGL(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, F.n_scenes), dim3(kThreads), 0, h->stream, F.scenes.p,
+                         F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p);
+      HIPCHK(hipGetLastError());
+      F.hs_prod_valid = true;
+    }
+    hipLaunchKernelGGL(hsig2d_fleet_kernel, dim3(B), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, bt, prescaler,
+                       F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p, out);
+    HIPCHK(hipGetLastError());
+  }
+  F.hsig_host.assign(std::max<size_t>(total, 1), 0.0);
+  if (total > 0) HIPCHK(hipMemcpyAsync(F.hsig_host.data(), out, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // (off is read until here)
+  F.hsig_off = std::move(off);
+  F.hsig_mode = mode; F.hsig_B = B;
+  if (!values) return TEB_AMD_OK;   // compute only: the signatures stay in the handle for the filter call
+  if (capacity_values < (int64_t)total) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_compute_h_signatures_per_scene: capacity_values is smaller than *n_values (the signatures are kept for the filter call)");
+  if (total > 0) std::memcpy(values, F.hsig_host.data(), total * sizeof(double));
+  return TEB_AMD_OK;
+}
+
+int teb_amd_filter_equivalence_classes_per_scene(teb_amd_handle_t* h, double threshold, const int32_t* best,
+                                                 int32_t max_number_plans_in_current_class, int32_t* keep, int32_t* valid, int32_t* reasonable) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_filter_equivalence_classes_per_scene"))) return rc;
+  auto& F = h->fleet;
+  if (F.hsig_mode == 0 || F.hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures_per_scene first");
+  const int B = F.hsig_B, mode = F.hsig_mode;
+  if ((rc = check_best_per_scene(h, best, B, "teb_amd_filter_equivalence_classes_per_scene"))) return rc;
+  std::vector<int> kp(B, 0), vld(B, 0), rsn(B, 0);
+  std::vector<const double*> row(B);
+  for (int b = 0; b < B; ++b) row[b] = F.hsig_host.data() + F.hsig_off[b];
+  std::vector<std::vector<int>> of;
+  bands_per_scene(h, B, of);
+  for (int s = 0; s < F.n_scenes; ++s) {
+    const int W = mode == 3 ? (int)F.tabs[s].rows() : 2;
+    filter_class_list(mode, W, threshold, max_number_plans_in_current_class, of[s], best ? best[s] : -1, row, F.best_class[s], F.best_class_mode[s],
+                      kp.data(), vld.data(), rsn.data());
+  }
+  for (int b = 0; b < B; ++b) {
+    if (keep) keep[b] = kp[b];
+    if (valid) valid[b] = vld[b];
+    if (reasonable) reasonable[b] = rsn[b];
   }
   return TEB_AMD_OK;
 }
@@ -2274,7 +2417,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
     if (best >= 0 && best < h->B) { h->best_class = ct.classes[best]; h->best_class_mode = mode; }
   }
   if (h->best_class_mode == mode && (int)h->best_class.size() == W) { ct.has_best = true; ct.best = h->best_class; }   // best_teb_eq_class_
-  h->hsig_mode = 0;   // the batch is about to change: signatures have to be recomputed before the next filter call
+  h->signatures_stale();   // the batch is about to change: signatures have to be recomputed before the next filter call
   const int n_old = h->B;
   // tebs_.push_back(candidate) for the accepted candidates of a chunk: scratch bands -> the next slots of the batch, one gather;
   // default attributes of a new TebOptimalPlanner (fixed zero start / goal velocity), then setVelocityStart / setVelocityGoalFree
@@ -2542,8 +2685,9 @@ int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best
     h->hsig_host.swap(moved);
     h->hsig_B = K;
   } else {
-    h->hsig_mode = 0;
+    h->signatures_stale();
   }
+  h->fleet.hsig_mode = 0;   // the per-scene signatures are computed again after a compaction (band offsets and the map move)
   if (!h->fleet.band_scene.empty()) {   // the band -> scene map (teb_amd_set_band_scenes) travels with the bands; the freed slots: scene 0
     auto& F = h->fleet;
     std::vector<int> moved(F.band_scene.size(), 0);
@@ -2561,31 +2705,23 @@ int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best
   return TEB_AMD_OK;
 }
 
-int teb_amd_filter_detours(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, int32_t best, int32_t* keep) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_detours"))) return rc;
-  if (!p || !keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
-  const int B = h->B;
-  if (B <= 0) return TEB_AMD_OK;
+namespace {
+// deletePlansDetouringBackwards over the bands `order` of ONE planner (src/homotopy_class_planner.cpp:760-820), in two halves: whether
+// the rule runs at all - it needs two kept bands and a kept best one - and the rule over the statistics of detour_stats_kernel
+// (st [4 * band]) and the optimized flags (opt [band]).
+bool detour_rule_runs(const std::vector<int>& order, int best, const int32_t* keep) {
   int kept = 0;
-  for (int b = 0; b < B; ++b) kept += keep[b] != 0;
-  if (kept < 2 || best < 0 || best >= B || !keep[best]) return TEB_AMD_OK;   // "a moving direction wasn't chosen yet", :769-773
-  if ((rc = ensure_candidate_buffers(h))) return rc;
-  hipLaunchKernelGGL(detour_stats_kernel, dim3(B), dim3(kThreads), 0, h->stream, batch_of(h), p->length_start_orientation_vector, h->cand_sig.p);
-  HIPCHK(hipGetLastError());
-  std::vector<double> st((size_t)4 * B);
-  std::vector<int> opt(B);
-  HIPCHK(hipMemcpyAsync(st.data(), h->cand_sig.p, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(opt.data(), h->optimized.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int b : order) kept += keep[b] != 0;
+  return kept >= 2 && std::find(order.begin(), order.end(), best) != order.end() && keep[best];   // "a moving direction wasn't chosen yet", :769-773
+}
+void apply_detour_rule(const std::vector<int>& order, int best, const teb_amd_hcp_params_t* p, const double* st, const int* opt, int32_t* keep) {
   auto found = [&](int b) { return st[4 * b] != 0; };
   auto orient = [&](int b) { return st[4 * b + 1]; };
   auto duration = [&](int b) { return st[4 * b + 2]; };
   auto poses = [&](int b) { return (int)st[4 * b + 3]; };
-  if (poses(best) < 2) return TEB_AMD_OK;
+  if (poses(best) < 2) return;
   const double best_plan_duration = std::max(duration(best), 1.0);
-  if (!found(best)) return TEB_AMD_OK;   // the plan is shorter than len_orientation_vector
+  if (!found(best)) return;   // the plan is shorter than len_orientation_vector
   auto normalize_theta = [](double theta) {   // g2o::normalize_theta (misc.h)
     if (theta >= -M_PI && theta < M_PI) return theta;
     const double multiplier = std::floor(theta / (2 * M_PI));
@@ -2594,13 +2730,64 @@ int teb_amd_filter_detours(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, i
     if (theta < -M_PI) theta += 2 * M_PI;
     return theta;
   };
-  for (int b = 0; b < B; ++b) {
+  for (int b : order) {
     if (!keep[b] || b == best) continue;
     if (poses(b) < 2 || !found(b)) { keep[b] = 0; continue; }
     if (std::fabs(normalize_theta(orient(b) - orient(best))) > p->detours_orientation_tolerance) { keep[b] = 0; continue; }
     if (!opt[b]) { keep[b] = 0; continue; }
     if (duration(b) / best_plan_duration > p->max_ratio_detours_duration_best_duration) { keep[b] = 0; continue; }
   }
+}
+// detour_stats_kernel over all B bands: st [4 * B], opt [B]
+int detour_statistics(teb_amd_handle* h, const teb_amd_hcp_params_t* p, int B, std::vector<double>& st, std::vector<int>& opt) {
+  if (int rc = ensure_candidate_buffers(h)) return rc;
+  hipLaunchKernelGGL(detour_stats_kernel, dim3(B), dim3(kThreads), 0, h->stream, batch_of(h), p->length_start_orientation_vector, h->cand_sig.p);
+  HIPCHK(hipGetLastError());
+  st.assign((size_t)4 * B, 0.0);
+  opt.assign(B, 0);
+  HIPCHK(hipMemcpyAsync(st.data(), h->cand_sig.p, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(opt.data(), h->optimized.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return TEB_AMD_OK;
+}
+}  // namespace
+
+int teb_amd_filter_detours(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, int32_t best, int32_t* keep) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_detours"))) return rc;
+  if (!p || !keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
+  const int B = h->B;
+  if (B <= 0) return TEB_AMD_OK;
+  std::vector<int> order(B);
+  for (int b = 0; b < B; ++b) order[b] = b;
+  if (!detour_rule_runs(order, best, keep)) return TEB_AMD_OK;
+  std::vector<double> st;
+  std::vector<int> opt;
+  if ((rc = detour_statistics(h, p, B, st, opt))) return rc;
+  apply_detour_rule(order, best, p, st.data(), opt.data(), keep);
+  return TEB_AMD_OK;
+}
+
+int teb_amd_filter_detours_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const int32_t* best, int32_t* keep) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_filter_detours_per_scene"))) return rc;
+  if (!p || !keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
+  const int B = h->B;
+  if (B <= 0) return TEB_AMD_OK;
+  if ((rc = check_band_scenes(h, B))) return rc;
+  if ((rc = check_best_per_scene(h, best, B, "teb_amd_filter_detours_per_scene"))) return rc;
+  std::vector<std::vector<int>> of;
+  bands_per_scene(h, B, of);
+  std::vector<int> runs;   // the scenes past their own early-out
+  for (int s = 0; s < h->fleet.n_scenes; ++s)
+    if (best && detour_rule_runs(of[s], best[s], keep)) runs.push_back(s);
+  if (runs.empty()) return TEB_AMD_OK;
+  std::vector<double> st;
+  std::vector<int> opt;
+  if ((rc = detour_statistics(h, p, B, st, opt))) return rc;   // one launch over all bands
+  for (int s : runs) apply_detour_rule(of[s], best[s], p, st.data(), opt.data(), keep);
   return TEB_AMD_OK;
 }
 
@@ -2644,7 +2831,7 @@ int teb_amd_device_state(teb_amd_handle_t* h, void** x, void** y, void** theta, 
   if (stride) *stride = h->stride;
   h->nmax_known = -1;        // the caller may write pose counts through `n`: the host's upper bound is void from here on (the kernel guards
   h->consumers_valid = false;   // itself against counts beyond its LDS strips as well)
-  h->hsig_mode = 0;
+  h->signatures_stale();
   return TEB_AMD_OK;
 }
 
@@ -2664,7 +2851,7 @@ int teb_amd_restore_state(teb_amd_handle_t* h) {
   // snap_nmax bounded the first snap_B bands only; the copy brings back the counts of ALL max_tebs slots, so with another batch size the
   // bound says nothing about the bands beyond the old B
   h->consumers_valid = false; h->nmax_known = (h->B == h->snap_B) ? h->snap_nmax : -1;
-  h->hsig_mode = 0;   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
   return TEB_AMD_OK;
 }
 

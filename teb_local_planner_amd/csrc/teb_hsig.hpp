@@ -6,6 +6,7 @@
 // CPU: O(n * M * 10) fp64 operations per candidate in 3-D. Here: one launch over the device-resident strips of the whole batch.
 #pragma once
 #include "teb_strip.hpp"
+#include "teb_fleet.hpp"
 
 namespace tebamd {
 
@@ -17,9 +18,10 @@ __device__ __forceinline__ double sqn3(const double* a) { return ((0.0 + a[0] * 
 // 3-D: one lane per (band, obstacle); the lane walks the band's segments and the 10 integration steps per segment in the
 // reference's order with the reference's operations (only + - * / sqrt: IEEE-exact, so the result is bit-equal to the CPU's).
 // grid = (ceil(M / kThreads), B). Dynamic LDS: 3 * stride doubles (x, y, transition time of every pose; read as broadcasts).
-__global__ void __launch_bounds__(kThreads) hsig3d_kernel(const SceneDev sc, const BatchDev bt, double* __restrict__ out) {
+// The body is shared with the fleet form (hsig3d_fleet_kernel): band b against scene sc, its values to out[0 .. M).
+__device__ __forceinline__ void hsig3d_body(const SceneDev& sc, const BatchDev& bt, const int b, double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) double hs_lds[];
-  const int b = blockIdx.y, S = bt.stride, M = sc.M;
+  const int S = bt.stride, M = sc.M;
   const int n = bt.n[b];
   double* lx = hs_lds; double* ly = hs_lds + S; double* lt = hs_lds + 2 * S;
   const size_t so = (size_t)b * S;
@@ -64,7 +66,10 @@ __global__ void __launch_bounds__(kThreads) hsig3d_kernel(const SceneDev sc, con
       for (int q = 0; q < 3; ++q) r[q] += dl[q];
     }
   }
-  out[(size_t)b * M + l] = H / (4.0 * M_PI);
+  out[l] = H / (4.0 * M_PI);
+}
+__global__ void __launch_bounds__(kThreads) hsig3d_kernel(const SceneDev sc, const BatchDev bt, double* __restrict__ out) {
+  hsig3d_body(sc, bt, blockIdx.y, out + (size_t)blockIdx.y * sc.M);
 }
 
 // The same signature for a batch that does not fill the chip with one lane per (band, obstacle) - a planning tick has a handful of
@@ -75,11 +80,11 @@ __global__ void __launch_bounds__(kThreads) hsig3d_kernel(const SceneDev sc, con
 // the two kernels return identical bits; only the latency differs (a 5-band, 12-obstacle tick: 1.7 ms -> tens of microseconds).
 // grid = (ceil(M / 16), B). Dynamic LDS: 3 * stride doubles.
 constexpr int kHsTile = 16, kHsChunk = kThreads / kHsTile;
-__global__ void __launch_bounds__(kThreads) hsig3d_small_kernel(const SceneDev sc, const BatchDev bt, double* __restrict__ out) {
+__device__ __forceinline__ void hsig3d_small_body(const SceneDev& sc, const BatchDev& bt, const int b, double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) double hs_lds[];
   __shared__ double terms[10 * kHsChunk * kHsTile];   // [step][segment of the chunk][obstacle of the tile]
   __shared__ int skip[kHsChunk];
-  const int b = blockIdx.y, S = bt.stride, M = sc.M;
+  const int S = bt.stride, M = sc.M;
   const int n = bt.n[b];
   double* lx = hs_lds; double* ly = hs_lds + S; double* lt = hs_lds + 2 * S;
   const size_t so = (size_t)b * S;
@@ -142,7 +147,33 @@ __global__ void __launch_bounds__(kThreads) hsig3d_small_kernel(const SceneDev s
     }
     __syncthreads();
   }
-  if (s == 0 && lane_ok) out[(size_t)b * M + l] = H / (4.0 * M_PI);
+  if (s == 0 && lane_ok) out[l] = H / (4.0 * M_PI);
+}
+__global__ void __launch_bounds__(kThreads) hsig3d_small_kernel(const SceneDev sc, const BatchDev bt, double* __restrict__ out) {
+  hsig3d_small_body(sc, bt, blockIdx.y, out + (size_t)blockIdx.y * sc.M);
+}
+
+// The fleet forms (teb_fleet.hpp: a scene per band): the workgroup of band b starts from scenes[scene_of[b]] - uniform over the
+// workgroup, so the record arrives through scalar loads - and runs the body above, so a band's values are the bits of a single-scene
+// launch over its scene alone. Band b has its scene's row count M_b values, at out[off[b] .. off[b] + M_b) (off: prefix sums over the
+// bands, from the host). grid = (tiles of the WIDEST scene, B): a workgroup whose tile lies beyond its own scene returns before it
+// stages the band or meets a barrier.
+struct FleetHsigDev {
+  const SceneDev* scenes;   // [n_scenes]
+  const int* scene_of;      // [B], < n_scenes (checked by the host before the launch)
+  const int* off;           // [B + 1] first value of band b in out (3-D)
+};
+__global__ void __launch_bounds__(kThreads) hsig3d_fleet_kernel(const FleetHsigDev fl, const BatchDev bt, double* __restrict__ out) {
+  const int b = blockIdx.y;
+  const SceneDev sc = fl.scenes[fl.scene_of[b]];
+  if ((int)blockIdx.x * kThreads >= sc.M) return;
+  hsig3d_body(sc, bt, b, out + fl.off[b]);
+}
+__global__ void __launch_bounds__(kThreads) hsig3d_small_fleet_kernel(const FleetHsigDev fl, const BatchDev bt, double* __restrict__ out) {
+  const int b = blockIdx.y;
+  const SceneDev sc = fl.scenes[fl.scene_of[b]];
+  if ((int)blockIdx.x * kHsTile >= sc.M) return;
+  hsig3d_small_body(sc, bt, b, out + fl.off[b]);
 }
 
 // ---- 2-D ------------------------------------------------------------------------------------------------------------------
@@ -164,8 +195,8 @@ __device__ __forceinline__ void cdiv(CplxE& z, double br, double bi) {   // z /=
 }
 
 // prod_l = prod_{j != l, |o_l - o_j| >= 0.05} 1 / (o_l - o_j): the band-independent factor of A_l, once per obstacle table
-__global__ void hsig2d_prod_kernel(const SceneDev sc, double* __restrict__ pre, double* __restrict__ pim, int* __restrict__ pex) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
+__device__ __forceinline__ void hsig2d_prod_body(const SceneDev& sc, const int l, double* __restrict__ pre, double* __restrict__ pim,
+                                                 int* __restrict__ pex) {
   if (l >= sc.M) return;
   CplxE z{1.0, 0.0, 0};
   const double ox = sc.cx[l], oy = sc.cy[l];
@@ -177,22 +208,35 @@ __global__ void hsig2d_prod_kernel(const SceneDev sc, double* __restrict__ pre, 
   }
   pre[l] = z.re; pim[l] = z.im; pex[l] = z.e;
 }
+__global__ void hsig2d_prod_kernel(const SceneDev sc, double* __restrict__ pre, double* __restrict__ pim, int* __restrict__ pex) {
+  hsig2d_prod_body(sc, blockIdx.x * blockDim.x + threadIdx.x, pre, pim, pex);
+}
+// The products of every scene of a set in one launch, each over its own rows only: grid = (blocks over the largest scene, scenes).
+// The rows of the scenes lie one after the other in the set's store (scene_segments); row_base is the store's first centroid, so
+// sc.cx - row_base is the scene's first row there, and its products go to the same rows of pre / pim / pex.
+__global__ void hsig2d_prod_fleet_kernel(const SceneDev* __restrict__ scenes, const double* row_base, double* __restrict__ pre,
+                                         double* __restrict__ pim, int* __restrict__ pex) {
+  const SceneDev sc = scenes[blockIdx.y];
+  const size_t row = (size_t)(sc.cx - row_base);
+  hsig2d_prod_body(sc, blockIdx.x * blockDim.x + threadIdx.x, pre + row, pim + row, pex + row);
+}
 
 // one workgroup per band: lane l (strided) accumulates sum_i A_l * log_value(i, l) over the segments in order, with A_l kept
 // as mantissa * 2^e; the lanes' sums are brought to the common exponent of the block and tree-reduced.
-__global__ void __launch_bounds__(kThreads) hsig2d_kernel(const SceneDev sc, const BatchDev bt, double prescaler,
-                                                           const double* __restrict__ pre, const double* __restrict__ pim,
-                                                           const int* __restrict__ pex, double* __restrict__ out) {
+// The body is shared with the fleet form: band b against scene sc and its products, (re, im) to out[0], out[1].
+__device__ __forceinline__ void hsig2d_body(const SceneDev& sc, const BatchDev& bt, const int b, const double prescaler,
+                                            const double* __restrict__ pre, const double* __restrict__ pim,
+                                            const int* __restrict__ pex, double* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) double hs_lds[];
   __shared__ double red_re[kThreads], red_im[kThreads];
   __shared__ int red_e[kThreads];
-  const int b = blockIdx.x, S = bt.stride, M = sc.M;
+  const int S = bt.stride, M = sc.M;
   const int n = bt.n[b];
   double* lx = hs_lds; double* ly = hs_lds + S;
   const size_t so = (size_t)b * S;
   for (int i = threadIdx.x; i < n; i += kThreads) { lx[i] = bt.x[so + i]; ly[i] = bt.y[so + i]; }
   __syncthreads();
-  if (M == 0) { if (threadIdx.x == 0) { out[2 * b] = 0; out[2 * b + 1] = 0; } return; }
+  if (M == 0) { if (threadIdx.x == 0) { out[0] = 0; out[1] = 0; } return; }
   int m = M - 1 > 5 ? M - 1 : 5;
   const int a = (int)ceil(double(m) / 2.0);
   const int bb = m - a;
@@ -256,9 +300,24 @@ __global__ void __launch_bounds__(kThreads) hsig2d_kernel(const SceneDev sc, con
   }
   if (threadIdx.x == 0) {
     const int e = red_e[0];
-    out[2 * b] = e > -100000 ? ldexp(red_re[0], e) : 0.0;
-    out[2 * b + 1] = e > -100000 ? ldexp(red_im[0], e) : 0.0;
+    out[0] = e > -100000 ? ldexp(red_re[0], e) : 0.0;
+    out[1] = e > -100000 ? ldexp(red_im[0], e) : 0.0;
   }
+}
+__global__ void __launch_bounds__(kThreads) hsig2d_kernel(const SceneDev sc, const BatchDev bt, double prescaler,
+                                                           const double* __restrict__ pre, const double* __restrict__ pim,
+                                                           const int* __restrict__ pex, double* __restrict__ out) {
+  hsig2d_body(sc, bt, blockIdx.x, prescaler, pre, pim, pex, out + 2 * (size_t)blockIdx.x);
+}
+// one workgroup per band of a fleet batch, over the rows and the products (hsig2d_prod_fleet_kernel) of its own scene; a scene without
+// rows gives (0, 0)
+__global__ void __launch_bounds__(kThreads) hsig2d_fleet_kernel(const FleetHsigDev fl, const BatchDev bt, double prescaler, const double* row_base,
+                                                                 const double* __restrict__ pre, const double* __restrict__ pim,
+                                                                 const int* __restrict__ pex, double* __restrict__ out) {
+  const int b = blockIdx.x;
+  const SceneDev sc = fl.scenes[fl.scene_of[b]];
+  const size_t row = (size_t)(sc.cx - row_base);
+  hsig2d_body(sc, bt, b, prescaler, pre + row, pim + row, pex + row, out + 2 * (size_t)b);
 }
 
 }  // namespace tebamd

@@ -120,6 +120,10 @@ def lib():
             L.teb_amd_clear_scenes.argtypes = [vp]
             L.teb_amd_get_scene_count.argtypes = [vp, _abi.p_i32]
             L.teb_amd_select_best_per_scene.argtypes = [vp, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_f64]
+        if hasattr(L, "teb_amd_compute_h_signatures_per_scene"):   # equivalence classes per scene of a fleet batch
+            L.teb_amd_compute_h_signatures_per_scene.argtypes = [vp, d, _abi.p_f64, C.c_int64, _abi.p_i32, C.POINTER(C.c_int64)]
+            L.teb_amd_filter_equivalence_classes_per_scene.argtypes = [vp, d, _abi.p_i32, i32, _abi.p_i32, _abi.p_i32, _abi.p_i32]
+            L.teb_amd_filter_detours_per_scene.argtypes = [vp, C.POINTER(_abi.HcpParams), _abi.p_i32, _abi.p_i32]
         _LIB = L
     return _LIB
 
@@ -178,6 +182,7 @@ class TebBatchSolver:
         p = _abi.pack_scenes(tables, vias)
         _chk(lib().teb_amd_set_scenes(self._h, p.n, p.obstacles, _abi._ptr(p.via_count, C.c_int32), _abi._ptr(p.via_x, C.c_double),
                                       _abi._ptr(p.via_y, C.c_double)), "teb_amd_set_scenes")
+        self._widest_scene = max(len(t) for t in tables)
 
     def set_band_scenes(self, scene_of):
         a = _abi.i32(scene_of)
@@ -204,6 +209,51 @@ class TebBatchSolver:
         _chk(lib().teb_amd_select_best_per_scene(self._h, _abi._ptr(lb, C.c_int32), _abi._ptr(ip, C.c_int32), _abi._ptr(best, C.c_int32),
                                                  _abi._ptr(cost, C.c_double)), "teb_amd_select_best_per_scene")
         return best[:ns].copy(), cost[:ns].copy()
+
+    def h_signatures_per_scene(self, prescaler=1.0, values=True):
+        """Fleet mode: the H-signature of every band against its own scene, one launch - a list of per-band arrays, [rows of the band's
+        scene] (HSignature3d, include_dynamic_obstacles) or [2] (HSignature: re, im). values=False: compute only (the signatures stay
+        in the handle for filter_equivalence_classes_per_scene)."""
+        self._sync_count()
+        n = C.c_int64(0)
+        if not values:
+            _chk(lib().teb_amd_compute_h_signatures_per_scene(self._h, prescaler, None, 0, None, C.byref(n)), "teb_amd_compute_h_signatures_per_scene")
+            return None
+        B = max(self.count, 1)
+        out = np.zeros(B * max(getattr(self, "_widest_scene", 0), 2))   # no band is wider than the widest scene
+        off = np.zeros(B + 1, np.int32)
+        _chk(lib().teb_amd_compute_h_signatures_per_scene(self._h, prescaler, _abi._ptr(out, C.c_double), out.size, _abi._ptr(off, C.c_int32),
+                                                          C.byref(n)), "teb_amd_compute_h_signatures_per_scene")
+        return [out[off[b]:off[b + 1]].copy() for b in range(self.count)]
+
+    def _best_per_scene(self, best, what):
+        if best is None:
+            return None
+        a = _abi.i32(best)
+        if len(a) != self.scene_count():
+            raise ValueError("%s: %d entries for %d scenes" % (what, len(a), self.scene_count()))
+        return a
+
+    def filter_equivalence_classes_per_scene(self, threshold=0.1, best=None, max_number_plans_in_current_class=1):
+        """filter_equivalence_classes over the bands of every scene on the signatures of the last h_signatures_per_scene call:
+        (keep, valid, reasonable), each [B]. best: per scene a band of that scene (visited first; its class is remembered for the
+        scene) or -1, None = none."""
+        self._sync_count()
+        bp = self._best_per_scene(best, "filter_equivalence_classes_per_scene")
+        keep = np.zeros(self.count, np.int32); valid = np.zeros(self.count, np.int32); reas = np.zeros(self.count, np.int32)
+        I = lambda a: _abi._ptr(a, C.c_int32)
+        _chk(lib().teb_amd_filter_equivalence_classes_per_scene(self._h, threshold, I(bp), max_number_plans_in_current_class, I(keep), I(valid),
+                                                                I(reas)), "teb_amd_filter_equivalence_classes_per_scene")
+        return keep, valid, reas
+
+    def filter_detours_per_scene(self, keep, best, params=None):
+        """filter_detours scene by scene (best: per scene a band of that scene or -1): returns the new keep array."""
+        p = params if params is not None else self.cfg.hcp_params()
+        bp = self._best_per_scene(best, "filter_detours_per_scene")
+        keep = _abi.i32(keep).copy()
+        _chk(lib().teb_amd_filter_detours_per_scene(self._h, C.byref(p), _abi._ptr(bp, C.c_int32), _abi._ptr(keep, C.c_int32)),
+             "teb_amd_filter_detours_per_scene")
+        return keep
 
     # -- state ---------------------------------------------------------------------------------------
     def upload(self, batch):
