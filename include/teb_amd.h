@@ -689,6 +689,8 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  *                            teb_amd_compact_bands moves its entries with the bands (the slots it frees go back to scene 0).
  *                            teb_amd_optimize_batch returns TEB_AMD_ERR_INVALID_ARG when a band maps to a scene >= n_scenes, or when
  *                            jacobian_mode is TEB_AMD_JACOBIAN_G2O_NUMERIC (fleet kernels exist for closed-form Jacobians).
+ *   teb_amd_get_band_scenes  the map of the resident bands as compaction and per-scene exploration moved and extended it: *count = B
+ *                            (may be NULL); scene_of NULL: count only; capacity < B: TEB_AMD_ERR_CAPACITY.
  *   teb_amd_clear_scenes     back to the single-scene table as it was.
  *   teb_amd_get_scene_count  0 = single-scene mode.
  *   teb_amd_select_best_per_scene  teb_amd_select_best over the bands of every scene: last_best / initial_plan [n_scenes] are BAND
@@ -701,7 +703,7 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  * results, upload / download, snapshot / restore, teb_amd_compact_bands). The calls that read or write THE scene of the handle return
  * TEB_AMD_ERR_INVALID_ARG while scenes are set (call teb_amd_clear_scenes first): teb_amd_set_obstacles, both costmap routes,
  * teb_amd_set_via_points, teb_amd_compute_h_signatures / teb_amd_filter_equivalence_classes / teb_amd_filter_detours (their
- * per-scene forms below take their place), teb_amd_explore_candidates (exploration per scene does not exist yet),
+ * per-scene forms below take their place), teb_amd_explore_candidates (teb_amd_explore_candidates_per_scene takes its place),
  * teb_amd_select_best and the distributed calls (a refused rank still enters the collective and sends the unusable record, as for
  * any other error of one rank), teb_amd_debug_linearize, teb_amd_debug_distance. Product library only (the other build variants
  * refuse the launch).
@@ -730,10 +732,46 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  * teb_amd_set_band_scenes, teb_amd_clear_scenes, teb_amd_set_config, teb_amd_compact_bands and every call that changes the bands
  * invalidate them. None of the three touches the single scene's state: after teb_amd_clear_scenes, teb_amd_compute_h_signatures and
  * teb_amd_filter_equivalence_classes give what they gave before teb_amd_set_scenes, remembered best class included.
+ *
+ * Candidate exploration per scene - exploreEquivalenceClassesAndInitTebs of every robot of the fleet. Valid only while scenes are set;
+ * in single-scene mode the three calls return TEB_AMD_ERR_INVALID_ARG (call teb_amd_set_scenes first). Every output pointer may be NULL.
+ *   teb_amd_explore_candidates_per_scene  teb_amd_explore_candidates of every scene with its own start / goal [3 n_scenes], start
+ *                            velocity [3 n_scenes] or NULL, best band (best[s]: a band of scene s or negative, NULL = none; a band of
+ *                            another scene is TEB_AMD_ERR_INVALID_ARG), unit samples ([n_scenes][2 roadmap_graph_no_samples] or NULL)
+ *                            and initial plan (plan_count [n_scenes] or NULL = none; the poses of the plans one after the other in
+ *                            plan_x / plan_y / plan_yaw). Contract: the bands of scene s, read in band order, are bit for bit the batch
+ *                            of a single-scene handle that holds only scene s, held the same bands of s before the call and ran
+ *                            teb_amd_explore_candidates with the arguments of s (max_tebs >= max_number_classes there): number and
+ *                            order of the bands, x / y / theta / dt, the via-point / velocity flags, n_vertices[s], n_paths[s], the
+ *                            graph, and initial_plan_teb[s] - the position of that band AMONG THE BANDS OF SCENE s, or -1.
+ *                            n_bands[s] = bands of scene s after the call, *n_total = all bands. New bands are appended to the batch
+ *                            and enter the band -> scene map. Their order at the tail: first the bands made from the initial plans, by
+ *                            scene index; then round by round the accepted graph candidates, by scene index and within a scene in
+ *                            path order (a round takes up to a fixed number of paths from every scene that still has room; the bands
+ *                            of a scene and every count are independent of that number); last the line bands of the scenes that
+ *                            stand at their goal without a band, by scene index.
+ *                            Every scene has its own default-seeded generator for the roadmap samples, its own remembered best class
+ *                            (shared with teb_amd_filter_equivalence_classes_per_scene), remembered initial-plan class and last graph:
+ *                            kept across teb_amd_set_scenes calls with the same number of scenes, forgotten by teb_amd_clear_scenes or
+ *                            another number of scenes. A scene that returns before its graph (full, or start within xy_goal_tolerance
+ *                            of the goal) draws nothing. None of this touches the single scene's state, generator included.
+ *                            Capacity: with c_s bands of scene s before the call, sum_s max(c_s, max_number_classes) > max_tebs
+ *                            returns TEB_AMD_ERR_CAPACITY before anything changes. A start-goal path or plan longer than a band:
+ *                            TEB_AMD_ERR_CAPACITY as for the single scene; the bands accepted so far stay and the map matches them.
+ *                            A band that maps to a scene >= n_scenes: TEB_AMD_ERR_INVALID_ARG. The per-scene signatures are reused
+ *                            when they are fresh (same bands, same prescaler) and are stale after the call.
+ *   teb_amd_get_exploration_graph_per_scene  teb_amd_get_exploration_graph for the last graph of one scene (*n_vertices = 0: the scene
+ *                            returned before its graph in the last call).
+ *   teb_amd_compact_bands_per_scene  within every scene the band best[s] and the scene's first band exchange places (std::iter_swap of
+ *                            renewAndAnalyzeOldTebs); then the kept bands move to the front of the batch in that order, the map with
+ *                            them (freed slots: scene 0). For every scene the subsequence of its bands is what
+ *                            teb_amd_compact_bands(keep of s, best of s) leaves on a handle that holds only that scene. new_best[s] =
+ *                            new index of the scene's best band, -1 when it was dropped or none was given. *n_kept = bands left.
  */
 int  teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obstacles_t* obstacles /* [n_scenes] */,
                         const int32_t* via_count /* [n_scenes] or NULL */, const double* via_x, const double* via_y /* concatenated */);
 int  teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_t count);
+int  teb_amd_get_band_scenes(teb_amd_handle_t* h, int32_t* scene_of /* [capacity] or NULL */, int32_t capacity, int32_t* count);
 int  teb_amd_clear_scenes(teb_amd_handle_t* h);
 int  teb_amd_get_scene_count(teb_amd_handle_t* h, int32_t* n_scenes);
 int  teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best, const int32_t* initial_plan,
@@ -746,6 +784,19 @@ int  teb_amd_filter_equivalence_classes_per_scene(teb_amd_handle_t* h, double th
                                                   int32_t* reasonable /* [B], any may be NULL */);
 int  teb_amd_filter_detours_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const int32_t* best /* [n_scenes] */,
                                       int32_t* keep /* [B] in/out */);
+int  teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start /* [3 n_scenes] */,
+                                          const double* goal /* [3 n_scenes] */, double dist_to_obst,
+                                          const double* start_vel /* [3 n_scenes] or NULL */, int32_t free_goal_vel,
+                                          const int32_t* best /* [n_scenes] band of scene s or negative; NULL = none */,
+                                          const double* unit_samples /* [n_scenes][2 roadmap_graph_no_samples] or NULL */,
+                                          int64_t max_paths, int32_t* n_total, int32_t* n_bands /* [n_scenes] */,
+                                          int32_t* n_vertices /* [n_scenes] */, int32_t* n_paths /* [n_scenes] */,
+                                          const int32_t* plan_count /* [n_scenes] or NULL */, const double* plan_x, const double* plan_y,
+                                          const double* plan_yaw /* concatenated */, int32_t* initial_plan_teb /* [n_scenes] */);
+int  teb_amd_get_exploration_graph_per_scene(teb_amd_handle_t* h, int32_t scene, double* vx, double* vy, unsigned char* adjacency,
+                                             int32_t capacity_vertices, int32_t* n_vertices);
+int  teb_amd_compact_bands_per_scene(teb_amd_handle_t* h, const int32_t* keep /* [B] */, const int32_t* best /* [n_scenes] or NULL */,
+                                     int32_t* n_kept, int32_t* new_best /* [n_scenes] */);
 
 #ifdef __cplusplus
 }

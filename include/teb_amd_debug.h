@@ -114,6 +114,10 @@ int teb_amd_debug_build_info(char* kernel_hash, int32_t kernel_hash_capacity, ch
 int teb_amd_set_phase_log(teb_amd_handle_t* h, int32_t enable);
 int teb_amd_get_phase_log(teb_amd_handle_t* h, double* cycles, int32_t capacity_bands, int32_t* bands);
 
+/* Paths a scene contributes to one round of teb_amd_explore_candidates_per_scene (0: the built-in value). The bands, counts and graphs
+ * of the call do not depend on it; tests run the same scene set with several values. */
+int teb_amd_debug_set_explore_quota(teb_amd_handle_t* h, int32_t quota);
+
 /* per-TEB flags of the last launch: bit0 association list overflow, bit1 autoResize capacity overflow */
 int teb_amd_debug_assoc_overflow(teb_amd_handle_t* h, int32_t* flags);
 

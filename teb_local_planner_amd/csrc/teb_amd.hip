@@ -233,13 +233,34 @@ struct teb_amd_handle {
     std::vector<double> hsig_host;   // band after band
     std::vector<std::vector<double>> best_class;   // [n_scenes] best_teb_eq_class_ of every scene's planner
     std::vector<int> best_class_mode;
-    void forget_best_classes(size_t ns) { best_class.assign(ns, {}); best_class_mode.assign(ns, 0); }
+    double hsig_prescaler = 0;       // of those signatures
+    // candidate exploration per scene (teb_amd_explore_candidates_per_scene): what a planner - a robot, a scene - remembers, with the
+    // lifetime of best_class; none of it is the single scene's (rnd_generator, initial_class, g_vx .. above)
+    std::vector<std::mt19937> rnd;                    // [n_scenes] ProbRoadmapGraph::rnd_generator_, default-seeded
+    std::vector<std::vector<double>> initial_class;   // [n_scenes] initial_plan_eq_class_
+    std::vector<int> initial_class_mode;
+    std::vector<std::vector<double>> g_vx, g_vy;      // [n_scenes] the last graph of every scene (empty: returned before its graph)
+    std::vector<std::vector<unsigned char>> g_adj;
+    // its scratch, separate from the single scene's and allocated at the first call: candidate strips, path points, offsets,
+    // candidate -> scene map, signatures; the graphs of a call (vertices, adjacency, records)
+    DevBuf<double> ex_x, ex_y, ex_th, ex_dt, ex_px, ex_py, ex_pyaw, ex_sig, ex_orient, ex_line, ex_gvx, ex_gvy;
+    DevBuf<int> ex_n, ex_off, ex_scene, ex_soff, ex_map;
+    DevBuf<unsigned char> ex_gadj;
+    DevBuf<GraphFleetRec> ex_rec;
+    void forget_best_classes(size_t ns) {   // and everything else a scene's planner remembers
+      best_class.assign(ns, {}); best_class_mode.assign(ns, 0);
+      rnd.assign(ns, std::mt19937()); initial_class.assign(ns, {}); initial_class_mode.assign(ns, 0);
+      g_vx.assign(ns, {}); g_vy.assign(ns, {}); g_adj.assign(ns, {});
+    }
     void release() {   // the device side
       store.free();
       free_all(scene_of, sel_last, sel_init, sel_idx, sel_cost, scenes, hs_pre, hs_pim, hs_pex, hs_off);
+      free_all(ex_x, ex_y, ex_th, ex_dt, ex_px, ex_py, ex_pyaw, ex_sig, ex_orient, ex_line, ex_gvx, ex_gvy, ex_n, ex_off, ex_scene, ex_soff, ex_map,
+               ex_gadj, ex_rec);
       allocated = false;
     }
   } fleet;
+  int explore_quota = 0;   // teb_amd_debug_set_explore_quota: paths per scene and round of the per-scene exploration, 0 = kExploreQuota
   // the bands, the obstacles or the configuration change: the signatures of an earlier compute call are stale, the single scene's and
   // the scene set's alike
   void signatures_stale() { hsig_mode = 0; fleet.hsig_mode = 0; }
@@ -1085,6 +1106,16 @@ int teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_
     HIPCHK(hipMemcpyAsync(F.scene_of.p, F.band_scene.data(), F.band_scene.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
+  return TEB_AMD_OK;
+}
+
+int teb_amd_get_band_scenes(teb_amd_handle_t* h, int32_t* scene_of, int32_t capacity, int32_t* count) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (count) *count = h->B;
+  if (!scene_of) return TEB_AMD_OK;
+  if (capacity < h->B) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_get_band_scenes: more bands than capacity");
+  for (int b = 0; b < h->B; ++b) scene_of[b] = (size_t)b < h->fleet.band_scene.size() ? h->fleet.band_scene[b] : 0;
   return TEB_AMD_OK;
 }
 
@@ -2246,7 +2277,7 @@ int teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler
   if (total > 0) HIPCHK(hipMemcpyAsync(F.hsig_host.data(), out, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // (off is read until here)
   F.hsig_off = std::move(off);
-  F.hsig_mode = mode; F.hsig_B = B;
+  F.hsig_mode = mode; F.hsig_B = B; F.hsig_prescaler = prescaler;
   if (!values) return TEB_AMD_OK;   // compute only: the signatures stay in the handle for the filter call
   if (capacity_values < (int64_t)total) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_compute_h_signatures_per_scene: capacity_values is smaller than *n_values (the signatures are kept for the filter call)");
   if (total > 0) std::memcpy(values, F.hsig_host.data(), total * sizeof(double));
@@ -2385,6 +2416,73 @@ struct PathEnumerator {
     return false;
   }
 };
+
+// The vertices of createGraph for ONE planner, on the host (O(M) on the centroids of its obstacle table): lrKeyPointGraph
+// (src/graph_search.cpp:115-153) or ProbRoadmapGraph (:247-290, samples from unit_samples or drawn from the planner's generator).
+// vx / vy: start, key points or samples, goal. ga: everything of the edge kernel's arguments but N, the vertex and the adjacency pointers.
+void graph_vertices(const HostObst& hob, const double* start, const double* goal, double start_goal_dist, double dist_to_obst,
+                    const teb_amd_hcp_params_t* p, std::mt19937& generator, const double* unit_samples, std::vector<double>& vx,
+                    std::vector<double>& vy, GraphArgs& ga) {
+  const int M = (int)hob.rows();
+  const double sx = start[0], sy = start[1], gx = goal[0], gy = goal[1];
+  double dfx = gx - sx, dfy = gy - sy;
+  auto normalize = [](double& x, double& y) { const double z = x * x + y * y; if (z > 0) { const double n = std::sqrt(z); x = x / n; y = y / n; } };
+  vx.assign(1, sx); vy.assign(1, sy);
+  ga.keypoint = p->simple_exploration ? 1 : 0; ga.near_u = ga.near_v = -1; ga.thr = p->obstacle_heading_threshold;
+  ga.sox = std::cos(start[2]); ga.soy = std::sin(start[2]);
+  if (p->simple_exploration) {                                              // lrKeyPointGraph::createGraph, :115-153
+    double nx = -dfy, ny = dfx;
+    normalize(nx, ny);
+    nx = nx * dist_to_obst; ny = ny * dist_to_obst;
+    normalize(dfx, dfy);
+    double min_dist = std::numeric_limits<double>::max();
+    for (int o = 0; o < M; ++o) {
+      const double ox = hob.cx[o] - sx, oy = hob.cy[o] - sy;
+      const double dist = std::sqrt(ox * ox + oy * oy);
+      if ((ox * dfx + oy * dfy) / dist < 0.1) continue;                     // obstacle not in front of the start
+      vx.push_back(hob.cx[o] + nx); vy.push_back(hob.cy[o] + ny);
+      vx.push_back(hob.cx[o] - nx); vy.push_back(hob.cy[o] - ny);
+      if (p->obstacle_heading_threshold && dist < min_dist) { min_dist = dist; ga.near_u = (int)vx.size() - 2; ga.near_v = (int)vx.size() - 1; }
+    }
+    ga.min_dist = 0.5 * dist_to_obst;
+  } else {                                                                  // ProbRoadmapGraph::createGraph, :247-290
+    double nx = -dfy, ny = dfx;
+    normalize(nx, ny);
+    const double area_width = p->roadmap_graph_area_width;
+    const double len = start_goal_dist * p->roadmap_graph_area_length_scale;
+    const double phi = std::atan2(dfy, dfx);
+    double ox, oy;
+    if (p->roadmap_graph_area_length_scale != 1.0) {
+      double ux = dfx, uy = dfy;
+      normalize(ux, uy);
+      const double f = 0.5 * (1.0 - p->roadmap_graph_area_length_scale) * start_goal_dist, w2 = 0.5 * area_width;
+      ox = (sx + f * ux) - w2 * nx; oy = (sy + f * uy) - w2 * ny;
+    } else {
+      const double w2 = 0.5 * area_width;
+      ox = sx - w2 * nx; oy = sy - w2 * ny;
+    }
+    normalize(dfx, dfy);
+    int drawn = 0;
+    auto draw = [&](double a, double b) {    // boost::random::uniform_real_distribution<double>(a, b) on the 32-bit engine
+      if (unit_samples) return unit_samples[drawn++] * (b - a) + a;
+      for (;;) {
+        const double numerator = (double)(generator() - std::mt19937::min());
+        const double divisor = (double)(std::mt19937::max() - std::mt19937::min()) + 1;
+        const double result = numerator / divisor * (b - a) + a;
+        if (result < b) return result;
+      }
+    };
+    const double cphi = std::cos(phi), sphi = std::sin(phi);
+    for (int i = 0; i < p->roadmap_graph_no_samples; ++i) {
+      const double uy = draw(0, area_width);   // GCC evaluates Eigen::Vector2d(distribution_x(g), distribution_y(g)) right to left
+      const double ux = draw(0, len);
+      vx.push_back(ox + (cphi * ux - sphi * uy)); vy.push_back(oy + (sphi * ux + cphi * uy));
+    }
+    ga.min_dist = dist_to_obst;
+  }
+  vx.push_back(gx); vy.push_back(gy);
+  ga.dnx = dfx; ga.dny = dfy;
+}
 }  // namespace
 
 int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
@@ -2467,8 +2565,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
   }
   auto body = [&]() -> int {
   if (h->B >= slots) return TEB_AMD_OK;                                     // src/graph_search.cpp:99-100, 231-232
-  const double sx = start[0], sy = start[1], gx = goal[0], gy = goal[1];
-  double dfx = gx - sx, dfy = gy - sy;
+  const double dfx = goal[0] - start[0], dfy = goal[1] - start[1];
   const double start_goal_dist = std::sqrt(dfx * dfx + dfy * dfy);
   if (start_goal_dist < p->xy_goal_tolerance) {                             // :104-113, :237-246
     if (h->B == 0) {                                                        // addAndInitNewTeb(start, goal, ...), hcp.cpp:358-384
@@ -2482,62 +2579,9 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
     return TEB_AMD_OK;
   }
   // ---- vertices (host: O(M) on the centroids kept from teb_amd_set_obstacles) ------------------------------------------------------
-  auto normalize = [](double& x, double& y) { const double z = x * x + y * y; if (z > 0) { const double n = std::sqrt(z); x = x / n; y = y / n; } };
-  std::vector<double> vx{sx}, vy{sy};
+  std::vector<double> vx, vy;
   GraphArgs ga;
-  ga.keypoint = p->simple_exploration ? 1 : 0; ga.near_u = ga.near_v = -1; ga.thr = p->obstacle_heading_threshold;
-  ga.sox = std::cos(start[2]); ga.soy = std::sin(start[2]);
-  if (p->simple_exploration) {                                              // lrKeyPointGraph::createGraph, :115-153
-    double nx = -dfy, ny = dfx;
-    normalize(nx, ny);
-    nx = nx * dist_to_obst; ny = ny * dist_to_obst;
-    normalize(dfx, dfy);
-    double min_dist = std::numeric_limits<double>::max();
-    for (int o = 0; o < M; ++o) {
-      const double ox = h->hob.cx[o] - sx, oy = h->hob.cy[o] - sy;
-      const double dist = std::sqrt(ox * ox + oy * oy);
-      if ((ox * dfx + oy * dfy) / dist < 0.1) continue;                     // obstacle not in front of the start
-      vx.push_back(h->hob.cx[o] + nx); vy.push_back(h->hob.cy[o] + ny);
-      vx.push_back(h->hob.cx[o] - nx); vy.push_back(h->hob.cy[o] - ny);
-      if (p->obstacle_heading_threshold && dist < min_dist) { min_dist = dist; ga.near_u = (int)vx.size() - 2; ga.near_v = (int)vx.size() - 1; }
-    }
-    ga.min_dist = 0.5 * dist_to_obst;
-  } else {                                                                  // ProbRoadmapGraph::createGraph, :247-290
-    double nx = -dfy, ny = dfx;
-    normalize(nx, ny);
-    const double area_width = p->roadmap_graph_area_width;
-    const double len = start_goal_dist * p->roadmap_graph_area_length_scale;
-    const double phi = std::atan2(dfy, dfx);
-    double ox, oy;
-    if (p->roadmap_graph_area_length_scale != 1.0) {
-      double ux = dfx, uy = dfy;
-      normalize(ux, uy);
-      const double f = 0.5 * (1.0 - p->roadmap_graph_area_length_scale) * start_goal_dist, w2 = 0.5 * area_width;
-      ox = (sx + f * ux) - w2 * nx; oy = (sy + f * uy) - w2 * ny;
-    } else {
-      const double w2 = 0.5 * area_width;
-      ox = sx - w2 * nx; oy = sy - w2 * ny;
-    }
-    normalize(dfx, dfy);
-    int drawn = 0;
-    auto draw = [&](double a, double b) {    // boost::random::uniform_real_distribution<double>(a, b) on the 32-bit engine
-      if (unit_samples) return unit_samples[drawn++] * (b - a) + a;
-      for (;;) {
-        const double numerator = (double)(h->rnd_generator() - std::mt19937::min());
-        const double divisor = (double)(std::mt19937::max() - std::mt19937::min()) + 1;
-        const double result = numerator / divisor * (b - a) + a;
-        if (result < b) return result;
-      }
-    };
-    const double cphi = std::cos(phi), sphi = std::sin(phi);
-    for (int i = 0; i < p->roadmap_graph_no_samples; ++i) {
-      const double uy = draw(0, area_width);   // GCC evaluates Eigen::Vector2d(distribution_x(g), distribution_y(g)) right to left
-      const double ux = draw(0, len);
-      vx.push_back(ox + (cphi * ux - sphi * uy)); vy.push_back(oy + (sphi * ux + cphi * uy));
-    }
-    ga.min_dist = dist_to_obst;
-  }
-  vx.push_back(gx); vy.push_back(gy);
+  graph_vertices(h->hob, start, goal, start_goal_dist, dist_to_obst, p, h->rnd_generator, unit_samples, vx, vy, ga);
   const int N = (int)vx.size();
   if (n_vertices) *n_vertices = N;
   // ---- edges (device) -------------------------------------------------------------------------------------------------------------
@@ -2545,7 +2589,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
   if (h->g_adj.n < (size_t)N * N) { h->g_adj.free(); HIPCHK(h->g_adj.alloc((size_t)N * N)); }
   HIPCHK(hipMemcpyAsync(h->g_vx.p, vx.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->g_vy.p, vy.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  ga.N = N; ga.gx = h->g_vx.p; ga.gy = h->g_vy.p; ga.dnx = dfx; ga.dny = dfy; ga.adj = h->g_adj.p;
+  ga.N = N; ga.gx = h->g_vx.p; ga.gy = h->g_vy.p; ga.adj = h->g_adj.p;
   const long long pairs = (long long)N * N;
   hipLaunchKernelGGL(graph_edges_kernel, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, scene_of(h), ga);
   HIPCHK(hipGetLastError());
@@ -2630,14 +2674,390 @@ int teb_amd_get_exploration_graph(teb_amd_handle_t* h, double* vx, double* vy, u
   return TEB_AMD_OK;
 }
 
-int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best, int32_t* n_kept, int32_t* new_best) {
+// ---- candidate generation per scene of a fleet batch (teb_amd.h, fleet batches; kernels: the fleet forms of teb_graph.hpp) ----------
+namespace {
+constexpr int kExploreQuota = 16;  // paths a scene contributes to a round (teb_amd_debug_set_explore_quota overrides it)
+
+// the candidate scratch of the scene set, for K candidates and `values` signature values; grows, never shrinks
+int ensure_fleet_candidate_buffers(teb_amd_handle* h, size_t K, size_t values) {
+  auto& F = h->fleet;
+  bool ok = true;
+  auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
+  if (F.ex_n.n < K) {
+    free_all(F.ex_x, F.ex_y, F.ex_th, F.ex_dt, F.ex_n, F.ex_px, F.ex_py, F.ex_pyaw, F.ex_off, F.ex_scene, F.ex_soff, F.ex_line);
+    const size_t KS = K * (size_t)h->stride, KP = K * ((size_t)h->stride + 1);
+    A(F.ex_x.alloc(KS)); A(F.ex_y.alloc(KS)); A(F.ex_th.alloc(KS)); A(F.ex_dt.alloc(KS)); A(F.ex_n.alloc(K));
+    A(F.ex_px.alloc(KP)); A(F.ex_py.alloc(KP)); A(F.ex_pyaw.alloc(KP)); A(F.ex_off.alloc(K + 1)); A(F.ex_scene.alloc(K));
+    A(F.ex_soff.alloc(K + 1)); A(F.ex_line.alloc(6 * K));
+  }
+  if (F.ex_sig.n < std::max<size_t>(values, 2)) { F.ex_sig.free(); A(F.ex_sig.alloc(std::max<size_t>(values, 2))); }
+  if (F.ex_map.n < (size_t)h->max_tebs) { F.ex_map.free(); A(F.ex_map.alloc(h->max_tebs)); }
+  if (F.ex_orient.n < 2 * (size_t)h->max_tebs) {
+    F.ex_orient.free(); F.ex_rec.free();
+    A(F.ex_orient.alloc(2 * (size_t)h->max_tebs)); A(F.ex_rec.alloc(h->max_tebs));
+  }
+  if (!ok) { (void)hipGetLastError(); return fail(TEB_AMD_ERR_HIP, "teb_amd_explore_candidates_per_scene: candidate scratch allocation failed"); }
+  return TEB_AMD_OK;
+}
+}  // namespace
+
+int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
+                                         double dist_to_obst, const double* start_vel, int32_t free_goal_vel, const int32_t* best,
+                                         const double* unit_samples, int64_t max_paths, int32_t* n_total, int32_t* n_bands,
+                                         int32_t* n_vertices, int32_t* n_paths, const int32_t* plan_count, const double* plan_x,
+                                         const double* plan_y, const double* plan_yaw, int32_t* initial_plan_teb) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if (!keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null keep");
+  if ((rc = require_fleet_mode(h, "teb_amd_explore_candidates_per_scene"))) return rc;
+  if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
+  auto& F = h->fleet;
+  const int ns = F.n_scenes, B0 = h->B;
+  const teb_amd_config_t& c = h->cfg;
+  std::vector<int> plan_off(ns + 1, 0);
+  for (int s = 0; s < ns; ++s) {
+    const int np = plan_count ? plan_count[s] : 0;
+    if (np < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "negative plan_count");
+    if (np > 0 && (!plan_x || !plan_y || !plan_yaw)) return fail(TEB_AMD_ERR_INVALID_ARG, "null initial plan");
+    if (np > h->stride + 1) return fail(TEB_AMD_ERR_CAPACITY, "plan / path longer than max_poses + 1");
+    plan_off[s + 1] = plan_off[s] + np;
+  }
+  if ((rc = check_band_scenes(h, B0))) return rc;
+  if ((rc = check_best_per_scene(h, best, B0, "teb_amd_explore_candidates_per_scene"))) return rc;
+  std::vector<std::vector<int>> of;   // the bands of every scene in band order; grows with the accepted candidates
+  bands_per_scene(h, B0, of);
+  const int slots = p->max_number_classes;   // per scene (the reference handle of the contract has max_tebs >= max_number_classes)
+  {
+    long long need = 0;
+    for (int s = 0; s < ns; ++s) need += std::max<long long>((long long)of[s].size(), slots);
+    if (need > h->max_tebs) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "teb_amd_explore_candidates_per_scene: %d scenes may grow to %lld bands, max_tebs is %d", ns, need, h->max_tebs);
+      return fail(TEB_AMD_ERR_CAPACITY, buf);
+    }
+  }
+  const int mode = c.include_dynamic_obstacles ? 3 : 2;
+  auto width = [&](int s) { return mode == 3 ? (int)F.tabs[s].rows() : 2; };
+  int widest = 0;
+  for (const HostObst& t : F.tabs) widest = std::max(widest, (int)t.rows());
+  const int q = h->explore_quota > 0 ? h->explore_quota : kExploreQuota;
+  const size_t K = std::max<size_t>(kCandChunk, (size_t)q * ns);
+  if ((rc = ensure_fleet_candidate_buffers(h, K, K * (size_t)std::max(widest, 2)))) return rc;
+  for (int s = 0; s < ns; ++s) {
+    F.g_vx[s].clear(); F.g_vy[s].clear(); F.g_adj[s].clear();
+    if (n_vertices) n_vertices[s] = 0;
+    if (n_paths) n_paths[s] = 0;
+    if (n_bands) n_bands[s] = (int)of[s].size();
+    if (initial_plan_teb) initial_plan_teb[s] = -1;
+  }
+  if (n_total) *n_total = B0;
+  // ---- 1. equivalence_classes_ of the existing bands, one table per scene -----------------------------------------------------------
+  std::vector<ClassTable> ct(ns);
+  if (B0 > 0) {
+    const bool fresh = F.hsig_mode == mode && F.hsig_B == B0 && F.hsig_prescaler == p->h_signature_prescaler;
+    if (!fresh && (rc = teb_amd_compute_h_signatures_per_scene(h, p->h_signature_prescaler, nullptr, 0, nullptr, nullptr))) return rc;
+  }
+  for (int s = 0; s < ns; ++s) {
+    ClassTable& t = ct[s];
+    t.mode = mode; t.W = width(s); t.thr = p->h_signature_threshold; t.max_in_best = p->max_number_plans_in_current_class;
+    for (int b : of[s]) t.classes.emplace_back(F.hsig_host.data() + F.hsig_off[b], F.hsig_host.data() + F.hsig_off[b] + t.W);
+    if (best && best[s] >= 0) { F.best_class[s].assign(F.hsig_host.data() + F.hsig_off[best[s]], F.hsig_host.data() + F.hsig_off[best[s]] + t.W); F.best_class_mode[s] = mode; }
+    if (F.best_class_mode[s] == mode && (int)F.best_class[s].size() == t.W) { t.has_best = true; t.best = F.best_class[s]; }   // best_teb_eq_class_
+  }
+  h->signatures_stale();   // the batch is about to change
+  h->consumers_valid = false; h->nmax_known = -1;
+  BatchDev cand = batch_of(h);   // the scratch strips of the scene set seen as a batch of K bands
+  cand.B = (int)K; cand.n = F.ex_n.p; cand.x = F.ex_x.p; cand.y = F.ex_y.p; cand.th = F.ex_th.p; cand.dt = F.ex_dt.p;
+  // the candidates of a launch: scene of every candidate, its signature values at sig[soff[k] ..)
+  std::vector<int> cscene, soff;
+  std::vector<double> sig;
+  auto classify = [&]() -> int {
+    const int count = (int)cscene.size();
+    soff.assign(count + 1, 0);
+    for (int k = 0; k < count; ++k) soff[k + 1] = soff[k] + width(cscene[k]);
+    const size_t total = (size_t)soff[count];
+    sig.assign(std::max<size_t>(total, 1), 0.0);
+    HIPCHK(hipMemcpyAsync(F.ex_scene.p, cscene.data(), count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    FleetHsigDev fl;
+    fl.scenes = F.scenes.p; fl.scene_of = F.ex_scene.p; fl.off = F.ex_soff.p;
+    if (mode == 3) {
+      if (total > 0) {
+        HIPCHK(hipMemcpyAsync(F.ex_soff.p, soff.data(), soff.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        const bool wide = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE || (h->opt.hsig3d_kernel != TEB_AMD_HSIG3D_SMALL && (long long)total >= 32768);
+        if (wide)
+          hipLaunchKernelGGL(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
+                             h->stream, fl, cand, F.ex_sig.p);
+        else
+          hipLaunchKernelGGL(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
+                             h->stream, fl, cand, F.ex_sig.p);
+        HIPCHK(hipGetLastError());
+      }
+    } else {
+      if (widest > 0 && !F.hs_prod_valid) {   // the products of the set, shared with teb_amd_compute_h_signatures_per_scene
+        hipLaunchKernelGGL(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, ns), dim3(kThreads), 0, h->stream, F.scenes.p,
+                           F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p);
+        HIPCHK(hipGetLastError());
+        F.hs_prod_valid = true;
+      }
+      hipLaunchKernelGGL(hsig2d_fleet_kernel, dim3(count), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, cand,
+                         p->h_signature_prescaler, F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p, F.ex_sig.p);
+      HIPCHK(hipGetLastError());
+    }
+    if (total > 0) HIPCHK(hipMemcpyAsync(sig.data(), F.ex_sig.p, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    int err = 0;
+    HIPCHK(hipMemcpyAsync(&err, h->err_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (err) return fail(TEB_AMD_ERR_CAPACITY, "candidate band needs more poses than max_poses");
+    return TEB_AMD_OK;
+  };
+  // tebs_.push_back(candidate) of every scene: the accepted scratch bands -> the next slots of the batch in one gather, with the
+  // defaults of a new TebOptimalPlanner, setVelocityStart / setVelocityGoalFree of their scene, and their entries of the map
+  auto accept_all = [&](const std::vector<int>& acc) -> int {
+    if (acc.empty()) return TEB_AMD_OK;
+    const int slot0 = h->B, cnt = (int)acc.size();
+    if (slot0 + cnt > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more bands than max_tebs");   // (excluded by the capacity rule)
+    std::vector<int> ones(cnt, 1), rot(cnt, TEB_AMD_ROT_NONE), hvg(cnt, free_goal_vel ? 0 : 1), zero(cnt, 0);
+    std::vector<double> vv(3 * (size_t)cnt, 0.0), z3(3 * (size_t)cnt, 0.0);
+    for (int k = 0; k < cnt; ++k) {
+      const int s = cscene[acc[k]];
+      if (start_vel) for (int j = 0; j < 3; ++j) vv[3 * k + j] = start_vel[3 * s + j];
+      F.band_scene[slot0 + k] = s;
+      of[s].push_back(slot0 + k);
+    }
+    HIPCHK(hipMemcpyAsync(h->has_vs.p + slot0, ones.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->has_vg.p + slot0, hvg.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->rotdir.p + slot0, rot.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->via_en.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));   // born without via-points
+    HIPCHK(hipMemcpyAsync(h->optimized.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->vs.p + 3 * (size_t)slot0, vv.data(), vv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->vg.p + 3 * (size_t)slot0, z3.data(), z3.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.scene_of.p + slot0, F.band_scene.data() + slot0, cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.ex_map.p, acc.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    h->B = slot0 + cnt;
+    hipLaunchKernelGGL(move_bands_kernel, dim3(cnt), dim3(kThreads), 0, h->stream, cand, batch_of(h), F.ex_map.p, slot0, 0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));   // the staging vectors live on this stack frame
+    return TEB_AMD_OK;
+  };
+  auto sig_of = [&](int k) { return sig.data() + soff[k]; };
+  std::vector<int> initial_idx(ns, -1);   // initial_plan_teb_ of every scene: position among the scene's bands
+  auto body = [&]() -> int {
+    // ---- 2. the initial plans as candidates: addAndInitNewTeb(*initial_plan_, ...), one launch ---------------------------------------
+    cscene.clear();
+    std::vector<int> off(1, 0);
+    std::vector<double> px, py, pyaw;
+    for (int s = 0; s < ns; ++s) {
+      const int np = plan_off[s + 1] - plan_off[s];
+      if (np <= 0 || (int)of[s].size() >= slots) continue;
+      px.insert(px.end(), plan_x + plan_off[s], plan_x + plan_off[s + 1]);
+      py.insert(py.end(), plan_y + plan_off[s], plan_y + plan_off[s + 1]);
+      pyaw.insert(pyaw.end(), plan_yaw + plan_off[s], plan_yaw + plan_off[s + 1]);
+      off.push_back((int)px.size());
+      cscene.push_back(s);
+    }
+    if (!cscene.empty()) {
+      const int count = (int)cscene.size();
+      HIPCHK(hipMemcpyAsync(F.ex_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_px.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_py.p, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_pyaw.p, pyaw.data(), pyaw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
+      hipLaunchKernelGGL(init_plan_batch_kernel, dim3(count), dim3(kThreads), 0, h->stream, cand, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_pyaw.p,
+                         c.max_vel_x, c.max_vel_theta, p->global_plan_overwrite_orientation, c.min_samples, p->allow_init_with_backwards_motion,
+                         h->err_flag.p);
+      HIPCHK(hipGetLastError());
+      if (int r = classify()) return r;
+      std::vector<int> acc;
+      for (int k = 0; k < count; ++k) {
+        const int s = cscene[k];
+        F.initial_class[s].assign(sig_of(k), sig_of(k) + ct[s].W); F.initial_class_mode[s] = mode;   // initial_plan_eq_class_
+        if (ct[s].add_if_new(sig_of(k))) { acc.push_back(k); initial_idx[s] = (int)of[s].size(); }
+      }
+      if (int r = accept_all(acc)) return r;
+    }
+    // ---- 3. vertices, on the host scene by scene; the scenes that return before their graph -------------------------------------------
+    struct Graph { int s; std::vector<double> vx, vy; GraphArgs ga; std::vector<std::vector<int>> adj; };
+    std::vector<Graph> graphs;
+    std::vector<int> at_goal;   // at their goal without a band: a line band (addAndInitNewTeb(start, goal, ...), hcp.cpp:358-384)
+    for (int s = 0; s < ns; ++s) {
+      if ((int)of[s].size() >= slots) continue;                                 // src/graph_search.cpp:99-100, 231-232
+      const double* st = start + 3 * s; const double* gl = goal + 3 * s;
+      const double dfx = gl[0] - st[0], dfy = gl[1] - st[1];
+      const double start_goal_dist = std::sqrt(dfx * dfx + dfy * dfy);
+      if (start_goal_dist < p->xy_goal_tolerance) {                             // :104-113, :237-246
+        if (of[s].empty()) at_goal.push_back(s);
+        continue;
+      }
+      graphs.emplace_back();
+      Graph& g = graphs.back();
+      g.s = s;
+      graph_vertices(F.tabs[s], st, gl, start_goal_dist, dist_to_obst, p, F.rnd[s],
+                     unit_samples ? unit_samples + (size_t)s * 2 * std::max(p->roadmap_graph_no_samples, 0) : nullptr, g.vx, g.vy, g.ga);
+      g.ga.N = (int)g.vx.size();
+      if (n_vertices) n_vertices[s] = g.ga.N;
+    }
+    // ---- 4. edges: every graph in one launch, one download --------------------------------------------------------------------------
+    if (!graphs.empty()) {
+      size_t nv = 0, na = 0;
+      long long most = 0;
+      for (const Graph& g : graphs) { nv += g.vx.size(); na += g.vx.size() * g.vx.size(); most = std::max(most, (long long)g.ga.N * g.ga.N); }
+      if (F.ex_gvx.n < nv) { F.ex_gvx.free(); F.ex_gvy.free(); HIPCHK(F.ex_gvx.alloc(nv)); HIPCHK(F.ex_gvy.alloc(nv)); }
+      if (F.ex_gadj.n < na) { F.ex_gadj.free(); HIPCHK(F.ex_gadj.alloc(na)); }
+      std::vector<double> allx, ally;
+      std::vector<GraphFleetRec> recs(graphs.size());
+      size_t vo = 0, ao = 0;
+      for (size_t i = 0; i < graphs.size(); ++i) {
+        Graph& g = graphs[i];
+        allx.insert(allx.end(), g.vx.begin(), g.vx.end()); ally.insert(ally.end(), g.vy.begin(), g.vy.end());
+        g.ga.gx = F.ex_gvx.p + vo; g.ga.gy = F.ex_gvy.p + vo; g.ga.adj = F.ex_gadj.p + ao;
+        recs[i].g = g.ga; recs[i].scene = g.s;
+        vo += g.vx.size(); ao += g.vx.size() * g.vx.size();
+      }
+      HIPCHK(hipMemcpyAsync(F.ex_gvx.p, allx.data(), nv * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_gvy.p, ally.data(), nv * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_rec.p, recs.data(), recs.size() * sizeof(GraphFleetRec), hipMemcpyHostToDevice, h->stream));
+      hipLaunchKernelGGL(graph_edges_fleet_kernel, dim3((unsigned)((most + kThreads - 1) / kThreads), (unsigned)graphs.size()), dim3(kThreads), 0,
+                         h->stream, F.scenes.p, F.ex_rec.p);
+      HIPCHK(hipGetLastError());
+      std::vector<unsigned char> adjm(na);
+      HIPCHK(hipMemcpyAsync(adjm.data(), F.ex_gadj.p, na, hipMemcpyDeviceToHost, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+      ao = 0;
+      for (Graph& g : graphs) {
+        const int N = g.ga.N;
+        g.adj.assign(N, {});
+        for (int i = 0; i < N; ++i)
+          for (int j = 0; j < N; ++j) if (adjm[ao + (size_t)i * N + j]) g.adj[i].push_back(j);   // add_edge order of the double loop
+        F.g_vx[g.s] = g.vx; F.g_vy[g.s] = g.vy;
+        F.g_adj[g.s].assign(adjm.begin() + ao, adjm.begin() + ao + (size_t)N * N);
+        ao += (size_t)N * N;
+      }
+    }
+    // ---- 5. rounds: up to q paths of every scene that has room and paths left; init, classify, first come first served per scene -------
+    std::vector<double> orient(2 * (size_t)ns, 0.0);
+    for (int s = 0; s < ns; ++s) { orient[2 * s] = start[3 * s + 2]; orient[2 * s + 1] = goal[3 * s + 2]; }
+    if (!graphs.empty()) HIPCHK(hipMemcpyAsync(F.ex_orient.p, orient.data(), orient.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    std::vector<PathEnumerator> en;
+    en.reserve(graphs.size());
+    for (Graph& g : graphs) {
+      en.emplace_back(g.adj, 0, g.ga.N - 1);
+      if (max_paths > 0) en.back().max_expansions = max_paths * 10000;
+    }
+    std::vector<int64_t> examined(graphs.size(), 0);
+    std::vector<char> more(graphs.size(), 1);
+    std::vector<int> path, cgraph;
+    for (;;) {
+      off.assign(1, 0); px.clear(); py.clear(); cscene.clear(); cgraph.clear();
+      for (size_t i = 0; i < graphs.size(); ++i) {
+        const int s = graphs[i].s;
+        if (!more[i] || (int)of[s].size() >= slots) continue;
+        int count = 0;
+        while (count < q && (max_paths <= 0 || examined[i] + count < max_paths)) {
+          if (!en[i].next(path)) { more[i] = 0; break; }
+          if ((int)path.size() > h->stride + 1) return fail(TEB_AMD_ERR_CAPACITY, "a start-goal path has more vertices than a band has poses (max_poses)");
+          for (int v : path) { px.push_back(graphs[i].vx[v]); py.push_back(graphs[i].vy[v]); }
+          off.push_back((int)px.size());
+          cscene.push_back(s); cgraph.push_back((int)i);
+          ++count;
+        }
+        if (max_paths > 0 && examined[i] + count >= max_paths) more[i] = 0;
+      }
+      const int count = (int)cscene.size();
+      if (count == 0) break;
+      HIPCHK(hipMemcpyAsync(F.ex_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_px.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_py.p, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(F.ex_scene.p, cscene.data(), count * sizeof(int), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
+      hipLaunchKernelGGL(init_path_fleet_kernel, dim3(count), dim3(kThreads), 0, h->stream, cand, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_scene.p,
+                         F.ex_orient.p, c.max_vel_x, c.acc_lim_x, c.min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
+      HIPCHK(hipGetLastError());
+      if (int r = classify()) return r;
+      std::vector<int> acc;
+      for (int k = 0; k < count; ++k) {   // the candidates of a scene lie together, in path order
+        const int s = cscene[k], i = cgraph[k];
+        int pending = 0;
+        for (int a : acc) pending += cscene[a] == s;
+        if ((int)of[s].size() + pending >= slots) continue;
+        ++examined[i];
+        if (ct[s].add_if_new(sig_of(k))) acc.push_back(k);
+      }
+      if (int r = accept_all(acc)) return r;
+    }
+    for (size_t i = 0; i < graphs.size(); ++i)
+      if (n_paths) n_paths[graphs[i].s] = (int32_t)std::min<int64_t>(examined[i], std::numeric_limits<int32_t>::max());
+    // ---- 6. the scenes at their goal without a band: their line bands in one launch ---------------------------------------------------
+    if (!at_goal.empty()) {
+      const int count = (int)at_goal.size();
+      cscene = at_goal;
+      std::vector<double> pose(6 * (size_t)count);
+      for (int k = 0; k < count; ++k)
+        for (int j = 0; j < 3; ++j) { pose[6 * k + j] = start[3 * at_goal[k] + j]; pose[6 * k + 3 + j] = goal[3 * at_goal[k] + j]; }
+      HIPCHK(hipMemcpyAsync(F.ex_line.p, pose.data(), pose.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
+      hipLaunchKernelGGL(init_line_batch_kernel, dim3(count), dim3(kThreads), 0, h->stream, cand, F.ex_line.p, 0.0, c.max_vel_x, c.min_samples,
+                         p->allow_init_with_backwards_motion, h->err_flag.p);
+      HIPCHK(hipGetLastError());
+      if (int r = classify()) return r;
+      std::vector<int> acc;
+      for (int k = 0; k < count; ++k) if (ct[at_goal[k]].add_if_new(sig_of(k))) acc.push_back(k);
+      if (int r = accept_all(acc)) return r;
+    }
+    return TEB_AMD_OK;
+  };
+  rc = body();
+  if (n_total) *n_total = h->B;
+  for (int s = 0; s < ns; ++s) if (n_bands) n_bands[s] = (int)of[s].size();
+  if (rc) return rc;
+  // ---- 7. getInitialPlanTEB (:495-536) and updateReferenceTrajectoryViaPoints (:286-315) scene by scene, one upload of via_en ---------
   const int B = h->B;
-  if (new_best) *new_best = -1;
-  if (n_kept) *n_kept = 0;
-  if (B <= 0) return TEB_AMD_OK;
+  std::vector<int> ve(std::max(B, 1), 0);
+  bool any_rule = false;
+  if (B > 0) HIPCHK(hipMemcpyAsync(ve.data(), h->via_en.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  for (int s = 0; s < ns; ++s) {
+    const ClassTable& t = ct[s];
+    const int Bs = (int)of[s].size();
+    const bool have_initial_class = F.initial_class_mode[s] == mode && (int)F.initial_class[s].size() == t.W && t.valid(F.initial_class[s].data());
+    if (initial_idx[s] < 0 && have_initial_class)
+      for (int b = 0; b < Bs && b < (int)t.classes.size(); ++b)
+        if (t.equal(t.classes[b].data(), F.initial_class[s].data())) { initial_idx[s] = b; break; }
+    if (initial_plan_teb) initial_plan_teb[s] = initial_idx[s];
+    const int np = plan_off[s + 1] - plan_off[s];
+    if (Bs > 0 && !((!p->viapoints_all_candidates && np <= 0) || F.via_count[s] <= 0 || c.weight_viapoint <= 0)) {
+      any_rule = true;
+      for (int b = 0; b < Bs; ++b)
+        ve[of[s][b]] = p->viapoints_all_candidates ? 1 : (have_initial_class && b < (int)t.classes.size() && t.equal(F.initial_class[s].data(), t.classes[b].data()));
+    }
+  }
+  if (any_rule) {
+    HIPCHK(hipMemcpyAsync(h->via_en.p, ve.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  return TEB_AMD_OK;
+}
+
+int teb_amd_get_exploration_graph_per_scene(teb_amd_handle_t* h, int32_t scene, double* vx, double* vy, unsigned char* adjacency,
+                                            int32_t capacity_vertices, int32_t* n_vertices) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_get_exploration_graph_per_scene"))) return rc;
+  auto& F = h->fleet;
+  if (scene < 0 || scene >= F.n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_exploration_graph_per_scene: scene out of range");
+  const int N = (int)F.g_vx[scene].size();
+  if (n_vertices) *n_vertices = N;
+  if (N == 0 || (!vx && !vy && !adjacency)) return TEB_AMD_OK;
+  if (capacity_vertices < N) return fail(TEB_AMD_ERR_CAPACITY, "graph has more vertices than capacity_vertices");
+  if (vx) std::copy(F.g_vx[scene].begin(), F.g_vx[scene].end(), vx);
+  if (vy) std::copy(F.g_vy[scene].begin(), F.g_vy[scene].end(), vy);
+  if (adjacency) std::copy(F.g_adj[scene].begin(), F.g_adj[scene].end(), adjacency);
+  return TEB_AMD_OK;
+}
+
+namespace {
+// The bands map[0 .. K) (indices into the batch) become bands 0 .. K - 1, with their attributes, their signatures of the single scene
+// and their entries of the band -> scene map; B = K afterwards.
+int compact_by_map(teb_amd_handle* h, const std::vector<int>& map) {
+  const int B = h->B;
   if (!h->tmp_ready) {
     const size_t BS = (size_t)h->max_tebs * h->stride;
     bool ok = true;
@@ -2649,14 +3069,7 @@ int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best
     if (!ok) return fail(TEB_AMD_ERR_HIP, "compaction scratch allocation failed");
     h->tmp_ready = true;
   }
-  std::vector<int> order(B), map;
-  for (int b = 0; b < B; ++b) order[b] = b;
-  const bool has_best = best >= 0 && best < B;
-  if (has_best) std::swap(order[0], order[best]);   // std::iter_swap(tebs_.begin(), it_best_teb)
-  for (int k = 0; k < B; ++k) if (keep[order[k]]) map.push_back(order[k]);
   const int K = (int)map.size();
-  if (has_best && keep[best] && new_best) *new_best = 0;
-  if (n_kept) *n_kept = K;
   bool identity = true;
   for (int k = 0; k < K; ++k) if (map[k] != k) identity = false;
   if (!identity && K > 0) {
@@ -2702,6 +3115,55 @@ int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best
   }
   h->B = K;
   h->consumers_valid = false; h->nmax_known = -1;
+  return TEB_AMD_OK;
+}
+}  // namespace
+
+int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best, int32_t* n_kept, int32_t* new_best) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (!keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null keep");
+  const int B = h->B;
+  if (new_best) *new_best = -1;
+  if (n_kept) *n_kept = 0;
+  if (B <= 0) return TEB_AMD_OK;
+  std::vector<int> order(B), map;
+  for (int b = 0; b < B; ++b) order[b] = b;
+  const bool has_best = best >= 0 && best < B;
+  if (has_best) std::swap(order[0], order[best]);   // std::iter_swap(tebs_.begin(), it_best_teb)
+  for (int k = 0; k < B; ++k) if (keep[order[k]]) map.push_back(order[k]);
+  if ((rc = compact_by_map(h, map))) return rc;
+  if (has_best && keep[best] && new_best) *new_best = 0;
+  if (n_kept) *n_kept = (int)map.size();
+  return TEB_AMD_OK;
+}
+
+int teb_amd_compact_bands_per_scene(teb_amd_handle_t* h, const int32_t* keep, const int32_t* best, int32_t* n_kept, int32_t* new_best) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_compact_bands_per_scene"))) return rc;
+  if (!keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null keep");
+  const int B = h->B, ns = h->fleet.n_scenes;
+  if (new_best) std::fill(new_best, new_best + ns, -1);
+  if (n_kept) *n_kept = 0;
+  if (B <= 0) return TEB_AMD_OK;
+  if ((rc = check_band_scenes(h, B))) return rc;
+  if ((rc = check_best_per_scene(h, best, B, "teb_amd_compact_bands_per_scene"))) return rc;
+  // the gather map: std::iter_swap(tebs_.begin(), it_best_teb) inside every scene, then the kept bands in the resulting order
+  std::vector<int> order(B), first(ns, -1), map;
+  for (int b = 0; b < B; ++b) { order[b] = b; if (first[h->fleet.band_scene[b]] < 0) first[h->fleet.band_scene[b]] = b; }
+  if (best)
+    for (int s = 0; s < ns; ++s) if (best[s] >= 0) std::swap(order[first[s]], order[best[s]]);
+  std::vector<int> nb(ns, -1);
+  for (int k = 0; k < B; ++k)
+    if (keep[order[k]]) {
+      const int b = order[k], s = h->fleet.band_scene[b];
+      if (best && best[s] == b) nb[s] = (int)map.size();
+      map.push_back(b);
+    }
+  if ((rc = compact_by_map(h, map))) return rc;
+  if (new_best) std::copy(nb.begin(), nb.end(), new_best);
+  if (n_kept) *n_kept = (int)map.size();
   return TEB_AMD_OK;
 }
 
@@ -3216,6 +3678,14 @@ int teb_amd_debug_mcu_flags(teb_amd_handle_t* h, int32_t flags) {
   return TEB_AMD_OK;
 }
 
+
+int teb_amd_debug_set_explore_quota(teb_amd_handle_t* h, int32_t quota) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (quota < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "negative quota");
+  h->explore_quota = quota;
+  return TEB_AMD_OK;
+}
 
 int teb_amd_debug_assoc_overflow(teb_amd_handle_t* h, int32_t* flags) {
   int rc = check_handle(h);

@@ -4,7 +4,9 @@
 //                          then Obstacle::checkLineIntersection against every obstacle -> adjacency byte matrix [N * N].
 //                          One lane per pair; the obstacle index is wave-uniform, so the obstacle table arrives through scalar loads.
 //                          N^2 * M segment tests: 272 * M for the 17-vertex roadmap, 10^6 * M for a 500-obstacle keypoint graph.
+//   graph_edges_fleet_kernel  the same for the graphs of many scenes in one launch, each against its own obstacle table.
 //   init_path_batch_kernel the template initTrajectoryToGoal(path...) for a chunk of candidate paths, one workgroup per path.
+//   init_path_fleet_kernel the same for the candidates of many scenes (orientation of start and goal per scene).
 //   move_bands_kernel      gathers bands (and their per-band attributes) between strip sets: candidate -> batch, compaction.
 // fp64, one IEEE operation per source operation of the reference (the library is built with -ffp-contract=off).
 #pragma once
@@ -59,8 +61,8 @@ __device__ __forceinline__ void normalize2(double& x, double& y) {
 }
 
 // src/graph_search.cpp:156-213 (keypoint graph) and :301-333 (roadmap): the edge insertion double loop
-__global__ void __launch_bounds__(kThreads) graph_edges_kernel(const SceneDev sc, const GraphArgs g) {
-  const long long idx = (long long)blockIdx.x * kThreads + threadIdx.x;
+// The body is shared with the fleet form (graph_edges_fleet_kernel): pair idx of graph g against the obstacles of scene sc.
+__device__ __forceinline__ void graph_edges_body(const SceneDev& sc, const GraphArgs& g, const long long idx) {
   const int N = g.N;
   if (idx >= (long long)N * N) return;
   const int i = (int)(idx / N), j = (int)(idx % N);
@@ -85,6 +87,23 @@ __global__ void __launch_bounds__(kThreads) graph_edges_kernel(const SceneDev sc
     }
   }
   g.adj[idx] = edge ? 1 : 0;
+}
+__global__ void __launch_bounds__(kThreads) graph_edges_kernel(const SceneDev sc, const GraphArgs g) {
+  graph_edges_body(sc, g, (long long)blockIdx.x * kThreads + threadIdx.x);
+}
+// The graphs of many scenes in one launch: grid = (blocks over the largest N^2, graphs). blockIdx.y selects a record - a graph and
+// the scene it is tested against; record and obstacle table are uniform over the workgroup, so both arrive through scalar loads. The
+// vertices and the adjacency bytes of the graphs lie one after the other in one buffer each: g.gx / g.gy / g.adj of a record point at
+// its own part. A workgroup beyond its graph's N^2 returns before any ballot. The values are those of graph_edges_kernel on the scene alone.
+struct GraphFleetRec {
+  GraphArgs g;
+  int scene;   // < n_scenes
+};
+__global__ void __launch_bounds__(kThreads) graph_edges_fleet_kernel(const SceneDev* __restrict__ scenes, const GraphFleetRec* __restrict__ recs) {
+  const GraphFleetRec r = recs[blockIdx.y];
+  if ((long long)blockIdx.x * kThreads >= (long long)r.g.N * r.g.N) return;
+  const SceneDev sc = scenes[r.scene];
+  graph_edges_body(sc, r.g, (long long)blockIdx.x * kThreads + threadIdx.x);
 }
 
 // template initTrajectoryToGoal(path_start, path_end, fun_position, ...), timed_elastic_band.hpp:46-183, for one band; called by
@@ -147,6 +166,17 @@ __global__ void init_path_batch_kernel(BatchDev bt, const int* off, const double
   const int k = blockIdx.x;
   const int o = off[k];
   init_path_band(strip_of(bt, k), off[k + 1] - o, px + o, py + o, max_vel_x, 1, max_acc_x, 1, start_orientation, 1, goal_orientation,
+                 min_samples, guess_backwards, err);
+}
+
+// the candidates of many scenes: candidate k belongs to scene cand_scene[k] and takes that scene's start / goal orientation
+// (orient [n_scenes][2])
+__global__ void init_path_fleet_kernel(BatchDev bt, const int* off, const double* px, const double* py, const int* cand_scene,
+                                       const double* orient, double max_vel_x, double max_acc_x, int min_samples, int guess_backwards,
+                                       int* err) {
+  const int k = blockIdx.x;
+  const int o = off[k], s = cand_scene[k];
+  init_path_band(strip_of(bt, k), off[k + 1] - o, px + o, py + o, max_vel_x, 1, max_acc_x, 1, orient[2 * s], 1, orient[2 * s + 1],
                  min_samples, guess_backwards, err);
 }
 

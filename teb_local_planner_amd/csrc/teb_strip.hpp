@@ -65,9 +65,9 @@ __device__ inline int init_tail(StripDev s, int n, double gx, double gy, double 
 }
 
 // initTrajectoryToGoal(start, goal, diststep, max_vel_x, min_samples, guess_backwards_motion), :325-377. One workgroup.
-__global__ void init_line_kernel(BatchDev bt, int b, double sx, double sy, double sth, double gx, double gy, double gth,
-                                 double diststep, double max_vel_x, int min_samples, int guess_backwards, int* err) {
-  StripDev s = strip_of(bt, b);
+// The body is shared with the batch form (init_line_batch_kernel): every lane of the workgroup that owns the band calls it.
+__device__ __forceinline__ void init_line_band(StripDev s, double sx, double sy, double sth, double gx, double gy, double gth,
+                                               double diststep, double max_vel_x, int min_samples, int guess_backwards, int* err) {
   double timestep = 0.1;
   int n = 1;
   if (threadIdx.x == 0) { s.x[0] = sx; s.y[0] = sy; s.th[0] = sth; }
@@ -98,13 +98,23 @@ __global__ void init_line_kernel(BatchDev bt, int b, double sx, double sy, doubl
     if (r < 0) { *err = 1; *s.n = 0; } else *s.n = r;
   }
 }
+__global__ void init_line_kernel(BatchDev bt, int b, double sx, double sy, double sth, double gx, double gy, double gth,
+                                 double diststep, double max_vel_x, int min_samples, int guess_backwards, int* err) {
+  init_line_band(strip_of(bt, b), sx, sy, sth, gx, gy, gth, diststep, max_vel_x, min_samples, guess_backwards, err);
+}
+// one workgroup per band k of bt: start (x, y, theta) and goal (x, y, theta) of the band in pose[6 * k .. 6 * k + 6)
+__global__ void init_line_batch_kernel(BatchDev bt, const double* pose, double diststep, double max_vel_x, int min_samples,
+                                       int guess_backwards, int* err) {
+  const int k = blockIdx.x;
+  const double* q = pose + 6 * (size_t)k;
+  init_line_band(strip_of(bt, k), q[0], q[1], q[2], q[3], q[4], q[5], diststep, max_vel_x, min_samples, guess_backwards, err);
+}
 
 // initTrajectoryToGoal(plan, max_vel_x, max_vel_theta, estimate_orient, min_samples, guess_backwards_motion), :380-452.
-// plan = np positions + yaw staged in px/py/pyaw (device). One workgroup.
-__global__ void init_plan_kernel(BatchDev bt, int b, int np, const double* px, const double* py, const double* pyaw,
-                                 double max_vel_x, double max_vel_theta, int estimate_orient, int min_samples,
-                                 int guess_backwards, int* err) {
-  StripDev s = strip_of(bt, b);
+// plan = np positions + yaw staged in px/py/pyaw (device). One workgroup. The body is shared with the batch form.
+__device__ __forceinline__ void init_plan_band(StripDev s, int np, const double* px, const double* py, const double* pyaw,
+                                               double max_vel_x, double max_vel_theta, int estimate_orient, int min_samples,
+                                               int guess_backwards, int* err) {
   const double sx = px[0], sy = py[0], sth = pyaw[0];
   const double gx = px[np - 1], gy = py[np - 1], gth = pyaw[np - 1];
   const bool backwards = guess_backwards && ((gx - sx) * cos(sth) + (gy - sy) * sin(sth)) < 0;
@@ -129,6 +139,20 @@ __global__ void init_plan_kernel(BatchDev bt, int b, int np, const double* px, c
     const int r = init_tail<1>(s, n, gx, gy, gth, max_vel_x, max_vel_theta, 0.0, min_samples);
     if (r < 0) { *err = 1; *s.n = 0; } else *s.n = r;
   }
+}
+__global__ void init_plan_kernel(BatchDev bt, int b, int np, const double* px, const double* py, const double* pyaw,
+                                 double max_vel_x, double max_vel_theta, int estimate_orient, int min_samples,
+                                 int guess_backwards, int* err) {
+  init_plan_band(strip_of(bt, b), np, px, py, pyaw, max_vel_x, max_vel_theta, estimate_orient, min_samples, guess_backwards, err);
+}
+// one workgroup per plan k: poses [off[k], off[k + 1]) of px / py / pyaw -> band k of bt
+__global__ void init_plan_batch_kernel(BatchDev bt, const int* off, const double* px, const double* py, const double* pyaw,
+                                       double max_vel_x, double max_vel_theta, int estimate_orient, int min_samples,
+                                       int guess_backwards, int* err) {
+  const int k = blockIdx.x;
+  const int o = off[k];
+  init_plan_band(strip_of(bt, k), off[k + 1] - o, px + o, py + o, pyaw + o, max_vel_x, max_vel_theta, estimate_orient, min_samples,
+                 guess_backwards, err);
 }
 
 // updateAndPruneTEB, :555-597. One workgroup per band (blockIdx.x + b0). Dynamic LDS: 4 * stride doubles.

@@ -124,6 +124,14 @@ def lib():
             L.teb_amd_compute_h_signatures_per_scene.argtypes = [vp, d, _abi.p_f64, C.c_int64, _abi.p_i32, C.POINTER(C.c_int64)]
             L.teb_amd_filter_equivalence_classes_per_scene.argtypes = [vp, d, _abi.p_i32, i32, _abi.p_i32, _abi.p_i32, _abi.p_i32]
             L.teb_amd_filter_detours_per_scene.argtypes = [vp, C.POINTER(_abi.HcpParams), _abi.p_i32, _abi.p_i32]
+        if hasattr(L, "teb_amd_explore_candidates_per_scene"):   # candidate exploration per scene of a fleet batch
+            L.teb_amd_explore_candidates_per_scene.argtypes = [vp, C.POINTER(_abi.HcpParams), _abi.p_f64, _abi.p_f64, d, _abi.p_f64, i32, _abi.p_i32,
+                                                               _abi.p_f64, C.c_int64, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_i32,
+                                                               _abi.p_f64, _abi.p_f64, _abi.p_f64, _abi.p_i32]
+            L.teb_amd_get_exploration_graph_per_scene.argtypes = [vp, i32, _abi.p_f64, _abi.p_f64, C.POINTER(C.c_ubyte), i32, _abi.p_i32]
+            L.teb_amd_compact_bands_per_scene.argtypes = [vp, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_i32]
+            L.teb_amd_get_band_scenes.argtypes = [vp, _abi.p_i32, i32, _abi.p_i32]
+            L.teb_amd_debug_set_explore_quota.argtypes = [vp, i32]
         _LIB = L
     return _LIB
 
@@ -183,6 +191,7 @@ class TebBatchSolver:
         _chk(lib().teb_amd_set_scenes(self._h, p.n, p.obstacles, _abi._ptr(p.via_count, C.c_int32), _abi._ptr(p.via_x, C.c_double),
                                       _abi._ptr(p.via_y, C.c_double)), "teb_amd_set_scenes")
         self._widest_scene = max(len(t) for t in tables)
+        self._n_scenes = len(tables)
 
     def set_band_scenes(self, scene_of):
         a = _abi.i32(scene_of)
@@ -190,6 +199,7 @@ class TebBatchSolver:
 
     def clear_scenes(self):
         _chk(lib().teb_amd_clear_scenes(self._h), "teb_amd_clear_scenes")
+        self._n_scenes = 0
 
     def scene_count(self):
         n = C.c_int32(0)
@@ -254,6 +264,87 @@ class TebBatchSolver:
         _chk(lib().teb_amd_filter_detours_per_scene(self._h, C.byref(p), _abi._ptr(bp, C.c_int32), _abi._ptr(keep, C.c_int32)),
              "teb_amd_filter_detours_per_scene")
         return keep
+
+    def band_scenes(self):
+        """[B] scene of every resident band (the map of set_band_scenes as compaction and exploration moved and extended it)."""
+        self._sync_count()
+        a = np.zeros(max(self.count, 1), np.int32); n = C.c_int32(0)
+        _chk(lib().teb_amd_get_band_scenes(self._h, _abi._ptr(a, C.c_int32), len(a), C.byref(n)), "teb_amd_get_band_scenes")
+        return a[:n.value].copy()
+
+    def _per_scene(self, what, name, a, width=None):
+        """`a` as a contiguous array with one row per scene set by set_scenes, or None; ValueError before the library is entered."""
+        ns = getattr(self, "_n_scenes", 0)
+        if a is None:
+            return None
+        if len(a) != ns:
+            raise ValueError("%s: %d %s for %d scenes" % (what, len(a), name, ns))
+        if width is None:
+            return _abi.i32(a)
+        out = np.ascontiguousarray(np.asarray(a, np.float64).reshape(ns, -1))
+        if out.shape[1] != width:
+            raise ValueError("%s: %s have %d values per scene, not %d" % (what, name, out.shape[1], width))
+        return out
+
+    def explore_candidates_per_scene(self, starts, goals, dist_to_obst=None, start_vels=None, free_goal_vel=False, best=None,
+                                     unit_samples=None, max_paths=0, params=None, initial_plans=None):
+        """Fleet mode: exploreEquivalenceClassesAndInitTebs of every scene with its own start / goal / start velocity / best band /
+        unit samples / initial plan ((x, y, yaw) arrays or None per scene): dict(n_total, n_bands [n_scenes], n_vertices, n_paths,
+        initial_plan_teb - the position among the bands of the scene, or -1). New bands are appended to the batch."""
+        what = "explore_candidates_per_scene"
+        ns = getattr(self, "_n_scenes", 0)
+        p = params if params is not None else self.cfg.hcp_params()
+        if starts is None or goals is None:
+            raise ValueError(what + ": starts and goals are required")
+        st = self._per_scene(what, "starts", starts, 3); gl = self._per_scene(what, "goals", goals, 3)
+        sv = self._per_scene(what, "start velocities", start_vels, 3)
+        bp = self._per_scene(what, "best bands", best)
+        us = self._per_scene(what, "unit sample rows", unit_samples, 2 * max(int(p.roadmap_graph_no_samples), 0))
+        pc = px = py = pyaw = None
+        if initial_plans is not None:
+            if len(initial_plans) != ns:
+                raise ValueError("%s: %d initial plans for %d scenes" % (what, len(initial_plans), ns))
+            pc = _abi.i32([0 if q is None else len(q[0]) for q in initial_plans])
+            cat = lambda j: _abi.f64(np.concatenate([np.asarray(q[j], np.float64).ravel() for q in initial_plans if q is not None] + [np.zeros(1)]))
+            px, py, pyaw = cat(0), cat(1), cat(2)
+        dist_to_obst = self.cfg.obstacles.min_obstacle_dist if dist_to_obst is None else dist_to_obst
+        nt = C.c_int32(0)
+        nb = np.zeros(max(ns, 1), np.int32); nv = nb.copy(); npth = nb.copy(); ipt = np.full(max(ns, 1), -1, np.int32)
+        D = lambda a: _abi._ptr(a, C.c_double)
+        I = lambda a: _abi._ptr(a, C.c_int32)
+        _chk(lib().teb_amd_explore_candidates_per_scene(self._h, C.byref(p), D(st), D(gl), float(dist_to_obst), D(sv), int(bool(free_goal_vel)),
+                                                        I(bp), D(us), int(max_paths), C.byref(nt), I(nb), I(nv), I(npth), I(pc), D(px), D(py),
+                                                        D(pyaw), I(ipt)), "teb_amd_explore_candidates_per_scene")
+        self.count = nt.value
+        return dict(n_total=nt.value, n_bands=nb[:ns].copy(), n_vertices=nv[:ns].copy(), n_paths=npth[:ns].copy(),
+                    initial_plan_teb=ipt[:ns].copy())
+
+    def exploration_graph_per_scene(self, s):
+        """(vertices [N, 2], adjacency [N, N] uint8) of scene s in the last explore_candidates_per_scene call (N = 0: no graph)."""
+        nv = C.c_int32(0)
+        _chk(lib().teb_amd_get_exploration_graph_per_scene(self._h, int(s), None, None, None, 0, C.byref(nv)),
+             "teb_amd_get_exploration_graph_per_scene")
+        N = nv.value
+        vx = np.zeros(max(N, 1)); vy = np.zeros(max(N, 1)); adj = np.zeros((max(N, 1), max(N, 1)), np.uint8)
+        if N:
+            _chk(lib().teb_amd_get_exploration_graph_per_scene(self._h, int(s), _abi._ptr(vx, C.c_double), _abi._ptr(vy, C.c_double),
+                                                               adj.ctypes.data_as(C.POINTER(C.c_ubyte)), N, C.byref(nv)),
+                 "teb_amd_get_exploration_graph_per_scene")
+        return np.stack([vx[:N], vy[:N]], 1), adj[:N, :N]
+
+    def compact_bands_per_scene(self, keep, best=None):
+        """Keeps the bands with keep[b] != 0, every scene's best band first among the bands of its scene: (n_kept, new_best [n_scenes])."""
+        bp = self._per_scene("compact_bands_per_scene", "best bands", best)
+        keep = _abi.i32(keep)
+        ns = getattr(self, "_n_scenes", 0)
+        nk = C.c_int32(0); nb = np.full(max(ns, 1), -1, np.int32)
+        _chk(lib().teb_amd_compact_bands_per_scene(self._h, _abi._ptr(keep, C.c_int32), _abi._ptr(bp, C.c_int32), C.byref(nk),
+                                                   _abi._ptr(nb, C.c_int32)), "teb_amd_compact_bands_per_scene")
+        self.count = nk.value
+        return nk.value, nb[:ns].copy()
+
+    def debug_set_explore_quota(self, q):
+        _chk(lib().teb_amd_debug_set_explore_quota(self._h, int(q)), "teb_amd_debug_set_explore_quota")
 
     # -- state ---------------------------------------------------------------------------------------
     def upload(self, batch):
@@ -938,6 +1029,160 @@ class TebFleetPlanner:
 
     def pose_counts(self):
         return self._solver.pose_counts()
+
+
+class FleetHomotopyClassPlanner:
+    """HomotopyClassPlanner::plan() of every robot of a homogeneous fleet on ONE handle: robot r is scene r, its candidates are the bands
+    the band -> scene map gives it. A tick is set_config, set_scenes, updateAllTEBs per robot, then renewAndAnalyzeOldTebs
+    (h_signatures_per_scene, filter_equivalence_classes_per_scene, filter_detours_per_scene, compact_bands_per_scene),
+    explore_candidates_per_scene, one optimize over all bands and select_best_per_scene with switching_blocking_period per robot.
+    Every robot's bands end with the bits of a HomotopyClassPlanner of its own whose handle follows the fleet contract of
+    include/teb_amd.h. best_teb_ / initial_plan_teb_ [n_robots] are band indices of the batch (-1: none). updateAndPruneTEB is one call
+    per band in this version; randomlyDropTebs is not carried over (selection_dropping_probability > 0: NotImplementedError)."""
+
+    def __init__(self, cfg, n_robots, max_tebs=None, max_poses=None, max_obstacles=256, max_obstacle_vertices=256, max_via_points=64,
+                 device=0, stream=None, options=None):
+        if cfg.hcp.selection_dropping_probability > 0:
+            raise NotImplementedError("FleetHomotopyClassPlanner: randomlyDropTebs (selection_dropping_probability > 0) is not available per scene")
+        self.cfg_ = cfg
+        self.n_robots = int(n_robots)
+        self.solver = TebBatchSolver(cfg, max_tebs or self.n_robots * max(cfg.hcp.max_number_classes, 1), max_poses or 224, max(max_obstacles, 1),
+                                     max(max_obstacle_vertices, 1), max(max_via_points, 1), device=device, stream=stream, options=options)
+        self.best_teb_ = np.full(self.n_robots, -1, np.int32)
+        self.initial_plan_teb_ = np.full(self.n_robots, -1, np.int32)
+        self.last_results = None
+        self.last_exploration = None
+        self._goal = [None] * self.n_robots
+        self._last_switch = [0.0] * self.n_robots
+
+    def bands_of(self, r):
+        """band indices of robot r, in band order"""
+        return [int(b) for b in np.nonzero(self.solver.band_scenes() == r)[0]] if self.solver.count else []
+
+    # ---- updateAllTEBs (src/homotopy_class_planner.cpp:539-562) robot by robot --------------------------------------------------------
+    def updateAllTEBs(self, starts, goals, start_vels=None):
+        import math
+        s, t = self.solver, self.cfg_.trajectory
+        if s.count > 0:
+            scene_of = s.band_scenes()
+            keep = np.ones(s.count, np.int32)
+            for r in range(self.n_robots):
+                if self._goal[r] is None or not (scene_of == r).any():
+                    continue
+                d = math.hypot(goals[r][0] - self._goal[r][0], goals[r][1] - self._goal[r][1])
+                a = abs((goals[r][2] - self._goal[r][2] + math.pi) % (2 * math.pi) - math.pi)
+                if d >= t.force_reinit_new_goal_dist or a >= t.force_reinit_new_goal_angular:
+                    keep[scene_of == r] = 0                       # tebs_.clear() of that robot only
+                    self.best_teb_[r] = -1
+            if not keep.all():
+                at = np.cumsum(keep) - 1                          # the other robots' bands keep their order
+                self.best_teb_ = np.array([at[b] if b >= 0 else -1 for b in self.best_teb_], np.int32)
+                s.compact_bands_per_scene(keep, None)
+        if s.count > 0:
+            scene_of = s.band_scenes()
+            for b in range(s.count):                              # one call per band in this version
+                r = int(scene_of[b])
+                s.update_and_prune(starts[r], goals[r], t.min_samples, b=b)
+                if start_vels is not None and start_vels[r] is not None:
+                    s.set_velocity_start(start_vels[r], True, b=b)
+        self._goal = [tuple(g) for g in goals]
+
+    # ---- exploreEquivalenceClassesAndInitTebs (:318-340) of every robot ---------------------------------------------------------------
+    def exploreEquivalenceClassesAndInitTebs(self, starts, goals, dist_to_obst, start_vels=None, free_goal_vel=False, initial_plans=None):
+        s, h = self.solver, self.cfg_.hcp
+        best = self.best_teb_
+        if s.count > 0:
+            s.h_signatures_per_scene(h.h_signature_prescaler, values=False)
+            keep, _, _ = s.filter_equivalence_classes_per_scene(h.h_signature_threshold, best, h.max_number_plans_in_current_class)
+            if h.delete_detours_backwards:
+                keep = s.filter_detours_per_scene(keep, best)
+            _, best = s.compact_bands_per_scene(keep, best)
+        self.best_teb_ = np.asarray(best, np.int32).copy()
+        sv = None
+        if start_vels is not None and any(v is not None for v in start_vels):
+            sv = [(0.0, 0.0, 0.0) if v is None else v for v in start_vels]   # a new band's default: fixed zero start velocity
+        self.last_exploration = s.explore_candidates_per_scene(starts, goals, dist_to_obst, sv, free_goal_vel, self.best_teb_,
+                                                               initial_plans=initial_plans)
+        scene_of = s.band_scenes() if s.count else np.zeros(0, np.int32)
+        for r in range(self.n_robots):                            # getInitialPlanTEB() of selectBestTeb, as a band of the batch
+            k = int(self.last_exploration["initial_plan_teb"][r])
+            self.initial_plan_teb_[r] = np.nonzero(scene_of == r)[0][k] if k >= 0 else -1
+        return self.last_exploration["n_total"]
+
+    def plan(self, starts, goals, start_vels=None, obstacles_per_robot=None, via_per_robot=None, free_goal_vel=False, initial_plans=None,
+             now=None):
+        """plan(start, goal, start_vel, free_goal_vel) of every robot (:107-125), or plan(initial_plan, ...) (:84-96) for the robots with
+        an entry in initial_plans ((x, y, yaw) arrays; start / goal are then the plan's first / last pose). starts / goals [n_robots]
+        (x, y, theta); start_vels [n_robots] (vx, vy, omega) or None entries; obstacles_per_robot [n_robots] ObstacleTable;
+        via_per_robot [n_robots] [(x, y), ...]. Returns best_teb_."""
+        R = self.n_robots
+        for name, a in (("starts", starts), ("goals", goals), ("start velocities", start_vels), ("obstacle tables", obstacles_per_robot),
+                        ("via-point lists", via_per_robot), ("initial plans", initial_plans)):
+            if a is not None and len(a) != R:
+                raise ValueError("FleetHomotopyClassPlanner.plan: %d %s for %d robots" % (len(a), name, R))
+        starts = [tuple(p) for p in starts]; goals = [tuple(p) for p in goals]
+        if initial_plans is not None:
+            for r, q in enumerate(initial_plans):
+                if q is not None:
+                    starts[r] = (q[0][0], q[1][0], q[2][0]); goals[r] = (q[0][-1], q[1][-1], q[2][-1])
+        tables = list(obstacles_per_robot) if obstacles_per_robot is not None else [_abi.ObstacleTable() for _ in range(R)]
+        vias = list(via_per_robot) if via_per_robot is not None else [[] for _ in range(R)]
+        o, s = self.cfg_.optim, self.solver
+        s.set_config(self.cfg_)
+        s.set_scenes(tables, vias)
+        self.updateAllTEBs(starts, goals, start_vels)
+        self.exploreEquivalenceClassesAndInitTebs(starts, goals, self.cfg_.obstacles.min_obstacle_dist, start_vels, free_goal_vel, initial_plans)
+        if s.count == 0:
+            self.best_teb_[:] = -1
+            return self.best_teb_.copy()
+        self.optimizeAllTEBs(o.no_inner_iterations, o.no_outer_iterations)
+        return self.selectBestTeb(now)
+
+    def optimizeAllTEBs(self, iter_innerloop, iter_outerloop):
+        h = self.cfg_.hcp
+        self.solver.optimize(iter_innerloop, iter_outerloop, True, h.selection_obst_cost_scale, h.selection_viapoint_cost_scale,
+                             h.selection_alternative_time_cost)
+
+    def selectBestTeb(self, now=None):
+        """selectBestTeb (:564-667) of every robot in one launch; switching_blocking_period (:648-663) robot by robot."""
+        import time
+        last = self.best_teb_.copy()
+        best, _ = self.solver.select_best_per_scene(last, self.initial_plan_teb_)
+        now = time.monotonic() if now is None else now
+        for r in range(self.n_robots):
+            if last[r] >= 0 and best[r] != last[r]:
+                if now - self._last_switch[r] > self.cfg_.hcp.switching_blocking_period:
+                    self._last_switch[r] = now
+                else:
+                    best[r] = last[r]        # switching blocked
+        self.best_teb_ = np.asarray(best, np.int32).copy()
+        return self.best_teb_.copy()
+
+    def getVelocityCommands(self, look_ahead_poses=None):
+        """[(ok, vx, vy, omega)] of every robot: getVelocityCommand on its best band (:127-139)."""
+        t = self.cfg_.trajectory
+        la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
+        out = []
+        for r in range(self.n_robots):
+            if self.best_teb_[r] < 0:
+                out.append((False, 0.0, 0.0, 0.0))
+                continue
+            ok, v = self.solver.velocity_command(int(self.best_teb_[r]), la, t.prevent_look_ahead_poses_near_goal)
+            out.append((ok, float(v[0]), float(v[1]), float(v[2])))
+        return out
+
+    def bands(self, stride=None):
+        """Host copy of the resident bands: list of (x, y, theta, dt), in band order (bands_of(r): those of robot r)."""
+        s = self.solver
+        if s.count == 0:
+            return []
+        b = _abi.TebBatchHost(s.count, stride or s.max_poses)
+        s.download(b)
+        return [b.get_teb(k) for k in range(s.count)]
+
+    def results(self):
+        self.last_results = self.solver.results()
+        return self.last_results
 
 
 class HomotopyClassPlanner:
