@@ -767,6 +767,36 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  *                            them (freed slots: scene 0). For every scene the subsequence of its bands is what
  *                            teb_amd_compact_bands(keep of s, best of s) leaves on a handle that holds only that scene. new_best[s] =
  *                            new index of the scene's best band, -1 when it was dropped or none was given. *n_kept = bands left.
+ *
+ * Both ends of a fleet tick per scene - the costmaps in, the checks and the commands out. A costmap set holds one grid per scene.
+ *   teb_amd_set_costmaps     n grids of any sizes, `cells` one grid after the other (row-major, size_x[s] * size_y[s] bytes each), in one
+ *                            device buffer; grid s belongs to scene s. State of the handle BESIDE the single costmap of
+ *                            teb_amd_set_costmap, which is not touched and still serves the single-scene calls. n = 0 drops the set.
+ *                            Everything is checked before the first upload: on a bad argument (n < 0, a null array, a size <= 0, a
+ *                            resolution that is not > 0; n > max_tebs: TEB_AMD_ERR_CAPACITY) the previous set stays.
+ *   teb_amd_set_scenes_from_costmaps  teb_amd_set_scenes with table s = the rows teb_amd_set_obstacles_from_costmap makes from grid s
+ *                            and robot_pose[3 s .. 3 s + 3) (the reference's column-major order) ++ the rows of custom[s] (custom NULL:
+ *                            none anywhere). Three launches serve all scenes (count, scan, write), the host reads n_scenes totals and
+ *                            then the points once. Needs a costmap set with n = n_scenes, else TEB_AMD_ERR_INVALID_ARG. n_costmap
+ *                            [n_scenes] (or NULL) = cell rows of every scene, also when the call then fails with TEB_AMD_ERR_CAPACITY
+ *                            because the sum of the cell rows and the custom rows exceeds max_obstacles; out_x / out_y (or NULL): the
+ *                            cell centres of the scenes one after the other, at most `capacity` of them. An argument or capacity error
+ *                            leaves the previous scene set installed. The polygon route (teb_amd_set_obstacles_from_costmap_polygons)
+ *                            has no per-scene form.
+ *   teb_amd_is_trajectory_feasible_per_scene  teb_amd_is_trajectory_feasible of ONE band per scene against the scene's own grid, in
+ *                            one launch with one download: bands[s] is a band of scene s, or negative - then feasible[s] =
+ *                            first_infeasible[s] = -1. The pair of scene s is what teb_amd_is_trajectory_feasible(bands[s]) gives on a
+ *                            handle whose costmap is grid s. TEB_AMD_ERR_INVALID_ARG: a band of another scene, a band index >= the
+ *                            number of bands, no scenes set, a costmap set whose size is not the number of scenes. The sample limit and
+ *                            the 1024-pose limit are those of the single call.
+ *   teb_amd_update_and_prune_per_scene  teb_amd_update_and_prune of every band with the start / goal of ITS scene (new_start /
+ *                            new_goal [3 n_scenes], NULL: leave it), in one launch; where start_vel [3 n_scenes] is given and
+ *                            has_start_vel[s] != 0 (NULL: every scene) the bands of scene s get what teb_amd_set_velocity_start(b, 1,
+ *                            start_vel + 3 s) leaves. The call does not wait for the kernel. Invalidates what teb_amd_update_and_prune
+ *                            invalidates, and the per-scene signatures. TEB_AMD_ERR_INVALID_ARG: no scenes set, a band that maps to a
+ *                            scene >= n_scenes, no bands.
+ *   teb_amd_get_velocity_commands  teb_amd_get_velocity_command of n bands after one launch and one download: cmd [n][3] = (vx, vy,
+ *                            omega), ok [n]; a negative band gives ok = 0 and zeros. Available in either mode.
  */
 int  teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obstacles_t* obstacles /* [n_scenes] */,
                         const int32_t* via_count /* [n_scenes] or NULL */, const double* via_x, const double* via_y /* concatenated */);
@@ -797,6 +827,26 @@ int  teb_amd_get_exploration_graph_per_scene(teb_amd_handle_t* h, int32_t scene,
                                              int32_t capacity_vertices, int32_t* n_vertices);
 int  teb_amd_compact_bands_per_scene(teb_amd_handle_t* h, const int32_t* keep /* [B] */, const int32_t* best /* [n_scenes] or NULL */,
                                      int32_t* n_kept, int32_t* new_best /* [n_scenes] */);
+int  teb_amd_set_costmaps(teb_amd_handle_t* h, int32_t n, const uint8_t* cells /* grids one after the other, row-major */,
+                          const int32_t* size_x, const int32_t* size_y, const double* resolution, const double* origin_x,
+                          const double* origin_y /* [n] each */);
+int  teb_amd_set_scenes_from_costmaps(teb_amd_handle_t* h, int32_t n_scenes, const double* robot_pose /* [3 n_scenes] */,
+                                      double costmap_obstacles_behind_robot_dist, const teb_amd_obstacles_t* custom /* [n_scenes] or NULL */,
+                                      const int32_t* via_count /* [n_scenes] or NULL */, const double* via_x, const double* via_y,
+                                      int32_t* n_costmap /* [n_scenes] or NULL */, double* out_x, double* out_y /* concatenated, or NULL */,
+                                      int32_t capacity);
+int  teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t* bands /* [n_scenes]: a band of scene s, or negative */,
+                                              int32_t n_footprint, const double* footprint_x, const double* footprint_y,
+                                              double inscribed_radius, double min_resolution_collision_check_angular,
+                                              int32_t look_ahead_idx, double feasibility_check_lookahead_distance,
+                                              int32_t* feasible /* [n_scenes] */, int32_t* first_infeasible /* [n_scenes] or NULL */);
+int  teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_start /* [3 n_scenes] or NULL */,
+                                        const double* new_goal /* [3 n_scenes] or NULL */, int32_t min_samples,
+                                        const double* start_vel /* [3 n_scenes] or NULL */,
+                                        const int32_t* has_start_vel /* [n_scenes] or NULL = all */);
+int  teb_amd_get_velocity_commands(teb_amd_handle_t* h, int32_t n, const int32_t* bands /* [n], negative = none */,
+                                   int32_t look_ahead_poses, int32_t prevent_look_ahead_poses_near_goal, double* cmd /* [n][3] */,
+                                   int32_t* ok /* [n] */);
 
 #ifdef __cplusplus
 }

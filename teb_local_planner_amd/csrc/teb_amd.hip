@@ -204,6 +204,19 @@ struct teb_amd_handle {
   int cm_sx = 0, cm_sy = 0;
   double cm_res = 0, cm_ox = 0, cm_oy = 0;
   DevBuf<int> cmo_cnt;   // teb_amd_set_obstacles_from_costmap: kept cells per (column, chunk of rows), then their offsets + the total
+  // the costmap set (teb_amd_set_costmaps): one grid per scene of a fleet, beside the single costmap above, which it never touches. The
+  // grids lie one after the other in ONE buffer; grids_host holds the GridDev records of the device array (device pointers).
+  struct CostmapSet {
+    int n = 0;   // 0 = none
+    DevBuf<unsigned char> cells;
+    DevBuf<GridDev> grids;
+    std::vector<GridDev> grids_host;
+  } cms;
+  // scratch of the per-scene calls at both ends of a fleet tick: the records and totals of teb_amd_set_scenes_from_costmaps and its
+  // points, the bands of teb_amd_is_trajectory_feasible_per_scene, the message of teb_amd_update_and_prune_per_scene
+  DevBuf<CmoSceneRec> cms_rec;
+  DevBuf<int> cms_tot, cms_bands;
+  DevBuf<double> cms_px, cms_py, prune_msg;
   // teb_amd_set_obstacles_from_costmap_polygons: rows / vertices / polygon vertices per block (then their offsets + totals), and the
   // converted rows (first-vertex offsets, vertex coordinates) before the host builds the table from them
   DevBuf<int> cmp_cnt, cmp_off;
@@ -848,7 +861,8 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
            h->sel_cost, h->stage_x, h->stage_y, h->stage_yaw, h->out_cmd, h->out_prof, h->out_traj, h->hsig, h->hs_pre, h->hs_pim, h->g_vx, h->g_vy, h->cand_x,
            h->cand_y, h->cand_th, h->cand_dt, h->cand_sig, h->cand_px, h->cand_py, h->tmp_x, h->tmp_y, h->tmp_th, h->tmp_dt, h->tmp_vs, h->tmp_vg, h->tmp_chi2,
            h->tmp_cost, h->tmp_lambda, h->cand_n, h->cand_off, h->cand_map, h->tmp_n, h->tmp_i, h->iter_log, h->phase_log, h->mcu_ctl, h->mcu_pub, h->mcu_items,
-           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cmo_cnt, h->cmp_cnt, h->cmp_off, h->cmp_x, h->cmp_y);
+           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cmo_cnt, h->cmp_cnt, h->cmp_off, h->cmp_x, h->cmp_y,
+           h->cms.cells, h->cms.grids, h->cms_rec, h->cms_tot, h->cms_bands, h->cms_px, h->cms_py, h->prune_msg);
   if (h->mcu_trace) (void)hipHostFree(h->mcu_trace);
   if (h->pack_host) (void)hipHostFree(h->pack_host);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1040,6 +1054,35 @@ int fleet_allocate(teb_amd_handle* h) {
   F.allocated = true;
   return TEB_AMD_OK;
 }
+// The tail of teb_amd_set_scenes and teb_amd_set_scenes_from_costmaps: the host tables of the n scenes exist and fit the capacities of the
+// handle; vias = sum of vc, in via_x / via_y one scene after the other.
+int install_scene_set(teb_amd_handle* h, std::vector<HostObst>&& tabs, std::vector<int>&& vc, const double* via_x, const double* via_y, size_t vias) {
+  const int n_scenes = (int)tabs.size();
+  int rc = fleet_allocate(h);
+  if (rc) return rc;
+  auto& F = h->fleet;
+  // rows, vertices and via-points of the scenes one after the other (voff: M + 1 entries per scene, local to the scene's vertices)
+  HostObst all;
+  for (const HostObst& t : tabs) all.append_segment(t);
+  // From here on the rows of the previous set are overwritten in place: whatever fails now is a HIP error, and the handle is then left
+  // in single-scene mode (n_scenes = 0) - nothing else consistent is left to return to.
+  hipError_t e = hipSuccess;
+  auto U = [&](hipError_t r) { if (e == hipSuccess) e = r; };
+  U(F.store.upload_rows(h->stream, all, 0, 0, 0));
+  U(F.store.upload_vias(h->stream, via_x, via_y, vias));
+  U(hipStreamSynchronize(h->stream));   // the uploads read `all` and the caller's arrays
+  if (e != hipSuccess) {
+    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0);
+    return fail(TEB_AMD_ERR_HIP, std::string("teb_amd_set_scenes: upload of the scene set -> ") + hipGetErrorString(e));
+  }
+  F.tabs = std::move(tabs);
+  F.via_count = std::move(vc);
+  rc = commit_fleet(h);
+  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0); return rc; }
+  F.n_scenes = n_scenes;
+  if (F.best_class.size() != (size_t)n_scenes) F.forget_best_classes(n_scenes);   // a remembered class belongs to a robot: kept while the fleet keeps its size
+  return TEB_AMD_OK;
+}
 }  // namespace
 
 int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obstacles_t* obstacles, const int32_t* via_count, const double* via_x,
@@ -1065,30 +1108,7 @@ int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obst
   if (rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
   if (verts > (size_t)h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
   if (vias > (size_t)h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
-  rc = fleet_allocate(h);
-  if (rc) return rc;
-  auto& F = h->fleet;
-  // rows, vertices and via-points of the scenes one after the other (voff: M + 1 entries per scene, local to the scene's vertices)
-  HostObst all;
-  for (const HostObst& t : tabs) all.append_segment(t);
-  // From here on the rows of the previous set are overwritten in place: whatever fails now is a HIP error, and the handle is then left
-  // in single-scene mode (n_scenes = 0) - nothing else consistent is left to return to.
-  hipError_t e = hipSuccess;
-  auto U = [&](hipError_t r) { if (e == hipSuccess) e = r; };
-  U(F.store.upload_rows(h->stream, all, 0, 0, 0));
-  U(F.store.upload_vias(h->stream, via_x, via_y, vias));
-  U(hipStreamSynchronize(h->stream));   // the uploads read `all` and the caller's arrays
-  if (e != hipSuccess) {
-    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0);
-    return fail(TEB_AMD_ERR_HIP, std::string("teb_amd_set_scenes: upload of the scene set -> ") + hipGetErrorString(e));
-  }
-  F.tabs = std::move(tabs);
-  F.via_count = std::move(vc);
-  rc = commit_fleet(h);
-  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0); return rc; }
-  F.n_scenes = n_scenes;
-  if (F.best_class.size() != (size_t)n_scenes) F.forget_best_classes(n_scenes);   // a remembered class belongs to a robot: kept while the fleet keeps its size
-  return TEB_AMD_OK;
+  return install_scene_set(h, std::move(tabs), std::move(vc), via_x, via_y, vias);
 }
 
 int teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_t count) {
@@ -2307,6 +2327,234 @@ int teb_amd_filter_equivalence_classes_per_scene(teb_amd_handle_t* h, double thr
     if (keep) keep[b] = kp[b];
     if (valid) valid[b] = vld[b];
     if (reasonable) reasonable[b] = rsn[b];
+  }
+  return TEB_AMD_OK;
+}
+
+// ---- both ends of a fleet tick per scene (teb_amd.h): a costmap set, the obstacle tables of every scene from its grid, feasibility of one
+// band per scene against its own grid, updateAllTEBs of every robot in one launch, the commands of many bands in one call -------------
+int teb_amd_set_costmaps(teb_amd_handle_t* h, int32_t n, const uint8_t* cells, const int32_t* size_x, const int32_t* size_y, const double* resolution,
+                         const double* origin_x, const double* origin_y) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  auto& S = h->cms;
+  if (n < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_costmaps: negative number of grids");
+  if (n == 0) { S.n = 0; S.grids_host.clear(); return TEB_AMD_OK; }
+  if (!cells || !size_x || !size_y || !resolution || !origin_x || !origin_y) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_costmaps: null argument");
+  if (n > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more grids than max_tebs");
+  // everything is checked before the first upload: on a bad argument the previous set stays
+  std::vector<GridDev> g(n);
+  std::vector<size_t> first(n);
+  size_t bytes = 0;
+  for (int s = 0; s < n; ++s) {
+    if (size_x[s] <= 0 || size_y[s] <= 0 || !(resolution[s] > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_costmaps: bad grid");
+    first[s] = bytes;
+    bytes += (size_t)size_x[s] * (size_t)size_y[s];
+  }
+  if (S.cells.n < bytes) {   // the new buffer before the old one goes: a failed allocation leaves the previous set
+    DevBuf<unsigned char> nb;
+    if (nb.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); nb.free(); return fail(TEB_AMD_ERR_HIP, "teb_amd_set_costmaps: device allocation failed"); }
+    HIPCHK(hipStreamSynchronize(h->stream));
+    S.cells.free();
+    S.cells = nb;
+  }
+  if (!S.grids.p) HIPCHK(S.grids.alloc((size_t)h->max_tebs));
+  for (int s = 0; s < n; ++s) g[s] = GridDev{S.cells.p + first[s], size_x[s], size_y[s], resolution[s], origin_x[s], origin_y[s]};
+  S.n = 0;   // from here on the previous grids are overwritten: a HIP error leaves no set
+  S.grids_host.clear();
+  HIPCHK(hipMemcpyAsync(S.cells.p, cells, bytes, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(S.grids.p, g.data(), (size_t)n * sizeof(GridDev), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // the caller's buffer may go away
+  S.grids_host = std::move(g);
+  S.n = n;
+  return TEB_AMD_OK;
+}
+
+int teb_amd_set_scenes_from_costmaps(teb_amd_handle_t* h, int32_t n_scenes, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
+                                     const teb_amd_obstacles_t* custom, const int32_t* via_count, const double* via_x, const double* via_y,
+                                     int32_t* n_costmap, double* out_x, double* out_y, int32_t capacity) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n_scenes < 1 || !robot_pose || capacity < 0)
+    return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scenes_from_costmaps: needs at least one scene, the robot poses and a capacity >= 0");
+  if (h->cms.n != n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scenes_from_costmaps: needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
+  // the custom rows of every scene (teb_amd_set_scenes' parse) and the via-points: checked before anything runs
+  std::vector<HostObst> tc(n_scenes);
+  std::vector<int> vc(n_scenes, 0);
+  size_t custom_rows = 0, verts = 0, vias = 0;
+  teb_amd_obstacles_t none{};
+  for (int s = 0; s < n_scenes; ++s) {
+    if (custom && custom[s].count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
+    if (const char* bad = parse_obstacle_table(custom ? &custom[s] : &none, tc[s])) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
+    custom_rows += tc[s].rows(); verts += tc[s].verts();
+    if (via_count) {
+      if (via_count[s] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
+      vc[s] = via_count[s]; vias += (size_t)via_count[s];
+    }
+  }
+  if (vias > 0 && (!via_x || !via_y)) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
+  if (custom_rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
+  if (verts > (size_t)h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
+  if (vias > (size_t)h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
+
+  // one record per scene: its grid, its filter (cos / sin from the host's libm, as for the single scene) and the single-scene lane rule
+  std::vector<CmoSceneRec> rec(n_scenes);
+  size_t counters = 0, max_lanes = 0;
+  for (int s = 0; s < n_scenes; ++s) {
+    CmoSceneRec& q = rec[s];
+    const double* pose = robot_pose + 3 * (size_t)s;
+    q.g = h->cms.grids_host[s];
+    q.f = CmoFilter{pose[0], pose[1], std::cos(pose[2]), std::sin(pose[2]), costmap_obstacles_behind_robot_dist};
+    q.ncols = q.g.sx - 1; q.nrows = q.g.sy - 1; q.chunk = 4; q.nchunks = 0;
+    if (q.ncols > 0 && q.nrows > 0) {   // rows per lane: the rule of teb_amd_set_obstacles_from_costmap
+      while (q.chunk < 64 && (size_t)q.ncols * (size_t)((q.nrows + q.chunk - 1) / q.chunk) > 65536) q.chunk *= 2;
+      q.nchunks = (q.nrows + q.chunk - 1) / q.chunk;
+    } else { q.ncols = 0; q.nrows = 0; }
+    const size_t lanes = (size_t)q.ncols * q.nchunks;
+    q.cnt_off = (int)counters; q.out_off = 0;
+    counters += lanes + 1;
+    max_lanes = std::max(max_lanes, lanes);
+    if (counters > (size_t)std::numeric_limits<int>::max()) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_set_scenes_from_costmaps: the grids of the set are too large for one call");
+  }
+  if (h->cmo_cnt.n < counters) { h->cmo_cnt.free(); HIPCHK(h->cmo_cnt.alloc(counters)); }
+  if (!h->cms_rec.p) { HIPCHK(h->cms_rec.alloc((size_t)h->max_tebs)); HIPCHK(h->cms_tot.alloc((size_t)h->max_tebs)); }
+
+  // count + scan into scratch: nothing of the live set is touched before the totals are known to fit
+  std::vector<int> tot(n_scenes, 0);
+  const unsigned blocks = (unsigned)((max_lanes + kCmoThreads - 1) / kCmoThreads);
+  HIPCHK(hipMemcpyAsync(h->cms_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmoSceneRec), hipMemcpyHostToDevice, h->stream));
+  if (blocks > 0) {
+    hipLaunchKernelGGL(costmap_obstacles_count_fleet_kernel, dim3(blocks, (unsigned)n_scenes), dim3(kCmoThreads), 0, h->stream, h->cms_rec.p, h->cmo_cnt.p);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(costmap_obstacles_scan_fleet_kernel, dim3((unsigned)n_scenes), dim3(kCmoScanThreads), 0, h->stream, h->cms_rec.p, h->cmo_cnt.p, h->cms_tot.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(tot.data(), h->cms_tot.p, (size_t)n_scenes * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  size_t cells_kept = 0;
+  for (int s = 0; s < n_scenes; ++s) {
+    if (n_costmap) n_costmap[s] = tot[s];
+    rec[s].out_off = (int)std::min<size_t>(cells_kept, (size_t)std::numeric_limits<int>::max());
+    cells_kept += (size_t)tot[s];
+  }
+  if (cells_kept + custom_rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "costmap cells + custom obstacles exceed max_obstacles");
+
+  // every scene's points at its prefix offset of one scratch buffer, read back once
+  std::vector<double> px(cells_kept), py(cells_kept);
+  if (cells_kept > 0) {
+    if (h->cms_px.n < cells_kept) { free_all(h->cms_px, h->cms_py); HIPCHK(h->cms_px.alloc((size_t)std::max(h->max_obst, 1))); HIPCHK(h->cms_py.alloc((size_t)std::max(h->max_obst, 1))); }
+    HIPCHK(hipMemcpyAsync(h->cms_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmoSceneRec), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(costmap_obstacles_write_fleet_kernel, dim3(blocks, (unsigned)n_scenes), dim3(kCmoThreads), 0, h->stream, h->cms_rec.p, h->cmo_cnt.p,
+                       h->cms_px.p, h->cms_py.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(px.data(), h->cms_px.p, cells_kept * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(py.data(), h->cms_py.p, cells_kept * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  const size_t give = std::min((size_t)capacity, cells_kept);
+  if (out_x) std::copy(px.begin(), px.begin() + give, out_x);
+  if (out_y) std::copy(py.begin(), py.begin() + give, out_y);
+
+  // host tables: the cell centres of scene s ++ its custom rows, exactly what teb_amd_set_scenes would parse
+  static_assert(TEB_AMD_OBST_POINT == 0, "zeroed rows are point rows");
+  std::vector<HostObst> tabs(n_scenes);
+  for (int s = 0; s < n_scenes; ++s) {
+    HostObst& t = tabs[s];
+    t.reset_rows((size_t)tot[s]);   // points, radius 0, velocity 0, not dynamic
+    std::copy(px.begin() + rec[s].out_off, px.begin() + rec[s].out_off + tot[s], t.ax.begin());
+    std::copy(py.begin() + rec[s].out_off, py.begin() + rec[s].out_off + tot[s], t.ay.begin());
+    t.cx = t.ax; t.cy = t.ay;
+    t.append(tc[s]);
+  }
+  return install_scene_set(h, std::move(tabs), std::move(vc), via_x, via_y, vias);
+}
+
+int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t* bands, int32_t nf, const double* fx, const double* fy,
+                                             double inscribed_radius, double min_res_angular, int32_t look_ahead_idx, double lookahead_distance,
+                                             int32_t* feasible, int32_t* first_infeasible) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_is_trajectory_feasible_per_scene"))) return rc;
+  const int ns = h->fleet.n_scenes;
+  if (h->cms.n != ns) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_is_trajectory_feasible_per_scene: needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
+  if (!bands || !feasible || nf < 1 || nf > kMaxFeasFootprint || !fx || !fy) return fail(TEB_AMD_ERR_INVALID_ARG, "bad bands / footprint / output");
+  if (!(inscribed_radius > 0) || !(min_res_angular > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "inscribed_radius and the angular resolution must be > 0");
+  for (int s = 0; s < ns; ++s)
+    if (bands[s] >= 0 && (bands[s] >= h->B || h->fleet.band_scene[bands[s]] != s)) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "teb_amd_is_trajectory_feasible_per_scene: bands[%d] = %d is not a band of scene %d", s, bands[s], s);
+      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+    }
+  if (h->stride > 1024) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check supports bands up to 1024 poses");
+  if (h->cm_fp.n < 2 * (size_t)kMaxFeasFootprint) { h->cm_fp.free(); HIPCHK(h->cm_fp.alloc(2 * (size_t)kMaxFeasFootprint)); }
+  if (h->cm_out.n < 2 * (size_t)h->max_tebs + 1) { h->cm_out.free(); HIPCHK(h->cm_out.alloc(2 * (size_t)h->max_tebs + 1)); }
+  if (!h->cms_bands.p) HIPCHK(h->cms_bands.alloc((size_t)h->max_tebs));
+  // [feasible | first_infeasible] ns each, then the overflow flag: one download
+  int* ovf = h->cm_out.p + 2 * (size_t)ns;
+  HIPCHK(hipMemcpyAsync(h->cms_bands.p, bands, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->cm_fp.p, fx, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->cm_fp.p + kMaxFeasFootprint, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
+  hipLaunchKernelGGL(feasibility_fleet_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, h->cms_bands.p,
+                     h->cms.grids.p, nf, h->cm_fp.p, h->cm_fp.p + kMaxFeasFootprint, inscribed_radius, min_res_angular, look_ahead_idx,
+                     lookahead_distance, 1 << 22, h->cm_out.p, h->cm_out.p + ns, ovf);
+  HIPCHK(hipGetLastError());
+  std::vector<int> out(2 * (size_t)ns + 1);
+  HIPCHK(hipMemcpyAsync(out.data(), h->cm_out.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // (the caller's bands and footprint are read until here)
+  if (out[2 * (size_t)ns]) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check: more than 2^22 interpolated samples requested (inscribed radius / angular resolution too small)");
+  for (int s = 0; s < ns; ++s) { feasible[s] = out[s]; if (first_infeasible) first_infeasible[s] = out[ns + s]; }
+  return TEB_AMD_OK;
+}
+
+int teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_start, const double* new_goal, int32_t min_samples,
+                                       const double* start_vel, const int32_t* has_start_vel) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_update_and_prune_per_scene"))) return rc;
+  if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
+  if ((rc = check_band_scenes(h, h->B))) return rc;
+  const size_t ns = (size_t)h->fleet.n_scenes;
+  // one message: [start | goal | start_vel] 3 ns each, [has_start_vel] ns (exact as doubles)
+  std::vector<double> msg(10 * ns, 0.0);
+  if (new_start) std::copy(new_start, new_start + 3 * ns, msg.begin());
+  if (new_goal) std::copy(new_goal, new_goal + 3 * ns, msg.begin() + 3 * ns);
+  if (start_vel) {
+    std::copy(start_vel, start_vel + 3 * ns, msg.begin() + 6 * ns);
+    for (size_t s = 0; s < ns; ++s) msg[9 * ns + s] = (!has_start_vel || has_start_vel[s]) ? 1.0 : 0.0;
+  }
+  if (!h->prune_msg.p) HIPCHK(h->prune_msg.alloc(10 * (size_t)h->max_tebs));
+  HIPCHK(hipMemcpyAsync(h->prune_msg.p, msg.data(), msg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // the upload reads msg; nothing waits for the kernel
+  hipLaunchKernelGGL(prune_fleet_kernel, dim3(h->B), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), h->fleet.scene_of.p,
+                     h->prune_msg.p, (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples, h->has_vs.p, h->vs.p);
+  HIPCHK(hipGetLastError());
+  h->consumers_valid = false; h->nmax_known = -1;
+  h->signatures_stale();   // the bands change: the single scene's signatures and the per-scene signatures are stale
+  return TEB_AMD_OK;
+}
+
+int teb_amd_get_velocity_commands(teb_amd_handle_t* h, int32_t n, const int32_t* bands, int32_t look_ahead_poses,
+                                  int32_t prevent_look_ahead_poses_near_goal, double* cmd, int32_t* ok) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (n < 0 || (n > 0 && (!bands || !cmd || !ok))) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_velocity_commands: bad arguments");
+  bool any = false;
+  for (int i = 0; i < n; ++i) {
+    if (bands[i] >= h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
+    any = any || bands[i] >= 0;
+  }
+  std::vector<double> c;
+  if (any) {
+    if ((rc = run_consumers(h, look_ahead_poses, prevent_look_ahead_poses_near_goal))) return rc;
+    c.resize(4 * (size_t)h->B);
+    HIPCHK(hipMemcpyAsync(c.data(), h->out_cmd.p, c.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  for (int i = 0; i < n; ++i) {
+    const double* q = bands[i] >= 0 ? c.data() + 4 * (size_t)bands[i] : nullptr;
+    cmd[3 * i] = q ? q[0] : 0.0; cmd[3 * i + 1] = q ? q[1] : 0.0; cmd[3 * i + 2] = q ? q[2] : 0.0;
+    ok[i] = q ? q[3] != 0 : 0;
   }
   return TEB_AMD_OK;
 }

@@ -82,16 +82,24 @@ __device__ __forceinline__ int footprint_cost(const GridDev& g, double x, double
 constexpr int kMaxFeasFootprint = 64;
 constexpr int kFeasThreads = 256;
 
-// grid = number of bands checked (band = first + blockIdx.x); out_feasible / out_first [gridDim.x]
-__global__ void __launch_bounds__(kFeasThreads)
-feasibility_kernel(const int* __restrict__ n_arr, const double* __restrict__ X, const double* __restrict__ Y, const double* __restrict__ TH,
-                   int stride, int first, GridDev g, int nf, const double* __restrict__ fpx, const double* __restrict__ fpy,
-                   double inscribed_radius, double min_res_angular, int look_ahead_idx, double lookahead_distance, int max_tests,
-                   int* __restrict__ out_feasible, int* __restrict__ out_first, int* __restrict__ out_overflow) {
-  __shared__ int s_look, s_fail, s_total;
-  __shared__ int s_base[1024 + 1];          // index of pose i's own test in the reference's order (i <= look_ahead)
-  __shared__ double s_fx[kMaxFeasFootprint], s_fy[kMaxFeasFootprint];
-  const int b = first + blockIdx.x, tid = threadIdx.x;
+// The LDS of one workgroup of the check
+struct FeasShared {
+  int look, fail, total;
+  int base[1024 + 1];          // index of pose i's own test in the reference's order (i <= look_ahead)
+  double fx[kMaxFeasFootprint], fy[kMaxFeasFootprint];
+};
+
+// The check of band b against grid g by one workgroup; verdict to out_feasible[slot] / out_first[slot]. Shared by the single-costmap
+// kernel and the per-scene kernel below: every lane of the workgroup calls it.
+__device__ __forceinline__ void feasibility_band(FeasShared& sh, const int* __restrict__ n_arr, const double* __restrict__ X,
+                                                 const double* __restrict__ Y, const double* __restrict__ TH, int stride, int b, const GridDev& g,
+                                                 int nf, const double* __restrict__ fpx, const double* __restrict__ fpy, double inscribed_radius,
+                                                 double min_res_angular, int look_ahead_idx, double lookahead_distance, int max_tests, int slot,
+                                                 int* __restrict__ out_feasible, int* __restrict__ out_first, int* __restrict__ out_overflow) {
+  int& s_look = sh.look; int& s_fail = sh.fail; int& s_total = sh.total;
+  int* s_base = sh.base;
+  double* s_fx = sh.fx; double* s_fy = sh.fy;
+  const int tid = threadIdx.x;
   const int n = n_arr[b];
   const double* x = X + (size_t)b * stride; const double* y = Y + (size_t)b * stride; const double* th = TH + (size_t)b * stride;
   if (tid < nf) { s_fx[tid] = fpx[tid]; s_fy[tid] = fpy[tid]; }
@@ -142,7 +150,7 @@ feasibility_kernel(const int* __restrict__ n_arr, const double* __restrict__ X, 
   __syncthreads();
   const int total = s_total;
   if (total < 0) {   // an absurd number of samples (inscribed radius / angular resolution ~ 0): refuse rather than spin
-    if (tid == 0) { out_feasible[blockIdx.x] = 0; out_first[blockIdx.x] = -1; *out_overflow = 1; }
+    if (tid == 0) { out_feasible[slot] = 0; out_first[slot] = -1; *out_overflow = 1; }
     return;
   }
   for (int q = tid; q < total; q += kFeasThreads) {
@@ -166,9 +174,39 @@ feasibility_kernel(const int* __restrict__ n_arr, const double* __restrict__ X, 
   __syncthreads();
   if (tid == 0) {
     const int f = s_fail;
-    out_feasible[blockIdx.x] = f == 0x7fffffff ? 1 : 0;
-    out_first[blockIdx.x] = f == 0x7fffffff ? -1 : f;
+    out_feasible[slot] = f == 0x7fffffff ? 1 : 0;
+    out_first[slot] = f == 0x7fffffff ? -1 : f;
   }
+}
+
+// grid = number of bands checked (band = first + blockIdx.x); out_feasible / out_first [gridDim.x]
+__global__ void __launch_bounds__(kFeasThreads)
+feasibility_kernel(const int* __restrict__ n_arr, const double* __restrict__ X, const double* __restrict__ Y, const double* __restrict__ TH,
+                   int stride, int first, GridDev g, int nf, const double* __restrict__ fpx, const double* __restrict__ fpy,
+                   double inscribed_radius, double min_res_angular, int look_ahead_idx, double lookahead_distance, int max_tests,
+                   int* __restrict__ out_feasible, int* __restrict__ out_first, int* __restrict__ out_overflow) {
+  __shared__ FeasShared sh;
+  feasibility_band(sh, n_arr, X, Y, TH, stride, first + blockIdx.x, g, nf, fpx, fpy, inscribed_radius, min_res_angular, look_ahead_idx,
+                   lookahead_distance, max_tests, blockIdx.x, out_feasible, out_first, out_overflow);
+}
+
+// grid = scenes (teb_amd_is_trajectory_feasible_per_scene): band bands[s] against grids[s] of the costmap set, both uniform over the
+// workgroup. A scene with a negative band returns before any barrier and reports (-1, -1).
+__global__ void __launch_bounds__(kFeasThreads)
+feasibility_fleet_kernel(const int* __restrict__ n_arr, const double* __restrict__ X, const double* __restrict__ Y, const double* __restrict__ TH,
+                         int stride, const int* __restrict__ bands, const GridDev* __restrict__ grids, int nf, const double* __restrict__ fpx,
+                         const double* __restrict__ fpy, double inscribed_radius, double min_res_angular, int look_ahead_idx,
+                         double lookahead_distance, int max_tests, int* __restrict__ out_feasible, int* __restrict__ out_first,
+                         int* __restrict__ out_overflow) {
+  __shared__ FeasShared sh;
+  const int s = blockIdx.x, b = bands[s];
+  if (b < 0) {
+    if (threadIdx.x == 0) { out_feasible[s] = -1; out_first[s] = -1; }
+    return;
+  }
+  const GridDev g = grids[s];
+  feasibility_band(sh, n_arr, X, Y, TH, stride, b, g, nf, fpx, fpy, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance,
+                   max_tests, s, out_feasible, out_first, out_overflow);
 }
 
 }  // namespace tebamd

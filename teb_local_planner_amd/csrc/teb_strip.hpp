@@ -155,12 +155,10 @@ __global__ void init_plan_batch_kernel(BatchDev bt, const int* off, const double
                  guess_backwards, err);
 }
 
-// updateAndPruneTEB, :555-597. One workgroup per band (blockIdx.x + b0). Dynamic LDS: 4 * stride doubles.
-__global__ void prune_kernel(BatchDev bt, int b0, int has_start, double sx, double sy, double sth, int has_goal, double gx,
-                             double gy, double gth, int min_samples) {
-  extern __shared__ __attribute__((aligned(16))) double sbuf[];
-  __shared__ int sh_k;
-  StripDev s = strip_of(bt, b0 + blockIdx.x);
+// updateAndPruneTEB, :555-597, of one band by one workgroup: every lane calls it. sbuf: LDS, 4 * s.cap doubles; sh_k: one LDS word.
+// Shared by prune_kernel and the per-scene form below.
+__device__ __forceinline__ void prune_band(StripDev s, int has_start, double sx, double sy, double sth, int has_goal, double gx, double gy,
+                                           double gth, int min_samples, double* sbuf, int& sh_k) {
   const int n = *s.n;
   if (n <= 0) return;
   if (has_start) {
@@ -193,6 +191,32 @@ __global__ void prune_kernel(BatchDev bt, int b0, int has_start, double sx, doub
     const int m = *s.n;
     if (m > 0) { s.x[m - 1] = gx; s.y[m - 1] = gy; s.th[m - 1] = gth; }
   }
+}
+// One workgroup per band (blockIdx.x + b0). Dynamic LDS: 4 * stride doubles.
+__global__ void prune_kernel(BatchDev bt, int b0, int has_start, double sx, double sy, double sth, int has_goal, double gx,
+                             double gy, double gth, int min_samples) {
+  extern __shared__ __attribute__((aligned(16))) double sbuf[];
+  __shared__ int sh_k;
+  prune_band(strip_of(bt, b0 + blockIdx.x), has_start, sx, sy, sth, has_goal, gx, gy, gth, min_samples, sbuf, sh_k);
+}
+// updateAllTEBs of every robot of a fleet (teb_amd_update_and_prune_per_scene): one workgroup per band b, start and goal of its scene
+// scene_of[b] (uniform over the workgroup) from msg = [start | goal | start_vel] 3 * ns doubles each, then [flag] ns doubles; has_start /
+// has_goal / has_vel say which parts the caller gave. Where the scene has a start velocity (flag != 0) the band's start velocity
+// becomes fixed at it: what teb_amd_set_velocity_start(b, 1, v) leaves. has_vs / vs: the writable has_vel_start / vel_start arrays of
+// the batch (BatchDev carries them as const). Dynamic LDS: 4 * stride doubles.
+__global__ void prune_fleet_kernel(BatchDev bt, const int* __restrict__ scene_of, const double* __restrict__ msg, int ns, int has_start,
+                                   int has_goal, int has_vel, int min_samples, int* has_vs, double* vs) {
+  extern __shared__ __attribute__((aligned(16))) double sbuf[];
+  __shared__ int sh_k;
+  const int b = blockIdx.x, sc = scene_of[b];
+  const double* st = msg + 3 * (size_t)sc;
+  const double* gl = msg + 3 * (size_t)(ns + sc);
+  const double* sv = msg + 3 * (size_t)(2 * ns + sc);
+  if (has_vel && threadIdx.x == 0 && msg[9 * (size_t)ns + sc] != 0.0) {
+    has_vs[b] = 1;
+    vs[3 * b] = sv[0]; vs[3 * b + 1] = sv[1]; vs[3 * b + 2] = sv[2];
+  }
+  prune_band(strip_of(bt, b), has_start, st[0], st[1], st[2], has_goal, gl[0], gl[1], gl[2], min_samples, sbuf, sh_k);
 }
 
 // extractVelocity, src/optimal_planner.cpp:1097-1133

@@ -132,6 +132,13 @@ def lib():
             L.teb_amd_compact_bands_per_scene.argtypes = [vp, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_i32]
             L.teb_amd_get_band_scenes.argtypes = [vp, _abi.p_i32, i32, _abi.p_i32]
             L.teb_amd_debug_set_explore_quota.argtypes = [vp, i32]
+        if hasattr(L, "teb_amd_set_costmaps"):   # both ends of a fleet tick per scene
+            L.teb_amd_set_costmaps.argtypes = [vp, i32, C.c_void_p, _abi.p_i32, _abi.p_i32, _abi.p_f64, _abi.p_f64, _abi.p_f64]
+            L.teb_amd_set_scenes_from_costmaps.argtypes = [vp, i32, _abi.p_f64, d, C.POINTER(_abi.Obstacles), _abi.p_i32, _abi.p_f64, _abi.p_f64,
+                                                           _abi.p_i32, _abi.p_f64, _abi.p_f64, i32]
+            L.teb_amd_is_trajectory_feasible_per_scene.argtypes = [vp, _abi.p_i32, i32, _abi.p_f64, _abi.p_f64, d, d, i32, d, _abi.p_i32, _abi.p_i32]
+            L.teb_amd_update_and_prune_per_scene.argtypes = [vp, _abi.p_f64, _abi.p_f64, i32, _abi.p_f64, _abi.p_i32]
+            L.teb_amd_get_velocity_commands.argtypes = [vp, i32, _abi.p_i32, i32, i32, _abi.p_f64, _abi.p_i32]
         _LIB = L
     return _LIB
 
@@ -345,6 +352,82 @@ class TebBatchSolver:
 
     def debug_set_explore_quota(self, q):
         _chk(lib().teb_amd_debug_set_explore_quota(self._h, int(q)), "teb_amd_debug_set_explore_quota")
+
+    # -- both ends of a fleet tick per scene (include/teb_amd.h) ----------------------------------------------
+    def set_costmaps(self, costmaps):
+        """One grid per scene: a list of objects with cells (uint8 [size_y, size_x]), resolution, origin_x, origin_y (oracle.oracle_py.Costmap
+        or alike); grid s belongs to scene s. An empty list drops the set. The single costmap of set_costmap is not touched."""
+        cms = list(costmaps)
+        n = len(cms)
+        if n == 0:
+            _chk(lib().teb_amd_set_costmaps(self._h, 0, None, None, None, None, None, None), "teb_amd_set_costmaps")
+            return
+        grids = [np.ascontiguousarray(c.cells, dtype=np.uint8) for c in cms]
+        for g in grids:
+            if g.ndim != 2:
+                raise ValueError("set_costmaps: cells must be [size_y, size_x]")
+        cells = np.concatenate([g.reshape(-1) for g in grids]) if sum(g.size for g in grids) else np.zeros(1, np.uint8)
+        sx = _abi.i32([g.shape[1] for g in grids]); sy = _abi.i32([g.shape[0] for g in grids])
+        res = _abi.f64([float(c.resolution) for c in cms]); ox = _abi.f64([float(c.origin_x) for c in cms]); oy = _abi.f64([float(c.origin_y) for c in cms])
+        D = lambda a: _abi._ptr(a, C.c_double)
+        _chk(lib().teb_amd_set_costmaps(self._h, n, cells.ctypes.data_as(C.c_void_p), _abi._ptr(sx, C.c_int32), _abi._ptr(sy, C.c_int32), D(res), D(ox),
+                                        D(oy)), "teb_amd_set_costmaps")
+
+    def set_scenes_from_costmaps(self, robot_poses, costmap_obstacles_behind_robot_dist, custom=None, vias=None):
+        """set_scenes with table s = set_obstacles_from_costmap's rows of grid s (set_costmaps) and robot_poses[s] ++ the rows of custom[s]
+        (ObstacleTable or None entries; None = no custom rows anywhere). Returns (n [n_scenes], [(xs, ys)] per scene): the number of cell
+        obstacles of every scene and their centres in table order."""
+        poses = np.ascontiguousarray(np.asarray(robot_poses, np.float64).reshape(-1, 3))
+        ns = len(poses)
+        tables = [t if t is not None else _abi.ObstacleTable() for t in (custom if custom is not None else [None] * ns)]
+        if len(tables) != ns or (vias is not None and len(vias) != ns):
+            raise ValueError("set_scenes_from_costmaps: %d robot poses, %d custom tables, %s via-point lists" % (ns, len(tables), None if vias is None else len(vias)))
+        p = _abi.pack_scenes(tables, vias)
+        cap = max(int(self.max_obstacles), 1)
+        n = np.zeros(ns, np.int32); xs = np.zeros(cap); ys = np.zeros(cap)
+        D = lambda a: _abi._ptr(a, C.c_double)
+        _chk(lib().teb_amd_set_scenes_from_costmaps(self._h, ns, D(poses), float(costmap_obstacles_behind_robot_dist), p.obstacles,
+                                                    _abi._ptr(p.via_count, C.c_int32), D(p.via_x), D(p.via_y), _abi._ptr(n, C.c_int32), D(xs), D(ys), cap),
+             "teb_amd_set_scenes_from_costmaps")
+        off = np.concatenate([[0], np.cumsum(n)])
+        self._widest_scene = max(int(n[s]) + len(tables[s]) for s in range(ns))
+        self._n_scenes = ns
+        return n.copy(), [(xs[off[s]:off[s + 1]].copy(), ys[off[s]:off[s + 1]].copy()) for s in range(ns)]
+
+    def is_trajectory_feasible_per_scene(self, bands, footprint, inscribed_radius, min_resolution_collision_check_angular=3.141592653589793,
+                                         look_ahead_idx=-1, feasibility_check_lookahead_distance=-1.0):
+        """isTrajectoryFeasible of band bands[s] (a band of scene s; negative: none) against grid s of set_costmaps, one launch:
+        (feasible [n_scenes], first_infeasible [n_scenes]) as int32 - 1 / 0, and -1 in both for a scene without a band."""
+        bd = self._per_scene("is_trajectory_feasible_per_scene", "bands", bands)
+        if bd is None:
+            raise ValueError("is_trajectory_feasible_per_scene: bands are required")
+        fx = _abi.f64([p[0] for p in footprint]); fy = _abi.f64([p[1] for p in footprint])
+        ok = np.zeros(max(len(bd), 1), np.int32); first = np.zeros(max(len(bd), 1), np.int32)
+        _chk(lib().teb_amd_is_trajectory_feasible_per_scene(self._h, _abi._ptr(bd, C.c_int32), len(footprint), _abi._ptr(fx, C.c_double),
+                                                            _abi._ptr(fy, C.c_double), float(inscribed_radius), float(min_resolution_collision_check_angular),
+                                                            int(look_ahead_idx), float(feasibility_check_lookahead_distance), _abi._ptr(ok, C.c_int32),
+                                                            _abi._ptr(first, C.c_int32)), "teb_amd_is_trajectory_feasible_per_scene")
+        return ok[:len(bd)].copy(), first[:len(bd)].copy()
+
+    def update_and_prune_per_scene(self, new_starts=None, new_goals=None, min_samples=3, start_vels=None, has_start_vel=None):
+        """updateAndPruneTEB of every band with the start / goal of its scene ([n_scenes, 3] or None), one launch; start_vels [n_scenes, 3]:
+        the bands of the scenes with has_start_vel[s] (None: all) get that fixed start velocity (set_velocity_start(v, True, b))."""
+        what = "update_and_prune_per_scene"
+        st = self._per_scene(what, "starts", new_starts, 3); gl = self._per_scene(what, "goals", new_goals, 3)
+        sv = self._per_scene(what, "start velocities", start_vels, 3)
+        hv = self._per_scene(what, "start velocity flags", has_start_vel)
+        D = lambda a: _abi._ptr(a, C.c_double)
+        _chk(lib().teb_amd_update_and_prune_per_scene(self._h, D(st), D(gl), int(min_samples), D(sv), _abi._ptr(hv, C.c_int32)),
+             "teb_amd_update_and_prune_per_scene")
+
+    def velocity_commands(self, bands, look_ahead_poses=1, prevent_look_ahead_poses_near_goal=0):
+        """getVelocityCommand of many bands after one launch and one download: (ok [n] bool, cmd [n, 3]); a negative band: False, zeros."""
+        bd = _abi.i32(bands)
+        n = len(bd)
+        cmd = np.zeros((max(n, 1), 3)); ok = np.zeros(max(n, 1), np.int32)
+        _chk(lib().teb_amd_get_velocity_commands(self._h, n, _abi._ptr(bd, C.c_int32), int(look_ahead_poses), int(prevent_look_ahead_poses_near_goal),
+                                                 _abi._ptr(cmd, C.c_double), _abi._ptr(ok, C.c_int32)), "teb_amd_get_velocity_commands")
+        return ok[:n].astype(bool), cmd[:n].copy()
 
     # -- state ---------------------------------------------------------------------------------------
     def upload(self, batch):
@@ -1037,8 +1120,10 @@ class FleetHomotopyClassPlanner:
     (h_signatures_per_scene, filter_equivalence_classes_per_scene, filter_detours_per_scene, compact_bands_per_scene),
     explore_candidates_per_scene, one optimize over all bands and select_best_per_scene with switching_blocking_period per robot.
     Every robot's bands end with the bits of a HomotopyClassPlanner of its own whose handle follows the fleet contract of
-    include/teb_amd.h. best_teb_ / initial_plan_teb_ [n_robots] are band indices of the batch (-1: none). updateAndPruneTEB is one call
-    per band in this version; randomlyDropTebs is not carried over (selection_dropping_probability > 0: NotImplementedError)."""
+    include/teb_amd.h. best_teb_ / initial_plan_teb_ [n_robots] are band indices of the batch (-1: none). With costmaps_per_robot,
+    plan() also derives every robot's obstacle table from its own grid (set_costmaps, set_scenes_from_costmaps), and
+    isTrajectoryFeasible / hasDiverged / getVelocityCommands answer for every robot's best band in one call each.
+    randomlyDropTebs is not carried over (selection_dropping_probability > 0: NotImplementedError)."""
 
     def __init__(self, cfg, n_robots, max_tebs=None, max_poses=None, max_obstacles=256, max_obstacle_vertices=256, max_via_points=64,
                  device=0, stream=None, options=None):
@@ -1054,12 +1139,14 @@ class FleetHomotopyClassPlanner:
         self.last_exploration = None
         self._goal = [None] * self.n_robots
         self._last_switch = [0.0] * self.n_robots
+        self._last_best_teb = np.full(self.n_robots, -1, np.int32)
+        self._has_costmaps = False
 
     def bands_of(self, r):
         """band indices of robot r, in band order"""
         return [int(b) for b in np.nonzero(self.solver.band_scenes() == r)[0]] if self.solver.count else []
 
-    # ---- updateAllTEBs (src/homotopy_class_planner.cpp:539-562) robot by robot --------------------------------------------------------
+    # ---- updateAllTEBs (src/homotopy_class_planner.cpp:539-562) of every robot ---------------------------------------------------------
     def updateAllTEBs(self, starts, goals, start_vels=None):
         import math
         s, t = self.solver, self.cfg_.trajectory
@@ -1078,13 +1165,12 @@ class FleetHomotopyClassPlanner:
                 at = np.cumsum(keep) - 1                          # the other robots' bands keep their order
                 self.best_teb_ = np.array([at[b] if b >= 0 else -1 for b in self.best_teb_], np.int32)
                 s.compact_bands_per_scene(keep, None)
-        if s.count > 0:
-            scene_of = s.band_scenes()
-            for b in range(s.count):                              # one call per band in this version
-                r = int(scene_of[b])
-                s.update_and_prune(starts[r], goals[r], t.min_samples, b=b)
-                if start_vels is not None and start_vels[r] is not None:
-                    s.set_velocity_start(start_vels[r], True, b=b)
+        if s.count > 0:                                           # every band of every robot, one launch
+            sv = hv = None
+            if start_vels is not None and any(v is not None for v in start_vels):
+                sv = [(0.0, 0.0, 0.0) if v is None else v for v in start_vels]
+                hv = [0 if v is None else 1 for v in start_vels]
+            s.update_and_prune_per_scene(starts, goals, t.min_samples, sv, hv)
         self._goal = [tuple(g) for g in goals]
 
     # ---- exploreEquivalenceClassesAndInitTebs (:318-340) of every robot ---------------------------------------------------------------
@@ -1110,14 +1196,17 @@ class FleetHomotopyClassPlanner:
         return self.last_exploration["n_total"]
 
     def plan(self, starts, goals, start_vels=None, obstacles_per_robot=None, via_per_robot=None, free_goal_vel=False, initial_plans=None,
-             now=None):
+             now=None, costmaps_per_robot=None, costmap_obstacles_behind_robot_dist=None):
         """plan(start, goal, start_vel, free_goal_vel) of every robot (:107-125), or plan(initial_plan, ...) (:84-96) for the robots with
         an entry in initial_plans ((x, y, yaw) arrays; start / goal are then the plan's first / last pose). starts / goals [n_robots]
         (x, y, theta); start_vels [n_robots] (vx, vy, omega) or None entries; obstacles_per_robot [n_robots] ObstacleTable;
-        via_per_robot [n_robots] [(x, y), ...]. Returns best_teb_."""
+        via_per_robot [n_robots] [(x, y), ...]. costmaps_per_robot [n_robots] (cells, resolution, origin_x, origin_y objects): every
+        robot's table is updateObstacleContainerWithCostmap of its own grid seen from starts[r] (costmap_obstacles_behind_robot_dist:
+        default cfg.obstacles.costmap_obstacles_behind_robot_dist) followed by obstacles_per_robot[r] as the custom rows, and the grids
+        stay installed for isTrajectoryFeasible. Returns best_teb_."""
         R = self.n_robots
         for name, a in (("starts", starts), ("goals", goals), ("start velocities", start_vels), ("obstacle tables", obstacles_per_robot),
-                        ("via-point lists", via_per_robot), ("initial plans", initial_plans)):
+                        ("via-point lists", via_per_robot), ("initial plans", initial_plans), ("costmaps", costmaps_per_robot)):
             if a is not None and len(a) != R:
                 raise ValueError("FleetHomotopyClassPlanner.plan: %d %s for %d robots" % (len(a), name, R))
         starts = [tuple(p) for p in starts]; goals = [tuple(p) for p in goals]
@@ -1129,7 +1218,13 @@ class FleetHomotopyClassPlanner:
         vias = list(via_per_robot) if via_per_robot is not None else [[] for _ in range(R)]
         o, s = self.cfg_.optim, self.solver
         s.set_config(self.cfg_)
-        s.set_scenes(tables, vias)
+        if costmaps_per_robot is not None:
+            dist = self.cfg_.obstacles.costmap_obstacles_behind_robot_dist if costmap_obstacles_behind_robot_dist is None else costmap_obstacles_behind_robot_dist
+            s.set_costmaps(costmaps_per_robot)
+            s.set_scenes_from_costmaps(starts, dist, tables, vias)
+        else:
+            s.set_scenes(tables, vias)
+        self._has_costmaps = costmaps_per_robot is not None
         self.updateAllTEBs(starts, goals, start_vels)
         self.exploreEquivalenceClassesAndInitTebs(starts, goals, self.cfg_.obstacles.min_obstacle_dist, start_vels, free_goal_vel, initial_plans)
         if s.count == 0:
@@ -1147,6 +1242,7 @@ class FleetHomotopyClassPlanner:
         """selectBestTeb (:564-667) of every robot in one launch; switching_blocking_period (:648-663) robot by robot."""
         import time
         last = self.best_teb_.copy()
+        self._last_best_teb = last.copy()                # last_best_teb_ (:566) of every robot
         best, _ = self.solver.select_best_per_scene(last, self.initial_plan_teb_)
         now = time.monotonic() if now is None else now
         for r in range(self.n_robots):
@@ -1159,16 +1255,81 @@ class FleetHomotopyClassPlanner:
         return self.best_teb_.copy()
 
     def getVelocityCommands(self, look_ahead_poses=None):
-        """[(ok, vx, vy, omega)] of every robot: getVelocityCommand on its best band (:127-139)."""
+        """[(ok, vx, vy, omega)] of every robot: getVelocityCommand on its best band (:127-139), one call for all."""
         t = self.cfg_.trajectory
         la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
+        ok, v = self.solver.velocity_commands(self.best_teb_, la, t.prevent_look_ahead_poses_near_goal)
+        return [(bool(ok[r]), float(v[r, 0]), float(v[r, 1]), float(v[r, 2])) for r in range(self.n_robots)]
+
+    def isTrajectoryFeasible(self, footprint_spec, inscribed_radius, circumscribed_radius=0.0, look_ahead_idx=-1,
+                             feasibility_check_lookahead_distance=-1.0):
+        """HomotopyClassPlanner::isTrajectoryFeasible (src/homotopy_class_planner.cpp:686-709) of every robot against ITS grid of the
+        costmaps plan(costmaps_per_robot=...) installed: a list of bools. Every round checks the best band of every undecided robot in
+        one call; an infeasible best band is removed and the robot's next best tried in the next round, unless it was already the best
+        band of the previous tick (then False). A robot without bands: False."""
+        s, R = self.solver, self.n_robots
+        if not self._has_costmaps:
+            raise ValueError("FleetHomotopyClassPlanner.isTrajectoryFeasible: plan(costmaps_per_robot=...) installs the grids the bands are checked against")
+        verdict = [None] * R
+        ang = self.cfg_.trajectory.min_resolution_collision_check_angular
+        while any(v is None for v in verdict):
+            scene_of = s.band_scenes() if s.count else np.zeros(0, np.int32)
+            open_ = [r for r in range(R) if verdict[r] is None]
+            for r in open_:
+                if not (scene_of == r).any():
+                    verdict[r] = False
+            open_ = [r for r in open_ if verdict[r] is None]
+            if not open_:
+                break
+            if any(self.best_teb_[r] < 0 for r in open_):          # findBestTeb (:711-723): re-select where the best band is gone
+                lb = np.array([-1 if (verdict[r] is None and self.best_teb_[r] < 0) else self.best_teb_[r] for r in range(R)], np.int32)
+                best, _ = s.select_best_per_scene(lb, self.initial_plan_teb_)
+                for r in open_:
+                    if self.best_teb_[r] < 0:
+                        self.best_teb_[r] = best[r]
+                        self._last_best_teb[r] = -1
+            bands = np.array([self.best_teb_[r] if verdict[r] is None else -1 for r in range(R)], np.int32)
+            for r in open_:
+                if bands[r] < 0:
+                    verdict[r] = False
+            if not (bands >= 0).any():
+                break
+            ok, _ = s.is_trajectory_feasible_per_scene(bands, footprint_spec, inscribed_radius, ang, look_ahead_idx,
+                                                       feasibility_check_lookahead_distance)
+            keep = np.ones(s.count, np.int32)
+            for r in range(R):
+                if bands[r] < 0:
+                    continue
+                if ok[r] == 1:
+                    verdict[r] = True
+                    continue
+                best = int(bands[r])
+                keep[best] = 0                                       # removeTeb (:725-744)
+                if self._last_best_teb[r] == best:
+                    verdict[r] = False                               # "not failing could result in oscillations between trajectories"
+                    self._last_best_teb[r] = -1
+                if self.initial_plan_teb_[r] == best:
+                    self.initial_plan_teb_[r] = -1
+                self.best_teb_[r] = -1
+            if not keep.all():
+                at = (np.cumsum(keep) - 1).astype(np.int32)        # the kept bands move to the front in order
+                move = lambda a: np.array([at[b] if b >= 0 else -1 for b in a], np.int32)
+                self.best_teb_, self.initial_plan_teb_, self._last_best_teb = move(self.best_teb_), move(self.initial_plan_teb_), move(self._last_best_teb)
+                s.compact_bands_per_scene(keep, None)
+        return [bool(v) for v in verdict]
+
+    def hasDiverged(self):
+        """TebOptimalPlanner::hasDiverged (src/optimal_planner.cpp:1023-1039) of every robot's best band: a list of bools (no best band:
+        False), from one download of the batch statistics."""
+        c = self.cfg_
+        if self.solver.count == 0:
+            return [False] * self.n_robots
+        available, back_chi2 = self.solver.batch_statistics()
         out = []
         for r in range(self.n_robots):
-            if self.best_teb_[r] < 0:
-                out.append((False, 0.0, 0.0, 0.0))
-                continue
-            ok, v = self.solver.velocity_command(int(self.best_teb_[r]), la, t.prevent_look_ahead_poses_near_goal)
-            out.append((ok, float(v[0]), float(v[1]), float(v[2])))
+            b = int(self.best_teb_[r])
+            out.append(bool(b >= 0 and c.recovery.divergence_detection_enable and available[b]
+                            and back_chi2[b] > c.recovery.divergence_detection_max_chi_squared))
         return out
 
     def bands(self, stride=None):
