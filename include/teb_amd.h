@@ -781,8 +781,26 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  *                            [n_scenes] (or NULL) = cell rows of every scene, also when the call then fails with TEB_AMD_ERR_CAPACITY
  *                            because the sum of the cell rows and the custom rows exceeds max_obstacles; out_x / out_y (or NULL): the
  *                            cell centres of the scenes one after the other, at most `capacity` of them. An argument or capacity error
- *                            leaves the previous scene set installed. The polygon route (teb_amd_set_obstacles_from_costmap_polygons)
- *                            has no per-scene form.
+ *                            leaves the previous scene set installed.
+ *   teb_amd_set_scenes_from_costmap_polygons  teb_amd_set_scenes with table s = the rows teb_amd_set_obstacles_from_costmap_polygons
+ *                            makes from grid s, robot_pose[3 s .. 3 s + 3) and tile_cells[s] (same conversion rule, row order, vertex
+ *                            bits, derived centroids and radii) ++ the rows of custom[s] (custom NULL: none anywhere). The tile size is
+ *                            per scene: sparse maps want 1, structured maps 8, and a fleet has both. Three launches serve all scenes
+ *                            (count, scan, write: as many workgroups as the scenes have blocks together), the host reads the
+ *                            3 n_scenes totals and then the offsets and vertices once. Needs a costmap set with n = n_scenes. A grid
+ *                            without a visit domain (size_x < 2 or size_y < 2) converts to no rows. n_obstacles / n_points [n_scenes]
+ *                            (or NULL) = converted rows of every scene and their vertices, also when the call then fails with
+ *                            TEB_AMD_ERR_CAPACITY. out_offset [capacity_obstacles + 1], out_x / out_y [capacity_points] (or NULL): the
+ *                            polygon list of the scenes one after the other - row i of the concatenation has the vertices
+ *                            out_offset[i] .. out_offset[i + 1] - 1 of the concatenated arrays, (sum of rows) + 1 offsets; written
+ *                            only when all three are given, the sum of the rows <= capacity_obstacles and the sum of the vertices <=
+ *                            capacity_points. TEB_AMD_ERR_INVALID_ARG: n_scenes < 1, a null pose array, null tile_cells, a tile size
+ *                            outside 1 .. 64, a negative capacity, a costmap set of another size, a bad custom table, bad via
+ *                            arrays. TEB_AMD_ERR_CAPACITY: converted + custom rows > max_obstacles, converted + custom polygon
+ *                            vertices > max_obstacle_vertices, via-points > max_via_points, grids too large for one call. Everything
+ *                            is checked before the live scene set is touched: on these errors the previous set stays installed and
+ *                            behaves as if the call had not been made. teb_amd_set_obstacles_from_costmap_polygons itself stays a
+ *                            single-scene call (refused while scenes are set).
  *   teb_amd_is_trajectory_feasible_per_scene  teb_amd_is_trajectory_feasible of ONE band per scene against the scene's own grid, in
  *                            one launch with one download: bands[s] is a band of scene s, or negative - then feasible[s] =
  *                            first_infeasible[s] = -1. The pair of scene s is what teb_amd_is_trajectory_feasible(bands[s]) gives on a
@@ -835,6 +853,12 @@ int  teb_amd_set_scenes_from_costmaps(teb_amd_handle_t* h, int32_t n_scenes, con
                                       const int32_t* via_count /* [n_scenes] or NULL */, const double* via_x, const double* via_y,
                                       int32_t* n_costmap /* [n_scenes] or NULL */, double* out_x, double* out_y /* concatenated, or NULL */,
                                       int32_t capacity);
+int  teb_amd_set_scenes_from_costmap_polygons(teb_amd_handle_t* h, int32_t n_scenes, const double* robot_pose /* [3 n_scenes] */,
+                                              double costmap_obstacles_behind_robot_dist, const int32_t* tile_cells /* [n_scenes], each 1 .. 64 */,
+                                              const teb_amd_obstacles_t* custom /* [n_scenes] or NULL */, const int32_t* via_count,
+                                              const double* via_x, const double* via_y, int32_t* n_obstacles /* [n_scenes] or NULL */,
+                                              int32_t* n_points /* [n_scenes] or NULL */, int32_t* out_offset, double* out_x, double* out_y,
+                                              int32_t capacity_obstacles, int32_t capacity_points);
 int  teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t* bands /* [n_scenes]: a band of scene s, or negative */,
                                               int32_t n_footprint, const double* footprint_x, const double* footprint_y,
                                               double inscribed_radius, double min_resolution_collision_check_angular,

@@ -221,6 +221,10 @@ struct teb_amd_handle {
   // converted rows (first-vertex offsets, vertex coordinates) before the host builds the table from them
   DevBuf<int> cmp_cnt, cmp_off;
   DevBuf<double> cmp_x, cmp_y;
+  // teb_amd_set_scenes_from_costmap_polygons shares them and adds the records of the scenes, the prefix array of their block counts
+  // and the 3 x n_scenes totals
+  DevBuf<CmpSceneRec> cmp_rec;
+  DevBuf<int> cmp_blk, cmp_tot;
   std::mt19937 rnd_generator;   // ProbRoadmapGraph::rnd_generator_ (graph_search.h:211): default-seeded 32-bit Mersenne twister
   // fleet batches (teb_fleet.hpp, teb_amd_set_scenes): the scene set - a second DevSceneStore, allocated at the first
   // teb_amd_set_scenes and sized by the capacities of the handle, with the rows, vertices and via-points of the scenes one after the
@@ -861,7 +865,7 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
            h->sel_cost, h->stage_x, h->stage_y, h->stage_yaw, h->out_cmd, h->out_prof, h->out_traj, h->hsig, h->hs_pre, h->hs_pim, h->g_vx, h->g_vy, h->cand_x,
            h->cand_y, h->cand_th, h->cand_dt, h->cand_sig, h->cand_px, h->cand_py, h->tmp_x, h->tmp_y, h->tmp_th, h->tmp_dt, h->tmp_vs, h->tmp_vg, h->tmp_chi2,
            h->tmp_cost, h->tmp_lambda, h->cand_n, h->cand_off, h->cand_map, h->tmp_n, h->tmp_i, h->iter_log, h->phase_log, h->mcu_ctl, h->mcu_pub, h->mcu_items,
-           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cmo_cnt, h->cmp_cnt, h->cmp_off, h->cmp_x, h->cmp_y,
+           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cmo_cnt, h->cmp_cnt, h->cmp_off, h->cmp_x, h->cmp_y, h->cmp_rec, h->cmp_blk, h->cmp_tot,
            h->cms.cells, h->cms.grids, h->cms_rec, h->cms_tot, h->cms_bands, h->cms_px, h->cms_py, h->prune_msg);
   if (h->mcu_trace) (void)hipHostFree(h->mcu_trace);
   if (h->pack_host) (void)hipHostFree(h->pack_host);
@@ -1997,6 +2001,26 @@ int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_
   return install_obstacles(h, std::move(t));
 }
 
+// A polygon list (row i has the vertices off[i] .. off[i + 1] - 1 of px / py) as an obstacle table: 1 vertex a point, 2 a line, more a
+// polygon; radius 0, velocity 0, not dynamic. Through teb_amd_set_obstacles' parse, so that centroids and bounding radii are the same
+// code. What both polygon routes of the costmap (single scene, scene set) make their converted rows with. Returns null or what is wrong.
+static const char* polygon_list_table(const int* off, const double* px, const double* py, int nr, HostObst& t) {
+  std::vector<int> type(nr), voff(nr + 1, 0);
+  std::vector<double> ax(nr), ay(nr), bx(nr, 0.0), by(nr, 0.0), pgx, pgy;
+  for (int i = 0; i < nr; ++i) {
+    const int k0 = off[i], k = off[i + 1] - k0;
+    type[i] = k == 1 ? TEB_AMD_OBST_POINT : k == 2 ? TEB_AMD_OBST_LINE : TEB_AMD_OBST_POLYGON;
+    ax[i] = k <= 2 ? px[k0] : 0.0; ay[i] = k <= 2 ? py[k0] : 0.0;   // a polygon is its vertices (ObstacleTable.add_polygon)
+    if (k == 2) { bx[i] = px[k0 + 1]; by[i] = py[k0 + 1]; }
+    if (k >= 3) { pgx.insert(pgx.end(), px + k0, px + k0 + k); pgy.insert(pgy.end(), py + k0, py + k0 + k); }
+    voff[i + 1] = (int)pgx.size();
+  }
+  teb_amd_obstacles_t ct{};
+  ct.count = nr; ct.type = type.data(); ct.ax = ax.data(); ct.ay = ay.data(); ct.bx = bx.data(); ct.by = by.data();
+  ct.vert_offset = voff.data(); ct.vert_x = pgx.data(); ct.vert_y = pgy.data();
+  return parse_obstacle_table(&ct, t);
+}
+
 // The converter slot of computeVelocityCommands (updateObstacleContainerWithCostmapConverter, src/teb_local_planner_ros.cpp:506-549)
 // fed by the device: the costmap's lethal cells as convex points / lines / polygons (kernels in teb_costmap_polygons.hpp) + the
 // caller's obstacles as the handle's obstacle table
@@ -2065,23 +2089,8 @@ int teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const doubl
     HIPCHK(hipStreamSynchronize(h->stream));
   }
 
-  // as an obstacle table (1 vertex: point, 2: line, more: polygon; radius 0, velocity 0, not dynamic) through teb_amd_set_obstacles'
-  // parse, so that centroids and bounding radii are the same code; then the custom rows behind it
-  std::vector<int> type(nr), voff(nr + 1, 0);
-  std::vector<double> ax(nr), ay(nr), bx(nr, 0.0), by(nr, 0.0), pgx, pgy;
-  for (int i = 0; i < nr; ++i) {
-    const int k0 = off[i], k = off[i + 1] - k0;
-    type[i] = k == 1 ? TEB_AMD_OBST_POINT : k == 2 ? TEB_AMD_OBST_LINE : TEB_AMD_OBST_POLYGON;
-    ax[i] = k <= 2 ? px[k0] : 0.0; ay[i] = k <= 2 ? py[k0] : 0.0;   // a polygon is its vertices (ObstacleTable.add_polygon)
-    if (k == 2) { bx[i] = px[k0 + 1]; by[i] = py[k0 + 1]; }
-    if (k >= 3) { pgx.insert(pgx.end(), px.begin() + k0, px.begin() + k0 + k); pgy.insert(pgy.end(), py.begin() + k0, py.begin() + k0 + k); }
-    voff[i + 1] = (int)pgx.size();
-  }
-  teb_amd_obstacles_t ct{};
-  ct.count = nr; ct.type = type.data(); ct.ax = ax.data(); ct.ay = ay.data(); ct.bx = bx.data(); ct.by = by.data();
-  ct.vert_offset = voff.data(); ct.vert_x = pgx.data(); ct.vert_y = pgy.data();
   HostObst t;
-  if (const char* bad = parse_obstacle_table(&ct, t)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
+  if (const char* bad = polygon_list_table(off.data(), px.data(), py.data(), nr, t)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
   t.append(tc);
   if (out_offset && out_x && out_y && nr <= capacity_obstacles && nv <= capacity_points) {
     std::copy(off.begin(), off.end(), out_offset);
@@ -2465,6 +2474,135 @@ int teb_amd_set_scenes_from_costmaps(teb_amd_handle_t* h, int32_t n_scenes, cons
     std::copy(py.begin() + rec[s].out_off, py.begin() + rec[s].out_off + tot[s], t.ay.begin());
     t.cx = t.ax; t.cy = t.ay;
     t.append(tc[s]);
+  }
+  return install_scene_set(h, std::move(tabs), std::move(vc), via_x, via_y, vias);
+}
+
+// teb_amd_set_scenes_from_costmaps on the polygon route: every scene's grid through the kernels of teb_costmap_polygons.hpp with the
+// scene's own tile size, three launches for the whole set
+int teb_amd_set_scenes_from_costmap_polygons(teb_amd_handle_t* h, int32_t n_scenes, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
+                                             const int32_t* tile_cells, const teb_amd_obstacles_t* custom, const int32_t* via_count, const double* via_x,
+                                             const double* via_y, int32_t* n_obstacles, int32_t* n_points, int32_t* out_offset, double* out_x,
+                                             double* out_y, int32_t capacity_obstacles, int32_t capacity_points) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  const char* fn = "teb_amd_set_scenes_from_costmap_polygons: ";
+  if (n_scenes < 1 || !robot_pose || !tile_cells || capacity_obstacles < 0 || capacity_points < 0)
+    return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "needs at least one scene, the robot poses, the tile sizes and capacities >= 0");
+  if (h->cms.n != n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
+  for (int s = 0; s < n_scenes; ++s)
+    if (tile_cells[s] < 1 || tile_cells[s] > kCmpMaxTile) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "tile_cells outside 1 .. 64");
+  // the custom rows of every scene (teb_amd_set_scenes' parse) and the via-points: checked before anything runs
+  std::vector<HostObst> tc(n_scenes);
+  std::vector<int> vc(n_scenes, 0);
+  size_t custom_rows = 0, custom_verts = 0, vias = 0;
+  teb_amd_obstacles_t none{};
+  for (int s = 0; s < n_scenes; ++s) {
+    if (custom && custom[s].count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
+    if (const char* bad = parse_obstacle_table(custom ? &custom[s] : &none, tc[s])) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
+    custom_rows += tc[s].rows(); custom_verts += tc[s].verts();
+    if (via_count) {
+      if (via_count[s] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
+      vc[s] = via_count[s]; vias += (size_t)via_count[s];
+    }
+  }
+  if (vias > 0 && (!via_x || !via_y)) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
+  if (custom_rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
+  if (custom_verts > (size_t)h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
+  if (vias > (size_t)h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
+
+  // one record per scene: its grid, its filter (cos / sin from the host's libm, as for the single scene), the single-scene block
+  // geometry at its own tile size, and its place in the flat block list and in the count arrays
+  std::vector<CmpSceneRec> rec(n_scenes);
+  std::vector<int> blk0(n_scenes + 1, 0);
+  long long blocks = 0, ncnt = 0;
+  const long long int_max = std::numeric_limits<int>::max();
+  for (int s = 0; s < n_scenes; ++s) {
+    CmpSceneRec& r = rec[s];
+    const double* pose = robot_pose + 3 * (size_t)s;
+    const int T = tile_cells[s];
+    r.g = h->cms.grids_host[s];
+    r.f = CmoFilter{pose[0], pose[1], std::cos(pose[2]), std::sin(pose[2]), costmap_obstacles_behind_robot_dist};
+    r.q = CmpGeom{r.g.sx - 1, r.g.sy - 1, T, kCmpSlots / (T * T), 0, 0};
+    long long nb = 0;
+    if (r.q.ncols > 0 && r.q.nrows > 0) {
+      r.q.nty = (r.q.nrows + T - 1) / T;
+      r.q.nby = (r.q.nty + r.q.k - 1) / r.q.k;
+      nb = (long long)((r.q.ncols + T - 1) / T) * r.q.nby;
+      if (nb > (1 << 30)) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "grid too large");
+    }
+    r.blk0 = (int)blocks; r.nblk = (int)nb; r.cnt0 = (int)ncnt; r.row0 = 0; r.vtx0 = 0;
+    blk0[s] = (int)blocks;
+    blocks += nb; ncnt += nb + 1;
+    if (blocks > int_max || 3 * ncnt > int_max) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "the grids of the set are too large for one call");
+  }
+  blk0[n_scenes] = (int)blocks;
+  if (h->cmp_cnt.n < 3 * (size_t)ncnt) { h->cmp_cnt.free(); HIPCHK(h->cmp_cnt.alloc(3 * (size_t)ncnt)); }
+  if (!h->cmp_rec.p) {
+    HIPCHK(h->cmp_rec.alloc((size_t)h->max_tebs)); HIPCHK(h->cmp_blk.alloc((size_t)h->max_tebs + 1)); HIPCHK(h->cmp_tot.alloc(3 * (size_t)h->max_tebs));
+  }
+
+  // count + scan into scratch: nothing of the live set is touched before the totals are known to fit
+  std::vector<int> tot(3 * (size_t)n_scenes, 0);   // rows, vertices, polygon vertices: [array][scene]
+  HIPCHK(hipMemcpyAsync(h->cmp_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmpSceneRec), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->cmp_blk.p, blk0.data(), ((size_t)n_scenes + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (blocks > 0) {
+    hipLaunchKernelGGL(costmap_polygons_count_fleet_kernel, dim3((unsigned)blocks), dim3(kCmpThreads), 0, h->stream, h->cmp_rec.p, h->cmp_blk.p, n_scenes,
+                       (int)ncnt, h->cmp_cnt.p);
+    HIPCHK(hipGetLastError());
+  }
+  hipLaunchKernelGGL(costmap_polygons_scan_fleet_kernel, dim3(3 * (unsigned)n_scenes), dim3(kCmoScanThreads), 0, h->stream, h->cmp_rec.p, n_scenes, (int)ncnt,
+                     h->cmp_cnt.p, h->cmp_tot.p);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(tot.data(), h->cmp_tot.p, tot.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  const int* nrs = tot.data();
+  const int* nvs = tot.data() + n_scenes;
+  long long rows = 0, verts = 0, pverts = 0;
+  for (int s = 0; s < n_scenes; ++s) {
+    if (n_obstacles) n_obstacles[s] = nrs[s];
+    if (n_points) n_points[s] = nvs[s];
+    rec[s].row0 = (int)std::min(rows, int_max); rec[s].vtx0 = (int)std::min(verts, int_max);
+    rows += nrs[s]; verts += nvs[s]; pverts += tot[2 * (size_t)n_scenes + s];
+  }
+  if (rows + (long long)custom_rows > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "converted costmap rows + custom obstacles exceed max_obstacles");
+  if (pverts + (long long)custom_verts > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
+
+  // every scene's converted rows at its prefix offsets of one scratch: first-vertex offsets (from the scene's first vertex on) and
+  // vertex coordinates (world), in table order; read back once
+  std::vector<int> off((size_t)rows + 1, 0);
+  std::vector<double> px((size_t)verts), py((size_t)verts);
+  if (rows > 0) {   // (rows <= max_obstacles; a point or line row has at most 2 vertices: verts <= 2 max_obstacles + max_obstacle_vertices)
+    if (h->cmp_off.n < (size_t)rows) { h->cmp_off.free(); HIPCHK(h->cmp_off.alloc((size_t)rows)); }
+    if (h->cmp_x.n < (size_t)verts) { h->cmp_x.free(); h->cmp_y.free(); HIPCHK(h->cmp_x.alloc((size_t)verts)); HIPCHK(h->cmp_y.alloc((size_t)verts)); }
+    HIPCHK(hipMemcpyAsync(h->cmp_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmpSceneRec), hipMemcpyHostToDevice, h->stream));
+    const CmpOut o{h->cmp_off.p, h->cmp_x.p, h->cmp_y.p};
+    hipLaunchKernelGGL(costmap_polygons_write_fleet_kernel, dim3((unsigned)blocks), dim3(kCmpThreads), 0, h->stream, h->cmp_rec.p, h->cmp_blk.p, n_scenes,
+                       (int)ncnt, h->cmp_cnt.p, o);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(off.data(), h->cmp_off.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(px.data(), h->cmp_x.p, (size_t)verts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(py.data(), h->cmp_y.p, (size_t)verts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+
+  // host tables: the converted rows of scene s (teb_amd_set_obstacles_from_costmap_polygons' table of its grid) ++ its custom rows,
+  // exactly what teb_amd_set_scenes would parse
+  std::vector<HostObst> tabs(n_scenes);
+  std::vector<int> so;
+  for (int s = 0; s < n_scenes; ++s) {
+    so.assign(off.begin() + rec[s].row0, off.begin() + rec[s].row0 + nrs[s]);
+    so.push_back(nvs[s]);
+    if (const char* bad = polygon_list_table(so.data(), px.data() + rec[s].vtx0, py.data() + rec[s].vtx0, nrs[s], tabs[s]))
+      return fail(TEB_AMD_ERR_INVALID_ARG, bad);
+    tabs[s].append(tc[s]);
+    for (int i = 0; i < nrs[s]; ++i) off[(size_t)rec[s].row0 + i] += rec[s].vtx0;   // the polygon list of the scenes one after the other
+  }
+  off[(size_t)rows] = (int)verts;
+  if (out_offset && out_x && out_y && rows <= capacity_obstacles && verts <= capacity_points) {
+    std::copy(off.begin(), off.end(), out_offset);
+    std::copy(px.begin(), px.end(), out_x);
+    std::copy(py.begin(), py.end(), out_y);
   }
   return install_scene_set(h, std::move(tabs), std::move(vc), via_x, via_y, vias);
 }

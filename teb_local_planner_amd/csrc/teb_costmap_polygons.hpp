@@ -26,7 +26,8 @@
 //   5. a second scan gives each row its first vertex in the block and the block its totals (rows, vertices, polygon vertices).
 // The count kernel stores the totals per block; after a scan over blocks (costmap_obstacles_scan_kernel) the write kernel runs the same
 // cmp_block again and writes each row's first-vertex offset and its vertices' world coordinates into scratch. The two kernels call the
-// same function, so the counts and the writes cannot disagree.
+// same function, so the counts and the writes cannot disagree. The forms for a scene set (at the end of this file) run the same
+// cmp_block and the same write pass behind a per-scene record.
 #pragma once
 #include "teb_costmap_obstacles.hpp"
 
@@ -213,14 +214,13 @@ __global__ void __launch_bounds__(kCmpThreads) costmap_polygons_count_kernel(Gri
   }
 }
 
-__global__ void __launch_bounds__(kCmpThreads) costmap_polygons_write_kernel(GridDev g, CmoFilter f, CmpGeom q, int nblk, const int* off,
-                                                                             CmpOut o) {
-  __shared__ CmpLds s;
-  int rows, verts, pverts;
-  cmp_block(g, f, q, blockIdx.x, s, rows, verts, pverts);
+// The write pass of a block after cmp_block: every row's first-vertex offset and its vertices' world coordinates. off_rows / off_verts:
+// the block's first row and first vertex (the scanned counts); o: where row 0 and vertex 0 of the table go.
+__device__ __forceinline__ void cmp_write_block(const GridDev& g, const CmpGeom& q, int blk, const CmpLds& s, const int* off_rows,
+                                                const int* off_verts, const CmpOut& o) {
   const int T = q.T, TT = T * T;
-  const int x0 = (blockIdx.x / q.nby) * T, y0 = (blockIdx.x % q.nby) * q.k * T;
-  const int row0 = off[blockIdx.x], v0 = off[(nblk + 1) + blockIdx.x];
+  const int x0 = (blk / q.nby) * T, y0 = (blk % q.nby) * q.k * T;
+  const int row0 = off_rows[blk], v0 = off_verts[blk];
   for (int i = threadIdx.x; i < kCmpSlots; i += kCmpThreads) {
     if (s.lab[i] != i) continue;
     const int c = s.chain[i] & 0xff, kl = (s.chain[i] >> 8) & 0xff, ku = s.chain[i] >> 16, base = s.seg[i] & 0xffff;
@@ -235,6 +235,78 @@ __global__ void __launch_bounds__(kCmpThreads) costmap_polygons_write_kernel(Gri
     for (int t = 0; t < nl; ++t) put(L[t]);
     for (int t = 0; t < nu; ++t) put(U[-t]);
   }
+}
+
+__global__ void __launch_bounds__(kCmpThreads) costmap_polygons_write_kernel(GridDev g, CmoFilter f, CmpGeom q, int nblk, const int* off,
+                                                                             CmpOut o) {
+  __shared__ CmpLds s;
+  int rows, verts, pverts;
+  cmp_block(g, f, q, blockIdx.x, s, rows, verts, pverts);
+  cmp_write_block(g, q, blockIdx.x, s, off, off + (nblk + 1), o);
+}
+
+// ---- the scene set (teb_amd_set_scenes_from_costmap_polygons): the passes over the grids of a costmap set (teb_amd_set_costmaps), one
+// launch each. The launch is flat: the blocks of the scenes one after the other, as many workgroups as the set has blocks (a workgroup
+// holds 97 KB of LDS and so runs alone on its CU: none is started for nothing). A workgroup finds its scene by a search over the prefix
+// array of block counts that depends on blockIdx.x alone, so the scene's record is uniform over the workgroup and arrives through scalar
+// loads. The blocks are the single-scene blocks: a scene's counts, offsets and vertices are those of a handle that holds only its grid.
+struct CmpSceneRec {
+  GridDev g;
+  CmoFilter f;
+  CmpGeom q;      // the scene's own tile size: T, k = kCmpSlots / T^2
+  int blk0;       // the scene's first block in the flat block list of the set
+  int nblk;       // its blocks (0: a grid without a visit domain)
+  int cnt0;       // first of the scene's nblk + 1 counters in each of the three count arrays
+  int row0, vtx0; // write pass: the scene's first row / first vertex in the scratch of the whole set
+};
+
+// The scene of flat block b: the last s with blk0[s] <= b (blk0: n + 1 entries, blk0[n] = blocks of the set > b), which skips the scenes
+// without blocks.
+__device__ __forceinline__ int cmp_scene_of_block(const int* __restrict__ blk0, int n, int b) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (blk0[mid] <= b) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// cnt: three arrays (rows, vertices, polygon vertices) of ncnt = sum of (nblk + 1) counters each
+__global__ void __launch_bounds__(kCmpThreads) costmap_polygons_count_fleet_kernel(const CmpSceneRec* __restrict__ recs,
+                                                                                   const int* __restrict__ blk0, int n_scenes, int ncnt,
+                                                                                   int* cnt) {
+  __shared__ CmpLds s;
+  const CmpSceneRec r = recs[cmp_scene_of_block(blk0, n_scenes, blockIdx.x)];   // by value: the record lives in scalar registers
+  const int blk = blockIdx.x - r.blk0;
+  int rows, verts, pverts;
+  cmp_block(r.g, r.f, r.q, blk, s, rows, verts, pverts);
+  if (threadIdx.x == 0) {
+    int* c = cnt + r.cnt0 + blk;
+    c[0] = rows;
+    c[ncnt] = verts;
+    c[2 * (size_t)ncnt] = pverts;
+  }
+}
+// one workgroup per (scene, array): blockIdx.x = 3 * scene + array. The total lands behind the scene's counters and in
+// totals[array * n_scenes + scene] - what the host reads, in one copy.
+__global__ void __launch_bounds__(kCmoScanThreads) costmap_polygons_scan_fleet_kernel(const CmpSceneRec* __restrict__ recs, int n_scenes,
+                                                                                      int ncnt, int* cnt, int* totals) {
+  __shared__ int part[kCmoScanThreads];
+  const int sc = blockIdx.x / 3, a = blockIdx.x % 3;
+  const CmpSceneRec& r = recs[sc];
+  costmap_obstacles_scan_group(cnt + (size_t)a * ncnt + r.cnt0, r.nblk, part);
+  if (threadIdx.x == kCmoScanThreads - 1) totals[a * n_scenes + sc] = part[threadIdx.x];
+}
+// o: the scratch of the whole set; a row's first-vertex offset counts from the scene's first vertex
+__global__ void __launch_bounds__(kCmpThreads) costmap_polygons_write_fleet_kernel(const CmpSceneRec* __restrict__ recs,
+                                                                                   const int* __restrict__ blk0, int n_scenes, int ncnt,
+                                                                                   const int* cnt, CmpOut o) {
+  __shared__ CmpLds s;
+  const CmpSceneRec r = recs[cmp_scene_of_block(blk0, n_scenes, blockIdx.x)];   // by value: the record lives in scalar registers
+  const int blk = blockIdx.x - r.blk0;
+  int rows, verts, pverts;
+  cmp_block(r.g, r.f, r.q, blk, s, rows, verts, pverts);
+  cmp_write_block(r.g, r.q, blk, s, cnt + r.cnt0, cnt + ncnt + r.cnt0, CmpOut{o.off + r.row0, o.x + r.vtx0, o.y + r.vtx0});
 }
 
 }  // namespace tebamd

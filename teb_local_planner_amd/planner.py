@@ -139,6 +139,10 @@ def lib():
             L.teb_amd_is_trajectory_feasible_per_scene.argtypes = [vp, _abi.p_i32, i32, _abi.p_f64, _abi.p_f64, d, d, i32, d, _abi.p_i32, _abi.p_i32]
             L.teb_amd_update_and_prune_per_scene.argtypes = [vp, _abi.p_f64, _abi.p_f64, i32, _abi.p_f64, _abi.p_i32]
             L.teb_amd_get_velocity_commands.argtypes = [vp, i32, _abi.p_i32, i32, i32, _abi.p_f64, _abi.p_i32]
+        if hasattr(L, "teb_amd_set_scenes_from_costmap_polygons"):   # the polygon route of the costmap per scene
+            L.teb_amd_set_scenes_from_costmap_polygons.argtypes = [vp, i32, _abi.p_f64, d, _abi.p_i32, C.POINTER(_abi.Obstacles), _abi.p_i32,
+                                                                   _abi.p_f64, _abi.p_f64, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_f64,
+                                                                   _abi.p_f64, i32, i32]
         _LIB = L
     return _LIB
 
@@ -393,6 +397,42 @@ class TebBatchSolver:
         self._widest_scene = max(int(n[s]) + len(tables[s]) for s in range(ns))
         self._n_scenes = ns
         return n.copy(), [(xs[off[s]:off[s + 1]].copy(), ys[off[s]:off[s + 1]].copy()) for s in range(ns)]
+
+    def set_scenes_from_costmap_polygons(self, robot_poses, costmap_obstacles_behind_robot_dist, tile_cells=8, custom=None, vias=None, return_tables=True):
+        """set_scenes with table s = set_obstacles_from_costmap_polygons' rows of grid s (set_costmaps), robot_poses[s] and the scene's own
+        tile size ++ the rows of custom[s] (ObstacleTable or None entries; None = no custom rows anywhere). tile_cells: an int for every
+        scene or one per scene (sparse maps want 1, structured maps 8: DESIGN.md section 7). Returns the converted rows of every scene
+        as a list of ObstacleTable, in table order; return_tables = False skips the out arrays and the host tables and returns the number
+        of converted rows per scene (what FleetHomotopyClassPlanner.plan wants: it does not look at the rows)."""
+        poses = np.ascontiguousarray(np.asarray(robot_poses, np.float64).reshape(-1, 3))
+        ns = len(poses)
+        tiles = _abi.i32([int(tile_cells)] * ns if np.ndim(tile_cells) == 0 else [int(t) for t in tile_cells])
+        tables = [t if t is not None else _abi.ObstacleTable() for t in (custom if custom is not None else [None] * ns)]
+        if len(tables) != ns or len(tiles) != ns or (vias is not None and len(vias) != ns):
+            raise ValueError("set_scenes_from_costmap_polygons: %d robot poses, %d tile sizes, %d custom tables, %s via-point lists"
+                             % (ns, len(tiles), len(tables), None if vias is None else len(vias)))
+        p = _abi.pack_scenes(tables, vias)
+        cap_o = max(int(self.max_obstacles), 1)
+        cap_p = 2 * cap_o + int(self.max_obstacle_vertices)   # a successful call fits: <= 2 vertices per point / line row
+        n_o = np.zeros(ns, np.int32); n_p = np.zeros(ns, np.int32)
+        off = xs = ys = None
+        if return_tables:
+            off = np.zeros(cap_o + 1, np.int32); xs = np.zeros(cap_p); ys = np.zeros(cap_p)
+        D = lambda a: _abi._ptr(a, C.c_double)
+        I = lambda a: _abi._ptr(a, C.c_int32)
+        _chk(lib().teb_amd_set_scenes_from_costmap_polygons(self._h, ns, D(poses), float(costmap_obstacles_behind_robot_dist), I(tiles), p.obstacles,
+                                                            I(p.via_count), D(p.via_x), D(p.via_y), I(n_o), I(n_p), I(off), D(xs), D(ys), cap_o, cap_p),
+             "teb_amd_set_scenes_from_costmap_polygons")
+        r0 = np.concatenate([[0], np.cumsum(n_o)])
+        self._widest_scene = max(int(n_o[s]) + len(tables[s]) for s in range(ns))
+        self._n_scenes = ns
+        if not return_tables:
+            return n_o.copy()
+        out = []
+        for s in range(ns):
+            o = off[r0[s]:r0[s + 1] + 1]
+            out.append(_abi.ObstacleTable.from_polygon_list(o - o[0], xs[o[0]:o[-1]], ys[o[0]:o[-1]]))
+        return out
 
     def is_trajectory_feasible_per_scene(self, bands, footprint, inscribed_radius, min_resolution_collision_check_angular=3.141592653589793,
                                          look_ahead_idx=-1, feasibility_check_lookahead_distance=-1.0):
@@ -1121,7 +1161,8 @@ class FleetHomotopyClassPlanner:
     explore_candidates_per_scene, one optimize over all bands and select_best_per_scene with switching_blocking_period per robot.
     Every robot's bands end with the bits of a HomotopyClassPlanner of its own whose handle follows the fleet contract of
     include/teb_amd.h. best_teb_ / initial_plan_teb_ [n_robots] are band indices of the batch (-1: none). With costmaps_per_robot,
-    plan() also derives every robot's obstacle table from its own grid (set_costmaps, set_scenes_from_costmaps), and
+    plan() also derives every robot's obstacle table from its own grid (set_costmaps, then set_scenes_from_costmaps or, with
+    costmap_tile_cells, set_scenes_from_costmap_polygons), and
     isTrajectoryFeasible / hasDiverged / getVelocityCommands answer for every robot's best band in one call each.
     randomlyDropTebs is not carried over (selection_dropping_probability > 0: NotImplementedError)."""
 
@@ -1196,15 +1237,21 @@ class FleetHomotopyClassPlanner:
         return self.last_exploration["n_total"]
 
     def plan(self, starts, goals, start_vels=None, obstacles_per_robot=None, via_per_robot=None, free_goal_vel=False, initial_plans=None,
-             now=None, costmaps_per_robot=None, costmap_obstacles_behind_robot_dist=None):
+             now=None, costmaps_per_robot=None, costmap_obstacles_behind_robot_dist=None, costmap_tile_cells=None):
         """plan(start, goal, start_vel, free_goal_vel) of every robot (:107-125), or plan(initial_plan, ...) (:84-96) for the robots with
         an entry in initial_plans ((x, y, yaw) arrays; start / goal are then the plan's first / last pose). starts / goals [n_robots]
         (x, y, theta); start_vels [n_robots] (vx, vy, omega) or None entries; obstacles_per_robot [n_robots] ObstacleTable;
         via_per_robot [n_robots] [(x, y), ...]. costmaps_per_robot [n_robots] (cells, resolution, origin_x, origin_y objects): every
         robot's table is updateObstacleContainerWithCostmap of its own grid seen from starts[r] (costmap_obstacles_behind_robot_dist:
         default cfg.obstacles.costmap_obstacles_behind_robot_dist) followed by obstacles_per_robot[r] as the custom rows, and the grids
-        stay installed for isTrajectoryFeasible. Returns best_teb_."""
+        stay installed for isTrajectoryFeasible. costmap_tile_cells (an int or [n_robots], each 1 .. 64; needs costmaps_per_robot): the
+        lethal cells become convex points / lines / polygons instead (set_scenes_from_costmap_polygons: robot r's grid in tiles of
+        costmap_tile_cells[r] cells); None is the point route. Returns best_teb_."""
         R = self.n_robots
+        if costmap_tile_cells is not None and costmaps_per_robot is None:
+            raise ValueError("FleetHomotopyClassPlanner.plan: costmap_tile_cells needs costmaps_per_robot")
+        if costmap_tile_cells is not None and np.ndim(costmap_tile_cells) != 0 and len(costmap_tile_cells) != R:
+            raise ValueError("FleetHomotopyClassPlanner.plan: %d tile sizes for %d robots" % (len(costmap_tile_cells), R))
         for name, a in (("starts", starts), ("goals", goals), ("start velocities", start_vels), ("obstacle tables", obstacles_per_robot),
                         ("via-point lists", via_per_robot), ("initial plans", initial_plans), ("costmaps", costmaps_per_robot)):
             if a is not None and len(a) != R:
@@ -1221,7 +1268,10 @@ class FleetHomotopyClassPlanner:
         if costmaps_per_robot is not None:
             dist = self.cfg_.obstacles.costmap_obstacles_behind_robot_dist if costmap_obstacles_behind_robot_dist is None else costmap_obstacles_behind_robot_dist
             s.set_costmaps(costmaps_per_robot)
-            s.set_scenes_from_costmaps(starts, dist, tables, vias)
+            if costmap_tile_cells is None:
+                s.set_scenes_from_costmaps(starts, dist, tables, vias)
+            else:
+                s.set_scenes_from_costmap_polygons(starts, dist, costmap_tile_cells, tables, vias, return_tables=False)
         else:
             s.set_scenes(tables, vias)
         self._has_costmaps = costmaps_per_robot is not None
