@@ -872,6 +872,84 @@ int  teb_amd_get_velocity_commands(teb_amd_handle_t* h, int32_t n, const int32_t
                                    int32_t look_ahead_poses, int32_t prevent_look_ahead_poses_near_goal, double* cmd /* [n][3] */,
                                    int32_t* ok /* [n] */);
 
+/*
+ * ---- Local plan windows per robot from resident global plans ---------------------------------------------------------------------------
+ * What TebLocalPlannerROS::computeVelocityCommands derives from the robot's global plan and pose before it calls plan()
+ * (src/teb_local_planner_ros.cpp:268-340): pruneGlobalPlan (:657-698), transformGlobalPlan (:701-822), updateViaPointsContainer
+ * (:627-645), estimateLocalGoalOrientation (:827-871), the start replacement (:336-340) and the transformed global goal of the
+ * goal-reached test (:291-292) - for every robot of a fleet in ONE launch (csrc/teb_plan_window.hpp: one workgroup per robot). The
+ * global plans live on the device like the costmaps; per tick only the poses go in. tf is the caller's: the plan -> global transform
+ * arrives as five doubles (cos, sin, tx, ty, yaw_tf), cos and sin computed on the host, so the device transform is products and sums.
+ * Every index and count is the reference's sequential decision bit for bit; positions and copied yaws are plain IEEE products and sums.
+ *
+ * The parameters are the four of cfg_.trajectory the adapter reads (teb_config.h:259-264) and the moving_average_length default of
+ * estimateLocalGoalOrientation (teb_local_planner_ros.h); they are no part of teb_amd_config_t.
+ */
+typedef struct teb_amd_plan_window_params {
+  int32_t struct_size;                        /* sizeof(teb_amd_plan_window_params_t), set by teb_amd_plan_window_params_default  */
+  double  global_plan_prune_distance;         /* 1                                                                                */
+  double  max_global_plan_lookahead_dist;     /* 1; <= 0: no length cut                                                           */
+  double  global_plan_viapoint_sep;           /* -1; <= 0: no via-points                                                          */
+  int32_t global_plan_overwrite_orientation;  /* 1                                                                                */
+  int32_t moving_average_length;              /* 3                                                                                */
+} teb_amd_plan_window_params_t;
+void teb_amd_plan_window_params_default(teb_amd_plan_window_params_t* p);
+int  teb_amd_sizeof_plan_window_params(void);
+/*
+ *   teb_amd_set_global_plans  n plans, plan r = plan_count[r] poses (x, y, yaw) in the plan frame, the plans one after the other in
+ *                            x / y / yaw; ONE device buffer, sized by the call. begin [n] (NULL = zeros) is the pruning cursor of every
+ *                            robot: what pruneGlobalPlan has erased so far; a caller that replaces one robot's plan passes the other
+ *                            robots' cursors (teb_amd_get_plan_cursors) to keep them. State of the handle beside the costmap set and
+ *                            the scene set: it touches neither and is valid in single-scene and fleet mode. n = 0 drops the set.
+ *                            TEB_AMD_ERR_CAPACITY: n > max_tebs. TEB_AMD_ERR_INVALID_ARG: n < 0, null plan_count, a count < 0, a cursor
+ *                            outside 0 .. count, a null array while the counts sum to more than 0. Everything is checked before the
+ *                            first upload: on an argument or capacity error, or a failed device allocation, the previous set
+ *                            stays. A device error during the upload itself (TEB_AMD_ERR_HIP) leaves the handle without a set.
+ *   teb_amd_plan_windows     the windows of all n robots (n = size of the plan set, else TEB_AMD_ERR_INVALID_ARG; so is a call without
+ *                            a set, null robot_pose / dist_threshold, a params struct of another size, a negative capacity).
+ *                            robot_pose [3 n] = (x, y, theta) in the global frame; plan_to_global [5 n] or NULL = identity;
+ *                            dist_threshold [n] = the reference's 0.85 * max(size_x, size_y) * resolution / 2 of every robot's costmap
+ *                            (:729-731). params NULL = the defaults. Steps per robot, every index relative to the cursor:
+ *                              robot in the plan frame  R^T (g - t);
+ *                              prune      first pose with squared distance < prune_distance^2 becomes the cursor (pruned = 1); none:
+ *                                         the cursor stays, pruned = 0;
+ *                              closest    i = first index of the minimum squared distance over the poses scanned; the scan ends at the
+ *                                         first pose farther than the running minimum once that minimum is < 0.05 (a loop in the
+ *                                         path: the first local minimum wins); sq_dist starts at 1e10;
+ *                              window     poses i .. k_end - 1: pose k is taken while the previous squared distance <= dist_threshold^2
+ *                                         and (lookahead <= 0 or plan_length <= lookahead), plan_length += |p(k-1) p(k)| after pose k
+ *                                         (k > 0), summed in that order; goal_idx = k_end - 1; an empty window: the global goal alone,
+ *                                         goal_idx = N - 1;
+ *                              transform  R p + t; yaw unchanged when yaw_tf == 0, else g2o::normalize_theta(yaw + yaw_tf);
+ *                              via-points from the last accepted pose (first: pose 0 of the window) the first later pose at distance
+ *                                         >= global_plan_viapoint_sep, on the transformed window before its first pose is replaced;
+ *                              goal       position of the window's last pose; yaw, when global_plan_overwrite_orientation: its own
+ *                                         (goal_idx >= N - 1), the global goal's transformed yaw (goal_idx > N - moving_average_length
+ *                                         - 2), else average_angles of up to moving_average_length headings between consecutive
+ *                                         transformed poses after goal_idx; the window's last yaw becomes the goal yaw;
+ *                              start      a one-pose window gets a pose inserted in front; pose 0 becomes robot_pose.
+ *                            Outputs per robot, each may be NULL: window_count [n] (poses of the delivered window, start insertion
+ *                            included), goal_idx [n], cursor [n] (the new begin, also kept on the device for the next call), pruned
+ *                            [n], goal [3 n], global_goal [3 n] (the plan's last pose, transformed), via_count [n]; offset [n + 1] with
+ *                            win_x / win_y / win_yaw [capacity_window] and via_offset [n + 1] with via_x / via_y [capacity_via]: the
+ *                            windows / via-points of the robots one after the other. Counts, offsets and per-robot values are always
+ *                            delivered; the concatenated arrays are written only when they fit, otherwise the call returns
+ *                            TEB_AMD_ERR_CAPACITY (the cursors have moved all the same). One launch; one download for the per-robot
+ *                            records, one for the arrays. A robot with an empty plan (count 0, or a cursor at its end) returns
+ *                            window_count = 0, goal_idx = 0, pruned = 1 and zeros.
+ *   teb_amd_get_plan_cursors begin [n of the set]; without a set TEB_AMD_ERR_INVALID_ARG.
+ * All three refuse a null handle with TEB_AMD_ERR_INVALID_ARG before touching it, and are part of every library variant.
+ */
+int  teb_amd_set_global_plans(teb_amd_handle_t* h, int32_t n, const int32_t* plan_count /* [n] */, const double* x, const double* y,
+                              const double* yaw /* concatenated */, const int32_t* begin /* [n] or NULL = 0 */);
+int  teb_amd_plan_windows(teb_amd_handle_t* h, int32_t n, const teb_amd_plan_window_params_t* params, const double* robot_pose /* [3 n] */,
+                          const double* plan_to_global /* [5 n] or NULL */, const double* dist_threshold /* [n] */,
+                          int32_t* window_count, int32_t* goal_idx, int32_t* cursor, int32_t* pruned /* [n] each */,
+                          double* goal /* [3 n] */, double* global_goal /* [3 n] */, int32_t* via_count /* [n] */,
+                          int32_t* offset /* [n + 1] */, double* win_x, double* win_y, double* win_yaw, int32_t capacity_window,
+                          int32_t* via_offset /* [n + 1] */, double* via_x, double* via_y, int32_t capacity_via);
+int  teb_amd_get_plan_cursors(teb_amd_handle_t* h, int32_t* begin /* [n] */);
+
 #ifdef __cplusplus
 }
 #endif

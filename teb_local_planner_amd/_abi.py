@@ -91,6 +91,23 @@ class HcpParams(C.Structure):
     ]
 
 
+class PlanWindowParams(C.Structure):
+    """teb_amd_plan_window_params_t (include/teb_amd.h): what the adapter reads from cfg_.trajectory for the plan window
+    (teb_config.h:259-264) and estimateLocalGoalOrientation's moving_average_length. No part of Config / TebConfig."""
+    _fields_ = [("struct_size", c_i32), ("global_plan_prune_distance", c_f64), ("max_global_plan_lookahead_dist", c_f64),
+                ("global_plan_viapoint_sep", c_f64), ("global_plan_overwrite_orientation", c_i32), ("moving_average_length", c_i32)]
+
+    def __init__(self, global_plan_prune_distance=1.0, max_global_plan_lookahead_dist=1.0, global_plan_viapoint_sep=-1.0,
+                 global_plan_overwrite_orientation=True, moving_average_length=3):
+        super().__init__()
+        self.struct_size = C.sizeof(PlanWindowParams)
+        self.global_plan_prune_distance = float(global_plan_prune_distance)
+        self.max_global_plan_lookahead_dist = float(max_global_plan_lookahead_dist)
+        self.global_plan_viapoint_sep = float(global_plan_viapoint_sep)
+        self.global_plan_overwrite_orientation = int(bool(global_plan_overwrite_orientation))
+        self.moving_average_length = int(moving_average_length)
+
+
 LAYOUT_AUTO, LAYOUT_BLOCKS_LDS, LAYOUT_BAND_LDS, LAYOUT_BAND_HBM = 0, 1, 2, 3
 HSIG3D_AUTO, HSIG3D_WIDE, HSIG3D_SMALL = 0, 1, 2
 

@@ -28,6 +28,7 @@
 #include "teb_feasibility.hpp"
 #include "teb_costmap_obstacles.hpp"
 #include "teb_costmap_polygons.hpp"
+#include "teb_plan_window.hpp"
 #include "teb_scene_store.hpp"
 
 using namespace tebamd;
@@ -225,6 +226,20 @@ struct teb_amd_handle {
   // and the 3 x n_scenes totals
   DevBuf<CmpSceneRec> cmp_rec;
   DevBuf<int> cmp_blk, cmp_tot;
+  // the global plans (teb_amd_set_global_plans): the plans of every robot one after the other in ONE buffer (x | y | yaw planes of
+  // `total` poses), their first poses, counts and pruning cursors, and the scratch of teb_amd_plan_windows: the poses / transforms /
+  // thresholds of a call, the per-robot records, the pack buffer of the windows and via-points and its ticket. Beside the costmap set
+  // and the scene set; touches neither.
+  struct PlanSet {
+    int n = 0;   // 0 = none
+    size_t total = 0;
+    DevBuf<double> poses, in, pack;
+    DevBuf<long long> first;
+    DevBuf<int> count, cursor;
+    DevBuf<PlanWinOut> rec;
+    DevBuf<unsigned long long> ticket;
+    std::vector<int> count_host;
+  } plans;
   std::mt19937 rnd_generator;   // ProbRoadmapGraph::rnd_generator_ (graph_search.h:211): default-seeded 32-bit Mersenne twister
   // fleet batches (teb_fleet.hpp, teb_amd_set_scenes): the scene set - a second DevSceneStore, allocated at the first
   // teb_amd_set_scenes and sized by the capacities of the handle, with the rows, vertices and via-points of the scenes one after the
@@ -866,7 +881,8 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
            h->cand_y, h->cand_th, h->cand_dt, h->cand_sig, h->cand_px, h->cand_py, h->tmp_x, h->tmp_y, h->tmp_th, h->tmp_dt, h->tmp_vs, h->tmp_vg, h->tmp_chi2,
            h->tmp_cost, h->tmp_lambda, h->cand_n, h->cand_off, h->cand_map, h->tmp_n, h->tmp_i, h->iter_log, h->phase_log, h->mcu_ctl, h->mcu_pub, h->mcu_items,
            h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cmo_cnt, h->cmp_cnt, h->cmp_off, h->cmp_x, h->cmp_y, h->cmp_rec, h->cmp_blk, h->cmp_tot,
-           h->cms.cells, h->cms.grids, h->cms_rec, h->cms_tot, h->cms_bands, h->cms_px, h->cms_py, h->prune_msg);
+           h->cms.cells, h->cms.grids, h->cms_rec, h->cms_tot, h->cms_bands, h->cms_px, h->cms_py, h->prune_msg,
+           h->plans.poses, h->plans.in, h->plans.pack, h->plans.first, h->plans.count, h->plans.cursor, h->plans.rec, h->plans.ticket);
   if (h->mcu_trace) (void)hipHostFree(h->mcu_trace);
   if (h->pack_host) (void)hipHostFree(h->pack_host);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -2694,6 +2710,178 @@ int teb_amd_get_velocity_commands(teb_amd_handle_t* h, int32_t n, const int32_t*
     cmd[3 * i] = q ? q[0] : 0.0; cmd[3 * i + 1] = q ? q[1] : 0.0; cmd[3 * i + 2] = q ? q[2] : 0.0;
     ok[i] = q ? q[3] != 0 : 0;
   }
+  return TEB_AMD_OK;
+}
+
+// ---- local plan windows per robot from resident global plans (teb_amd.h; kernel in teb_plan_window.hpp) ----------------------------
+void teb_amd_plan_window_params_default(teb_amd_plan_window_params_t* p) {   // teb_config.h:261-264; moving_average_length: teb_local_planner_ros.h
+  if (!p) return;
+  std::memset(p, 0, sizeof(*p));
+  p->struct_size = (int32_t)sizeof(*p);
+  p->global_plan_prune_distance = 1; p->max_global_plan_lookahead_dist = 1; p->global_plan_viapoint_sep = -1;
+  p->global_plan_overwrite_orientation = 1; p->moving_average_length = 3;
+}
+int teb_amd_sizeof_plan_window_params(void) { return (int)sizeof(teb_amd_plan_window_params_t); }
+
+int teb_amd_set_global_plans(teb_amd_handle_t* h, int32_t n, const int32_t* plan_count, const double* x, const double* y, const double* yaw,
+                             const int32_t* begin) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  auto& P = h->plans;
+  const char* fn = "teb_amd_set_global_plans: ";
+  if (n < 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "negative number of plans");
+  if (n == 0) { P.n = 0; P.total = 0; P.count_host.clear(); return TEB_AMD_OK; }
+  if (n > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "more plans than max_tebs");
+  if (!plan_count) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null plan_count");
+  // everything is checked before the first upload: on a bad argument the previous set stays
+  std::vector<long long> first(n);
+  std::vector<int> cur(n, 0);
+  size_t total = 0;
+  for (int r = 0; r < n; ++r) {
+    if (plan_count[r] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "negative pose count");
+    if (begin && (begin[r] < 0 || begin[r] > plan_count[r])) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "cursor outside 0 .. count");
+    first[r] = (long long)total;
+    total += (size_t)plan_count[r];
+    if (begin) cur[r] = begin[r];
+  }
+  if (total > 0 && (!x || !y || !yaw)) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null pose array");
+  // The per-robot buffers of the first call, all six or none: a failed allocation frees what it got, so a later call tries again
+  // (no previous set exists yet at that point).
+  if (!P.first.p || !P.count.p || !P.cursor.p || !P.rec.p || !P.in.p || !P.ticket.p) {
+    const size_t T = (size_t)h->max_tebs;
+    free_all(P.first, P.count, P.cursor, P.rec, P.in, P.ticket);
+    if (P.first.alloc(T) != hipSuccess || P.count.alloc(T) != hipSuccess || P.cursor.alloc(T) != hipSuccess || P.rec.alloc(T) != hipSuccess ||
+        P.in.alloc(9 * T) != hipSuccess || P.ticket.alloc(1) != hipSuccess) {
+      (void)hipGetLastError();
+      free_all(P.first, P.count, P.cursor, P.rec, P.in, P.ticket);
+      return fail(TEB_AMD_ERR_HIP, std::string(fn) + "device allocation failed");
+    }
+  }
+  // the new buffers before the old ones go: a failed allocation leaves the previous set. A window holds at most the poses of its plan
+  // and the inserted start, so 5 (total + n) doubles hold the windows and via-points of every robot (PlanWinOut::alloc).
+  if (P.poses.n < 3 * total || P.pack.n < 5 * (total + (size_t)h->max_tebs)) {
+    DevBuf<double> np, nk;
+    if (np.alloc(3 * total) != hipSuccess || nk.alloc(5 * (total + (size_t)h->max_tebs)) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+      (void)hipGetLastError(); np.free(); nk.free();
+      return fail(TEB_AMD_ERR_HIP, std::string(fn) + "device allocation failed");
+    }
+    P.poses.free(); P.pack.free();
+    P.poses = np; P.pack = nk;
+  }
+  P.n = 0;   // from here on the previous plans are overwritten: a HIP error leaves no set
+  P.count_host.clear();
+  HIPCHK(upload(h->stream, P.poses.p, x, total));
+  HIPCHK(upload(h->stream, P.poses.p + total, y, total));
+  HIPCHK(upload(h->stream, P.poses.p + 2 * total, yaw, total));
+  HIPCHK(upload(h->stream, P.first.p, first.data(), (size_t)n));
+  HIPCHK(upload(h->stream, P.count.p, plan_count, (size_t)n));
+  HIPCHK(upload(h->stream, P.cursor.p, cur.data(), (size_t)n));
+  HIPCHK(hipStreamSynchronize(h->stream));   // the caller's buffers may go away
+  P.count_host.assign(plan_count, plan_count + n);
+  P.total = total;
+  P.n = n;
+  return TEB_AMD_OK;
+}
+
+int teb_amd_get_plan_cursors(teb_amd_handle_t* h, int32_t* begin) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (h->plans.n == 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_plan_cursors: no global plans set (teb_amd_set_global_plans)");
+  if (!begin) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_plan_cursors: null argument");
+  HIPCHK(hipMemcpyAsync(begin, h->plans.cursor.p, (size_t)h->plans.n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return TEB_AMD_OK;
+}
+
+int teb_amd_plan_windows(teb_amd_handle_t* h, int32_t n, const teb_amd_plan_window_params_t* params, const double* robot_pose,
+                         const double* plan_to_global, const double* dist_threshold, int32_t* window_count, int32_t* goal_idx,
+                         int32_t* cursor, int32_t* pruned, double* goal, double* global_goal, int32_t* via_count, int32_t* offset,
+                         double* win_x, double* win_y, double* win_yaw, int32_t capacity_window, int32_t* via_offset, double* via_x,
+                         double* via_y, int32_t capacity_via) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  auto& P = h->plans;
+  const char* fn = "teb_amd_plan_windows: ";
+  if (P.n == 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "no global plans set (teb_amd_set_global_plans)");
+  if (n != P.n) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "the plan set holds another number of robots");
+  if (!robot_pose || !dist_threshold || capacity_window < 0 || capacity_via < 0)
+    return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "needs the robot poses, the distance thresholds and capacities >= 0");
+  teb_amd_plan_window_params_t prm;
+  teb_amd_plan_window_params_default(&prm);
+  if (params) {
+    if (params->struct_size != (int32_t)sizeof(prm)) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "params of another struct_size");
+    prm = *params;
+  }
+  const size_t N = (size_t)n;
+  // one upload of what changes per tick: poses [3 n] | thresholds [n] | transforms [5 n]
+  std::vector<double> in(9 * N);
+  std::copy(robot_pose, robot_pose + 3 * N, in.begin());
+  std::copy(dist_threshold, dist_threshold + N, in.begin() + 3 * N);
+  if (plan_to_global) std::copy(plan_to_global, plan_to_global + 5 * N, in.begin() + 4 * N);
+  HIPCHK(upload(h->stream, P.in.p, in.data(), plan_to_global ? 9 * N : 4 * N));
+  HIPCHK(hipMemsetAsync(P.ticket.p, 0, sizeof(unsigned long long), h->stream));
+  PlanWinArgs a;
+  a.px = P.poses.p; a.py = P.poses.p + P.total; a.pyaw = P.poses.p + 2 * P.total;
+  a.first = P.first.p; a.count = P.count.p; a.cursor = P.cursor.p;
+  a.pose = P.in.p; a.thr = P.in.p + 3 * N; a.tf = plan_to_global ? P.in.p + 4 * N : nullptr;
+  a.prune_distance = prm.global_plan_prune_distance; a.max_plan_length = prm.max_global_plan_lookahead_dist;
+  a.via_sep = prm.global_plan_viapoint_sep;
+  a.overwrite_orientation = prm.global_plan_overwrite_orientation; a.moving_average_length = prm.moving_average_length;
+  a.out = P.rec.p; a.pack = P.pack.p; a.ticket = P.ticket.p; a.pack_capacity = (long long)P.pack.n;
+  hipLaunchKernelGGL(plan_window_kernel, dim3((unsigned)n), dim3(kPwThreads), 0, h->stream, a);
+  HIPCHK(hipGetLastError());
+  std::vector<PlanWinOut> rec(N);
+  HIPCHK(hipMemcpyAsync(rec.data(), P.rec.p, N * sizeof(PlanWinOut), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // offset bookkeeping: the per-robot values, the offsets of the concatenations, what the pack buffer holds
+  long long nw = 0, nv = 0, used = 0;
+  for (size_t r = 0; r < N; ++r) {
+    const PlanWinOut& q = rec[r];
+    if (q.window_count > 0 && (q.off < 0 || q.off + 5ll * q.alloc > (long long)P.pack.n || q.window_count > q.alloc || q.via_count > q.alloc))
+      return fail(TEB_AMD_ERR_HIP, std::string(fn) + "a window left its block of the pack buffer");
+    if (window_count) window_count[r] = q.window_count;
+    if (goal_idx) goal_idx[r] = q.goal_idx;
+    if (cursor) cursor[r] = q.cursor;
+    if (pruned) pruned[r] = q.pruned;
+    if (via_count) via_count[r] = q.via_count;
+    if (goal) std::copy(q.goal, q.goal + 3, goal + 3 * r);
+    if (global_goal) std::copy(q.global_goal, q.global_goal + 3, global_goal + 3 * r);
+    if (offset) offset[r] = (int32_t)nw;
+    if (via_offset) via_offset[r] = (int32_t)nv;
+    nw += q.window_count; nv += q.via_count;
+    if (q.window_count > 0) used = std::max(used, q.off + 5ll * q.alloc);
+  }
+  if (nw > std::numeric_limits<int32_t>::max()) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "more window poses than an offset holds");
+  if (offset) offset[N] = (int32_t)nw;
+  if (via_offset) via_offset[N] = (int32_t)nv;
+  const bool want_win = win_x || win_y || win_yaw, want_via = via_x || via_y;
+  const bool win_fits = nw <= capacity_window, via_fits = nv <= capacity_via;
+  if ((want_win && win_fits && nw > 0) || (want_via && via_fits && nv > 0)) {
+    std::vector<double> pack((size_t)used);
+    HIPCHK(hipMemcpyAsync(pack.data(), P.pack.p, (size_t)used * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    long long iw = 0, iv = 0;
+    for (size_t r = 0; r < N; ++r) {
+      const PlanWinOut& q = rec[r];
+      if (q.window_count > 0) {
+        const double* b = pack.data() + q.off;
+        const size_t A = (size_t)q.alloc, W = (size_t)q.window_count, V = (size_t)q.via_count;
+        if (want_win && win_fits) {
+          if (win_x) std::copy(b, b + W, win_x + iw);
+          if (win_y) std::copy(b + A, b + A + W, win_y + iw);
+          if (win_yaw) std::copy(b + 2 * A, b + 2 * A + W, win_yaw + iw);
+        }
+        if (want_via && via_fits) {
+          if (via_x) std::copy(b + 3 * A, b + 3 * A + V, via_x + iv);
+          if (via_y) std::copy(b + 4 * A, b + 4 * A + V, via_y + iv);
+        }
+      }
+      iw += q.window_count; iv += q.via_count;
+    }
+  }
+  if ((want_win && !win_fits) || (want_via && !via_fits))
+    return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "the windows or the via-points exceed the caller's arrays");
   return TEB_AMD_OK;
 }
 

@@ -14,7 +14,7 @@ import os
 import numpy as np
 
 from . import _abi
-from .config import TebConfig
+from .config import TebConfig, normalize_theta
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -143,6 +143,14 @@ def lib():
             L.teb_amd_set_scenes_from_costmap_polygons.argtypes = [vp, i32, _abi.p_f64, d, _abi.p_i32, C.POINTER(_abi.Obstacles), _abi.p_i32,
                                                                    _abi.p_f64, _abi.p_f64, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_f64,
                                                                    _abi.p_f64, i32, i32]
+        if hasattr(L, "teb_amd_plan_windows"):   # local plan windows per robot from resident global plans
+            L.teb_amd_plan_window_params_default.argtypes = [C.POINTER(_abi.PlanWindowParams)]
+            L.teb_amd_plan_window_params_default.restype = None
+            L.teb_amd_set_global_plans.argtypes = [vp, i32, _abi.p_i32, _abi.p_f64, _abi.p_f64, _abi.p_f64, _abi.p_i32]
+            L.teb_amd_plan_windows.argtypes = [vp, i32, C.POINTER(_abi.PlanWindowParams), _abi.p_f64, _abi.p_f64, _abi.p_f64, _abi.p_i32, _abi.p_i32,
+                                               _abi.p_i32, _abi.p_i32, _abi.p_f64, _abi.p_f64, _abi.p_i32, _abi.p_i32, _abi.p_f64, _abi.p_f64,
+                                               _abi.p_f64, i32, _abi.p_i32, _abi.p_f64, _abi.p_f64, i32]
+            L.teb_amd_get_plan_cursors.argtypes = [vp, _abi.p_i32]
         _LIB = L
     return _LIB
 
@@ -166,6 +174,7 @@ class TebBatchSolver:
         self.max_tebs, self.max_poses, self.max_obstacles = max_tebs, max_poses, max_obstacles
         self.max_obstacle_vertices = max_obstacle_vertices
         self.count = 0
+        self._plan_counts = None   # pose counts of the resident global plans (set_global_plans)
 
     def close(self):
         if self._h:
@@ -468,6 +477,83 @@ class TebBatchSolver:
         _chk(lib().teb_amd_get_velocity_commands(self._h, n, _abi._ptr(bd, C.c_int32), int(look_ahead_poses), int(prevent_look_ahead_poses_near_goal),
                                                  _abi._ptr(cmd, C.c_double), _abi._ptr(ok, C.c_int32)), "teb_amd_get_velocity_commands")
         return ok[:n].astype(bool), cmd[:n].copy()
+
+    # -- local plan windows per robot from resident global plans (include/teb_amd.h) ---------------------------
+    def set_global_plans(self, plans, begin=None):
+        """plans[r] = (x, y, yaw) arrays of robot r's global plan in the plan frame (None or empty arrays: no plan); begin [n] or None =
+        zeros: the pruning cursors. An empty list drops the set."""
+        plans = [(_abi.f64([]),) * 3 if p is None else tuple(_abi.f64(a).reshape(-1) for a in p) for p in plans]
+        n = len(plans)
+        if n == 0:
+            _chk(lib().teb_amd_set_global_plans(self._h, 0, None, None, None, None, None), "teb_amd_set_global_plans")
+            self._plan_counts = None
+            return
+        for p in plans:
+            if len(p) != 3 or not (len(p[0]) == len(p[1]) == len(p[2])):
+                raise ValueError("set_global_plans: a plan is three arrays (x, y, yaw) of one length")
+        cnt = _abi.i32([len(p[0]) for p in plans])
+        cat = lambda k: _abi.f64(np.concatenate([p[k] for p in plans])) if cnt.sum() else _abi.f64([0.0])
+        x, y, yaw = cat(0), cat(1), cat(2)
+        bg = None if begin is None else _abi.i32(begin)
+        if bg is not None and len(bg) != n:
+            raise ValueError("set_global_plans: %d cursors for %d plans" % (len(bg), n))
+        D = lambda a: _abi._ptr(a, C.c_double)
+        _chk(lib().teb_amd_set_global_plans(self._h, n, _abi._ptr(cnt, C.c_int32), D(x), D(y), D(yaw), _abi._ptr(bg, C.c_int32)),
+             "teb_amd_set_global_plans")
+        self._plan_counts = cnt.copy()
+
+    def plan_cursors(self):
+        """The pruning cursors of the resident plans [n]."""
+        if self._plan_counts is None:
+            raise ValueError("plan_cursors: no global plans set")
+        b = np.zeros(len(self._plan_counts), np.int32)
+        _chk(lib().teb_amd_get_plan_cursors(self._h, _abi._ptr(b, C.c_int32)), "teb_amd_get_plan_cursors")
+        return b
+
+    def plan_windows(self, robot_poses, dist_thresholds, params=None, plan_to_global=None, capacity_window=None, capacity_via=None):
+        """teb_amd_plan_windows for the resident plans: robot_poses [n, 3] in the global frame, dist_thresholds [n] (the reference's
+        0.85 * max(size_x, size_y) * resolution / 2), plan_to_global [n, 5] = (cos, sin, tx, ty, yaw_tf) or None = identity, params a
+        _abi.PlanWindowParams or None = defaults. Returns a dict: window_count, goal_idx, cursor, pruned, via_count [n] int32; goal,
+        global_goal [n, 3]; offset, via_offset [n + 1]; win_x, win_y, win_yaw, via_x, via_y concatenated; windows [n] = (x, y, yaw)
+        per robot and vias [n] = [(x, y), ...] per robot. The capacities default to what always fits."""
+        if self._plan_counts is None:
+            raise ValueError("plan_windows: no global plans set")
+        n = len(self._plan_counts)
+        poses = np.ascontiguousarray(np.asarray(robot_poses, np.float64).reshape(-1, 3))
+        thr = _abi.f64(dist_thresholds).reshape(-1)
+        tf = None if plan_to_global is None else np.ascontiguousarray(np.asarray(plan_to_global, np.float64).reshape(-1, 5))
+        if len(poses) != n or len(thr) != n or (tf is not None and len(tf) != n):
+            raise ValueError("plan_windows: %d plans, %d poses, %d thresholds, %s transforms" % (n, len(poses), len(thr), None if tf is None else len(tf)))
+        cap = int(self._plan_counts.sum()) + n
+        cw = cap if capacity_window is None else int(capacity_window)
+        cv = cap if capacity_via is None else int(capacity_via)
+        I = lambda a: _abi._ptr(a, C.c_int32)
+        D = lambda a: _abi._ptr(a, C.c_double)
+        o = {k: np.zeros(n, np.int32) for k in ("window_count", "goal_idx", "cursor", "pruned", "via_count")}
+        o["goal"] = np.zeros((n, 3)); o["global_goal"] = np.zeros((n, 3))
+        o["offset"] = np.zeros(n + 1, np.int32); o["via_offset"] = np.zeros(n + 1, np.int32)
+        for k in ("win_x", "win_y", "win_yaw"):
+            o[k] = np.zeros(max(cw, 1))
+        for k in ("via_x", "via_y"):
+            o[k] = np.zeros(max(cv, 1))
+        rc = lib().teb_amd_plan_windows(self._h, n, C.byref(params) if params is not None else None, D(poses), D(tf), D(thr), I(o["window_count"]),
+                                        I(o["goal_idx"]), I(o["cursor"]), I(o["pruned"]), D(o["goal"]), D(o["global_goal"]), I(o["via_count"]),
+                                        I(o["offset"]), D(o["win_x"]), D(o["win_y"]), D(o["win_yaw"]), cw, I(o["via_offset"]), D(o["via_x"]),
+                                        D(o["via_y"]), cv)
+        if rc == _abi.ERR_CAPACITY and (capacity_window is not None or capacity_via is not None):
+            o["status"] = rc   # the caller chose the capacities: counts and per-robot values are delivered, the arrays untouched
+            return o
+        _chk(rc, "teb_amd_plan_windows")
+        o["status"] = rc
+        off, voff = o["offset"], o["via_offset"]
+        for k in ("win_x", "win_y", "win_yaw"):
+            o[k] = o[k][:off[n]]
+        for k in ("via_x", "via_y"):
+            o[k] = o[k][:voff[n]]
+        o["windows"] = [(o["win_x"][off[r]:off[r + 1]].copy(), o["win_y"][off[r]:off[r + 1]].copy(), o["win_yaw"][off[r]:off[r + 1]].copy())
+                        for r in range(n)]
+        o["vias"] = [list(zip(o["via_x"][voff[r]:voff[r + 1]].tolist(), o["via_y"][voff[r]:voff[r + 1]].tolist())) for r in range(n)]
+        return o
 
     # -- state ---------------------------------------------------------------------------------------
     def upload(self, batch):
@@ -1182,6 +1268,8 @@ class FleetHomotopyClassPlanner:
         self._last_switch = [0.0] * self.n_robots
         self._last_best_teb = np.full(self.n_robots, -1, np.int32)
         self._has_costmaps = False
+        self._plans = None                                          # setPlans: the global plans as given, resident on the device
+        self.no_infeasible_plans_ = np.zeros(self.n_robots, np.int32)   # computeVelocityCommands: failures in a row, robot by robot
 
     def bands_of(self, r):
         """band indices of robot r, in band order"""
@@ -1394,6 +1482,171 @@ class FleetHomotopyClassPlanner:
     def results(self):
         self.last_results = self.solver.results()
         return self.last_results
+
+    # ---- the adapter's entry point (TebLocalPlannerROS::computeVelocityCommands, src/teb_local_planner_ros.cpp:236-462) of every robot ----
+    def clearPlanner(self, r):
+        """HomotopyClassPlanner::clearPlanner of robot r (an index or a list of them): its bands leave the batch in one compaction, the other
+        robots' bands keep their order; its next plan() starts from new candidates."""
+        s = self.solver
+        rs = [int(r)] if np.ndim(r) == 0 else [int(k) for k in r]
+        for k in rs:
+            self.best_teb_[k] = self.initial_plan_teb_[k] = self._last_best_teb[k] = -1
+            self._goal[k] = None
+        if s.count == 0 or not rs:
+            return
+        keep = (~np.isin(s.band_scenes(), rs)).astype(np.int32)
+        if keep.all():
+            return
+        at = (np.cumsum(keep) - 1).astype(np.int32)
+        move = lambda a: np.array([at[b] if b >= 0 else -1 for b in a], np.int32)
+        self.best_teb_, self.initial_plan_teb_, self._last_best_teb = move(self.best_teb_), move(self.initial_plan_teb_), move(self._last_best_teb)
+        s.compact_bands_per_scene(keep, None)
+
+    def setPlans(self, plans, robots=None):
+        """setPlan of every robot: plans[r] = (x, y, yaw) arrays in the plan frame (None: no plan), resident on the device from here on.
+        With robots given, plans holds the new plans of those robots only; the others keep theirs and their pruning cursors."""
+        R = self.n_robots
+        if self._plans is None:
+            self._plans = [None] * R
+        if robots is None:
+            if len(plans) != R:
+                raise ValueError("FleetHomotopyClassPlanner.setPlans: %d plans for %d robots" % (len(plans), R))
+            self._plans = list(plans)
+            begin = None
+        else:
+            if len(plans) != len(robots):
+                raise ValueError("FleetHomotopyClassPlanner.setPlans: %d plans for %d robots to replace" % (len(plans), len(robots)))
+            begin = self.solver.plan_cursors() if self.solver._plan_counts is not None else np.zeros(R, np.int32)
+            for r, p in zip(robots, plans):
+                self._plans[int(r)] = p
+                begin[int(r)] = 0
+        self.solver.set_global_plans(self._plans, begin)
+
+    def computeVelocityCommands(self, robot_poses, robot_vels, costmaps_per_robot, footprint_spec, inscribed_radius, adapter=None,
+                                plan_to_global=None, now=None, window_params=None, obstacles_per_robot=None,
+                                costmap_obstacles_behind_robot_dist=None, costmap_tile_cells=None):
+        """computeVelocityCommands of every robot at once, in the reference's order: the plan windows from the resident global plans
+        (setPlans) and robot_poses [n_robots] (x, y, theta), thresholds from every grid's size (:729-731); the goal-reached test
+        (:290-304); plan(initial_plans = windows, via_per_robot = the windows' via-points, costmaps_per_robot) for the others; hasDiverged,
+        isTrajectoryFeasible, getVelocityCommands; saturateVelocity and, with adapter.cmd_angle_instead_rotvel, the steering angle.
+        robot_vels [n_robots] (vx, vy, omega) is the odometry twist; adapter: adapter_defaults() or alike; plan_to_global [n_robots, 5]
+        = (cos, sin, tx, ty, yaw_tf) or None; window_params: _abi.PlanWindowParams or None. Returns (status [n_robots], cmd [n_robots, 3]):
+        SUCCESS with the saturated command, GOAL_REACHED / NO_VALID_CMD / INTERNAL_ERROR (a robot without a plan) with a zero command. A
+        robot with NO_VALID_CMD has its bands dropped (clearPlanner) and no_infeasible_plans_[r] incremented; a success resets it.
+        cfg.robot.max_vel_trans is used as it stands: the reference's reconfigure step sets it to max_vel_x when it is 0
+        (src/teb_config.cpp:219-223), and a caller does the same in cfg.robot - at 0 saturateVelocity scales vx and vy to 0.
+        last_tick holds the windows, the raw commands and the verdicts of the call."""
+        import math
+        R, t = self.n_robots, self.cfg_.trajectory
+        a = adapter if adapter is not None else adapter_defaults()
+        if self._plans is None:
+            raise ValueError("FleetHomotopyClassPlanner.computeVelocityCommands: setPlans first")
+        poses = [tuple(float(v) for v in p) for p in robot_poses]
+        vels = [tuple(float(v) for v in p) for p in robot_vels]
+        if len(poses) != R or len(vels) != R or len(costmaps_per_robot) != R:
+            raise ValueError("FleetHomotopyClassPlanner.computeVelocityCommands: %d poses, %d velocities, %d costmaps for %d robots"
+                             % (len(poses), len(vels), len(costmaps_per_robot), R))
+        thr = []
+        for c in costmaps_per_robot:
+            sy, sx = np.shape(c.cells)
+            thr.append(max(sx * c.resolution / 2.0, sy * c.resolution / 2.0) * 0.85)
+        win = self.solver.plan_windows(poses, thr, window_params, plan_to_global)
+        status = [self.SUCCESS] * R
+        for r in range(R):
+            if win["window_count"][r] == 0:
+                status[r] = self.INTERNAL_ERROR               # "Could not transform the global plan" (:275-281): no plan
+                continue
+            gg = win["global_goal"][r]
+            dx, dy = gg[0] - poses[r][0], gg[1] - poses[r][1]
+            delta_orient = normalize_theta(gg[2] - poses[r][2])
+            stopped = (abs(vels[r][2]) <= a.theta_stopped_vel and abs(vels[r][0]) <= a.trans_stopped_vel
+                       and abs(vels[r][1]) <= a.trans_stopped_vel)   # base_local_planner::stopped
+            if (abs(math.sqrt(dx * dx + dy * dy)) < self.cfg_.goal_tolerance.xy_goal_tolerance and abs(delta_orient) < a.yaw_goal_tolerance
+                    and (not a.complete_global_plan or win["via_count"][r] == 0) and (stopped or a.free_goal_vel)):
+                status[r] = self.GOAL_REACHED
+        active = [status[r] == self.SUCCESS for r in range(R)]
+        # a robot that needs no plan still needs a scene: start = goal = its pose, its result is ignored and its bands dropped below
+        goals = [tuple(win["goal"][r]) if active[r] else poses[r] for r in range(R)]
+        plans = [win["windows"][r] if active[r] else None for r in range(R)]
+        vias = [win["vias"][r] if active[r] else [] for r in range(R)]
+        best = self.plan(poses, goals, vels, obstacles_per_robot, vias, a.free_goal_vel, plans, now, costmaps_per_robot,
+                         costmap_obstacles_behind_robot_dist, costmap_tile_cells)
+        planned = [bool(best[r] >= 0) for r in range(R)]
+        diverged = self.hasDiverged()
+        feasible = self.isTrajectoryFeasible(footprint_spec, inscribed_radius, 0.0, t.feasibility_check_no_poses,
+                                             t.feasibility_check_lookahead_distance)
+        raw = self.getVelocityCommands()
+        cmd = np.zeros((R, 3))
+        rb = self.cfg_.robot
+        for r in range(R):
+            if not active[r]:
+                continue
+            ok = planned[r] and not diverged[r] and feasible[r] and raw[r][0]
+            if ok:
+                v = saturate_velocity(raw[r][1], raw[r][2], raw[r][3], rb.max_vel_x, rb.max_vel_y, rb.max_vel_trans, rb.max_vel_theta,
+                                      rb.max_vel_x_backwards, a.use_proportional_saturation)
+                if a.cmd_angle_instead_rotvel:
+                    v = (v[0], v[1], steering_angle(v[0], v[2], a.wheelbase, 0.95 * rb.min_turning_radius))
+                    ok = math.isfinite(v[2])
+            if ok:
+                cmd[r] = v
+                self.no_infeasible_plans_[r] = 0
+            else:
+                status[r] = self.NO_VALID_CMD
+                self.no_infeasible_plans_[r] += 1
+        self.last_tick = dict(windows=win, raw=raw, planned=planned, diverged=diverged, feasible=feasible)
+        self.clearPlanner([r for r in range(R) if status[r] != self.SUCCESS])
+        return status, cmd
+
+
+FleetHomotopyClassPlanner.SUCCESS, FleetHomotopyClassPlanner.GOAL_REACHED = "SUCCESS", "GOAL_REACHED"
+FleetHomotopyClassPlanner.NO_VALID_CMD, FleetHomotopyClassPlanner.INTERNAL_ERROR = "NO_VALID_CMD", "INTERNAL_ERROR"
+
+
+def adapter_defaults():
+    """What computeVelocityCommands reads beside TebConfig, with the reference's defaults (teb_config.h:286-298): no part
+    of TebConfig. The velocity limits come from cfg.robot, xy_goal_tolerance from cfg.goal_tolerance."""
+    from types import SimpleNamespace
+    return SimpleNamespace(yaw_goal_tolerance=0.2, free_goal_vel=False, trans_stopped_vel=0.1, theta_stopped_vel=0.1,
+                           complete_global_plan=True, use_proportional_saturation=False, cmd_angle_instead_rotvel=False, wheelbase=1.0)
+
+
+def saturate_velocity(vx, vy, omega, max_vel_x, max_vel_y, max_vel_trans, max_vel_theta, max_vel_x_backwards,
+                      use_proportional_saturation=False):
+    """TebLocalPlannerROS::saturateVelocity (src/teb_local_planner_ros.cpp:874-919) -> (vx, vy, omega)"""
+    import math
+    ratio_x = ratio_omega = ratio_y = 1.0
+    if vx > max_vel_x:
+        ratio_x = max_vel_x / vx
+    if vy > max_vel_y or vy < -max_vel_y:
+        ratio_y = abs(max_vel_y / vy)
+    if omega > max_vel_theta or omega < -max_vel_theta:
+        ratio_omega = abs(max_vel_theta / omega)
+    if max_vel_x_backwards > 0 and vx < -max_vel_x_backwards:   # (<= 0: the reference warns and leaves vx alone)
+        ratio_x = -max_vel_x_backwards / vx
+    if use_proportional_saturation:
+        ratio = min(min(ratio_x, ratio_y), ratio_omega)
+        vx, vy, omega = vx * ratio, vy * ratio, omega * ratio
+    else:
+        vx, vy, omega = vx * ratio_x, vy * ratio_y, omega * ratio_omega
+    vel_linear = math.hypot(vx, vy)
+    if vel_linear > max_vel_trans:
+        k = max_vel_trans / vel_linear
+        vx, vy = vx * k, vy * k
+    return vx, vy, omega
+
+
+def steering_angle(v, omega, wheelbase, min_turning_radius):
+    """convertTransRotVelToSteeringAngle (:922-933); a radius of exactly 0 gives +-pi / 2 as atan(+-inf) does"""
+    import math
+    if omega == 0 or v == 0:
+        return 0.0
+    radius = v / omega
+    if abs(radius) < min_turning_radius:
+        radius = (1.0 if radius > 0 else (-1.0 if radius < 0 else 0.0)) * min_turning_radius
+    if radius == 0:
+        return math.copysign(math.pi / 2, wheelbase) * math.copysign(1.0, radius)
+    return math.atan(wheelbase / radius)
 
 
 class HomotopyClassPlanner:
