@@ -30,6 +30,7 @@
 #include "teb_costmap_polygons.hpp"
 #include "teb_plan_window.hpp"
 #include "teb_scene_store.hpp"
+#include "teb_hcp_host.hpp"
 
 using namespace tebamd;
 
@@ -192,12 +193,8 @@ struct teb_amd_handle {
       tmp_chi2, tmp_cost, tmp_lambda;
   DevBuf<int> cand_n, cand_off, cand_map, tmp_n, tmp_i;
   DevBuf<unsigned char> g_adj;
-  size_t g_cap = 0;
   bool cand_ready = false, tmp_ready = false;
-  std::vector<double> best_class;   // best_teb_eq_class_ (homotopy_class_planner.h): signature of the last best band; survives the band
-  int best_class_mode = 0;          // 0 = none yet, 2 / 3 = HSignature / HSignature3d
-  std::vector<double> initial_class;   // initial_plan_eq_class_: signature of the band made from the last initial plan
-  int initial_class_mode = 0;
+  PlannerMemory memory;   // what the single scene's planner remembers between ticks (teb_hcp_host.hpp); g_vx .. g_adj above are launch scratch
   // costmap (f4)
   DevBuf<unsigned char> cm_cells;
   DevBuf<double> cm_fp;
@@ -240,7 +237,6 @@ struct teb_amd_handle {
     DevBuf<unsigned long long> ticket;
     std::vector<int> count_host;
   } plans;
-  std::mt19937 rnd_generator;   // ProbRoadmapGraph::rnd_generator_ (graph_search.h:211): default-seeded 32-bit Mersenne twister
   // fleet batches (teb_fleet.hpp, teb_amd_set_scenes): the scene set - a second DevSceneStore, allocated at the first
   // teb_amd_set_scenes and sized by the capacities of the handle, with the rows, vertices and via-points of the scenes one after the
   // other (scene_segments) - and what a fleet launch needs beside it
@@ -263,27 +259,15 @@ struct teb_amd_handle {
     int hsig_mode = 0, hsig_B = 0;   // 0 = no valid signatures; 2 / 3 as hsig_mode of the handle
     std::vector<int> hsig_off;       // [hsig_B + 1]
     std::vector<double> hsig_host;   // band after band
-    std::vector<std::vector<double>> best_class;   // [n_scenes] best_teb_eq_class_ of every scene's planner
-    std::vector<int> best_class_mode;
     double hsig_prescaler = 0;       // of those signatures
-    // candidate exploration per scene (teb_amd_explore_candidates_per_scene): what a planner - a robot, a scene - remembers, with the
-    // lifetime of best_class; none of it is the single scene's (rnd_generator, initial_class, g_vx .. above)
-    std::vector<std::mt19937> rnd;                    // [n_scenes] ProbRoadmapGraph::rnd_generator_, default-seeded
-    std::vector<std::vector<double>> initial_class;   // [n_scenes] initial_plan_eq_class_
-    std::vector<int> initial_class_mode;
-    std::vector<std::vector<double>> g_vx, g_vy;      // [n_scenes] the last graph of every scene (empty: returned before its graph)
-    std::vector<std::vector<unsigned char>> g_adj;
-    // its scratch, separate from the single scene's and allocated at the first call: candidate strips, path points, offsets,
-    // candidate -> scene map, signatures; the graphs of a call (vertices, adjacency, records)
+    std::vector<PlannerMemory> memory;   // [n_scenes] what the planner of every scene - a robot - remembers; none of it is the single scene's
+    // scratch of the candidate exploration per scene, separate from the single scene's and allocated at the first call: candidate
+    // strips, path points, offsets, candidate -> scene map, signatures; the graphs of a call (vertices, adjacency, records)
     DevBuf<double> ex_x, ex_y, ex_th, ex_dt, ex_px, ex_py, ex_pyaw, ex_sig, ex_orient, ex_line, ex_gvx, ex_gvy;
     DevBuf<int> ex_n, ex_off, ex_scene, ex_soff, ex_map;
     DevBuf<unsigned char> ex_gadj;
     DevBuf<GraphFleetRec> ex_rec;
-    void forget_best_classes(size_t ns) {   // and everything else a scene's planner remembers
-      best_class.assign(ns, {}); best_class_mode.assign(ns, 0);
-      rnd.assign(ns, std::mt19937()); initial_class.assign(ns, {}); initial_class_mode.assign(ns, 0);
-      g_vx.assign(ns, {}); g_vy.assign(ns, {}); g_adj.assign(ns, {});
-    }
+    void new_planners(size_t ns) { memory.assign(ns, PlannerMemory()); }   // ns planners that remember nothing
     void release() {   // the device side
       store.free();
       free_all(scene_of, sel_last, sel_init, sel_idx, sel_cost, scenes, hs_pre, hs_pim, hs_pex, hs_off);
@@ -1092,15 +1076,15 @@ int install_scene_set(teb_amd_handle* h, std::vector<HostObst>&& tabs, std::vect
   U(F.store.upload_vias(h->stream, via_x, via_y, vias));
   U(hipStreamSynchronize(h->stream));   // the uploads read `all` and the caller's arrays
   if (e != hipSuccess) {
-    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0);
+    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.new_planners(0);
     return fail(TEB_AMD_ERR_HIP, std::string("teb_amd_set_scenes: upload of the scene set -> ") + hipGetErrorString(e));
   }
   F.tabs = std::move(tabs);
   F.via_count = std::move(vc);
   rc = commit_fleet(h);
-  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.forget_best_classes(0); return rc; }
+  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.new_planners(0); return rc; }
   F.n_scenes = n_scenes;
-  if (F.best_class.size() != (size_t)n_scenes) F.forget_best_classes(n_scenes);   // a remembered class belongs to a robot: kept while the fleet keeps its size
+  if (F.memory.size() != (size_t)n_scenes) F.new_planners(n_scenes);   // a remembered class belongs to a robot: kept while the fleet keeps its size
   return TEB_AMD_OK;
 }
 }  // namespace
@@ -1165,7 +1149,7 @@ int teb_amd_clear_scenes(teb_amd_handle_t* h) {
   h->fleet.n_scenes = 0;   // the single-scene table, its lists and its layout are as they were
   h->fleet.tabs.clear(); h->fleet.via_count.clear();
   h->fleet.hsig_mode = 0; h->fleet.hs_prod_valid = false;
-  h->fleet.forget_best_classes(0);
+  h->fleet.new_planners(0);
   return TEB_AMD_OK;
 }
 
@@ -2150,6 +2134,38 @@ int launch_hsig(teb_amd_handle* h, const BatchDev& bt, int B, double prescaler, 
   }
   return TEB_AMD_OK;
 }
+
+// Its counterpart for a scene set: the signatures of the `count` bands of bt (the batch or the set's candidate strips), band k against
+// the table of scene fl.scene_of[k], into out at fl.off[k] (3-D; `total` values in all, the offsets uploaded by the caller) or at 2 k
+// (2-D). widest: most rows of a table of the set.
+int launch_hsig_fleet(teb_amd_handle* h, const FleetHsigDev& fl, const BatchDev& bt, int count, size_t total, int widest, double prescaler,
+                      double* out) {
+  auto& F = h->fleet;
+  if (h->cfg.include_dynamic_obstacles) {
+    if (total > 0) {
+      // the rule of the single-scene launch on the total number of values; teb_amd_options_t::hsig3d_kernel pins one of the two
+      const bool wide = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE || (h->opt.hsig3d_kernel != TEB_AMD_HSIG3D_SMALL && (long long)total >= 32768);
+      if (wide)
+        hipLaunchKernelGGL(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
+                           h->stream, fl, bt, out);
+      else
+        hipLaunchKernelGGL(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
+                           h->stream, fl, bt, out);
+      HIPCHK(hipGetLastError());
+    }
+  } else {
+    if (widest > 0 && !F.hs_prod_valid) {   // the band-independent factor of A_l: once per scene set, every scene over its own rows
+      hipLaunchKernelGGL(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, F.n_scenes), dim3(kThreads), 0, h->stream, F.scenes.p,
+                         F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p);
+      HIPCHK(hipGetLastError());
+      F.hs_prod_valid = true;
+    }
+    hipLaunchKernelGGL(hsig2d_fleet_kernel, dim3(count), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, bt, prescaler,
+                       F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p, out);
+    HIPCHK(hipGetLastError());
+  }
+  return TEB_AMD_OK;
+}
 }  // namespace
 
 // ---- f3 (arithmetic core): equivalence classes of the device-resident bands (kernels in teb_hsig.hpp) ----------------------------
@@ -2173,50 +2189,6 @@ int teb_amd_compute_h_signatures(teb_amd_handle_t* h, double prescaler, double* 
   return TEB_AMD_OK;
 }
 
-namespace {
-// The class list of renewAndAnalyzeOldTebs over the bands `order` (band indices, in band order) of ONE planner: the single scene's
-// bands, or the bands of one scene of a set. row[b]: the W values of band b (mode 2 / 3). best: a band of `order` that is visited first
-// (std::iter_swap with the first band) and whose class becomes the remembered best class, or anything else for none. best_class /
-// best_class_mode: best_teb_eq_class_ of that planner. kp / vld / rsn [band index] are written for the bands of `order` only.
-void filter_class_list(int mode, int W, double threshold, int max_number_plans_in_current_class, std::vector<int> order, int best,
-                       const std::vector<const double*>& row, std::vector<double>& best_class, int& best_class_mode, int* kp, int* vld, int* rsn) {
-  auto is_valid = [&](int b) { for (int k = 0; k < W; ++k) if (!std::isfinite(row[b][k])) return false; return true; };
-  auto is_reasonable = [&](int b) { if (mode == 2) return true; for (int k = 0; k < W; ++k) if (row[b][k] > 1.0) return false; return true; };
-  auto sign_of = [](double z) { return z == 0 ? 0 : (z < 0 ? -1 : 1); };
-  auto equal_rows = [&](const double* x, const double* y) {   // x->isEqual(y)
-    if (mode == 2) return std::fabs(y[0] - x[0]) <= threshold && std::fabs(y[1] - x[1]) <= threshold;   // h_signature.h:196-204
-    for (int i = 0; i < W; ++i) {                                                                          // h_signature.h:360-377
-      if (std::fabs(y[i]) < threshold || std::fabs(x[i]) < threshold) continue;   // far-away obstacle: ignored
-      if (sign_of(y[i]) != sign_of(x[i])) return false;
-    }
-    return true;
-  };
-  auto is_equal = [&](int a, int b) { return equal_rows(row[a], row[b]); };   // cls[a]->isEqual(*cls[b])
-  std::vector<int> classes;
-  for (int b : order) { vld[b] = is_valid(b); kp[b] = 0; rsn[b] = is_reasonable(b); }
-  const auto at = std::find(order.begin(), order.end(), best);
-  if (at != order.end()) {   // best_teb_eq_class_ = calculateEquivalenceClass(best_teb_), src/homotopy_class_planner.cpp:224-227
-    std::iter_swap(order.begin(), at);
-    best_class.assign(row[best], row[best] + W); best_class_mode = mode;
-  }
-  // isInBestTebClass / numTebsInBestTebClass use best_teb_eq_class_, which outlives the band it was computed from (:385-410)
-  const bool have_best_class = best_class_mode == mode && (int)best_class.size() == W;
-  auto equal_to_best = [&](int b) { return equal_rows(best_class.data(), row[b]); };   // best_teb_eq_class_->isEqual(*cls[b])
-  for (int b : order) {
-    if (!vld[b]) continue;                                   // "Ignoring invalid H-signature"
-    bool has = false;
-    for (int c : classes) if (is_equal(b, c)) { has = true; break; }
-    if (has) {
-      const bool in_best = have_best_class && equal_to_best(b);
-      int count = 0;
-      if (have_best_class) for (int c : classes) if (equal_to_best(c)) ++count;
-      if (!in_best || count >= max_number_plans_in_current_class) continue;
-    }
-    classes.push_back(b); kp[b] = 1;
-  }
-}
-}  // namespace
-
 int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, int32_t best, int32_t max_number_plans_in_current_class,
                                        int32_t* keep, int32_t* valid, int32_t* reasonable) {
   int rc = check_handle(h);
@@ -2224,16 +2196,10 @@ int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, in
   if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_equivalence_classes"))) return rc;
   if (h->hsig_mode == 0 || h->hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures first");
   const int B = h->hsig_B, mode = h->hsig_mode, W = mode == 3 ? h->hsig_M : 2;
-  std::vector<int> order(B), kp(B, 0), vld(B, 0), rsn(B, 0);
+  std::vector<int> order(B);
   std::vector<const double*> row(B);
   for (int b = 0; b < B; ++b) { order[b] = b; row[b] = h->hsig_host.data() + (size_t)b * W; }
-  filter_class_list(mode, W, threshold, max_number_plans_in_current_class, std::move(order), best, row, h->best_class, h->best_class_mode,
-                    kp.data(), vld.data(), rsn.data());
-  for (int b = 0; b < B; ++b) {
-    if (keep) keep[b] = kp[b];
-    if (valid) valid[b] = vld[b];
-    if (reasonable) reasonable[b] = rsn[b];
-  }
+  filter_class_list(SignatureRule{mode, W, threshold}, max_number_plans_in_current_class, std::move(order), best, row, h->memory, keep, valid, reasonable);
   return TEB_AMD_OK;
 }
 
@@ -2294,30 +2260,8 @@ int teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler
   FleetHsigDev fl;
   fl.scenes = F.scenes.p; fl.scene_of = F.scene_of.p; fl.off = F.hs_off.p;
   double* out = h->hsig.p;   // [max_tebs * max(max_obstacles, 2)]: scratch of the launch (the single scene's signatures live in hsig_host)
-  if (mode == 3) {
-    if (total > 0) {
-      HIPCHK(hipMemcpyAsync(F.hs_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-      // the rule of the single-scene launch on the total number of values; teb_amd_options_t::hsig3d_kernel pins one of the two
-      const bool wide = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE || (h->opt.hsig3d_kernel != TEB_AMD_HSIG3D_SMALL && (long long)total >= 32768);
-      if (wide)
-        hipLaunchKernelGGL(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                           h->stream, fl, bt, out);
-      else
-        hipLaunchKernelGGL(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                           h->stream, fl, bt, out);
-      HIPCHK(hipGetLastError());
-    }
-  } else {
-    if (widest > 0 && !F.hs_prod_valid) {   // the band-independent factor of A_l: once per scene set, every scene over its own rows
-      hipLaunchKernelGGL(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, F.n_scenes), dim3(kThreads), 0, h->stream, F.scenes.p,
-                         F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p);
-      HIPCHK(hipGetLastError());
-      F.hs_prod_valid = true;
-    }
-    hipLaunchKernelGGL(hsig2d_fleet_kernel, dim3(B), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, bt, prescaler,
-                       F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p, out);
-    HIPCHK(hipGetLastError());
-  }
+  if (mode == 3 && total > 0) HIPCHK(hipMemcpyAsync(F.hs_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if ((rc = launch_hsig_fleet(h, fl, bt, B, total, widest, prescaler, out))) return rc;
   F.hsig_host.assign(std::max<size_t>(total, 1), 0.0);
   if (total > 0) HIPCHK(hipMemcpyAsync(F.hsig_host.data(), out, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // (off is read until here)
@@ -2338,21 +2282,13 @@ int teb_amd_filter_equivalence_classes_per_scene(teb_amd_handle_t* h, double thr
   if (F.hsig_mode == 0 || F.hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures_per_scene first");
   const int B = F.hsig_B, mode = F.hsig_mode;
   if ((rc = check_best_per_scene(h, best, B, "teb_amd_filter_equivalence_classes_per_scene"))) return rc;
-  std::vector<int> kp(B, 0), vld(B, 0), rsn(B, 0);
   std::vector<const double*> row(B);
   for (int b = 0; b < B; ++b) row[b] = F.hsig_host.data() + F.hsig_off[b];
-  std::vector<std::vector<int>> of;
+  std::vector<std::vector<int>> of;   // (every band < B is a band of one scene: check_band_scenes of the compute call)
   bands_per_scene(h, B, of);
-  for (int s = 0; s < F.n_scenes; ++s) {
-    const int W = mode == 3 ? (int)F.tabs[s].rows() : 2;
-    filter_class_list(mode, W, threshold, max_number_plans_in_current_class, of[s], best ? best[s] : -1, row, F.best_class[s], F.best_class_mode[s],
-                      kp.data(), vld.data(), rsn.data());
-  }
-  for (int b = 0; b < B; ++b) {
-    if (keep) keep[b] = kp[b];
-    if (valid) valid[b] = vld[b];
-    if (reasonable) reasonable[b] = rsn[b];
-  }
+  for (int s = 0; s < F.n_scenes; ++s)
+    filter_class_list(SignatureRule{mode, mode == 3 ? (int)F.tabs[s].rows() : 2, threshold}, max_number_plans_in_current_class, of[s],
+                      best ? best[s] : -1, row, F.memory[s], keep, valid, reasonable);
   return TEB_AMD_OK;
 }
 
@@ -2915,342 +2851,7 @@ int ensure_candidate_buffers(teb_amd_handle* h) {
   return TEB_AMD_OK;
 }
 
-BatchDev candidates_of(teb_amd_handle* h) {   // the scratch strips seen as a batch of kCandChunk bands
-  BatchDev c = batch_of(h);
-  c.B = kCandChunk;
-  c.n = h->cand_n.p; c.x = h->cand_x.p; c.y = h->cand_y.p; c.th = h->cand_th.p; c.dt = h->cand_dt.p;
-  return c;
-}
-
-// isValid / isEqual of HSignature and HSignature3d (h_signature.h:190-226, 349-409) on rows of W doubles
-struct ClassTable {
-  int mode = 2, W = 2, max_in_best = 1;
-  double thr = 0.1;
-  std::vector<std::vector<double>> classes;   // equivalence_classes_
-  bool has_best = false;
-  std::vector<double> best;                   // best_teb_eq_class_
-  static int sign_of(double z) { return z == 0 ? 0 : (z < 0 ? -1 : 1); }
-  bool valid(const double* v) const { for (int k = 0; k < W; ++k) if (!std::isfinite(v[k])) return false; return true; }
-  bool equal(const double* a, const double* b) const {   // a.isEqual(b)
-    if (mode == 2) return std::fabs(b[0] - a[0]) <= thr && std::fabs(b[1] - a[1]) <= thr;
-    for (int i = 0; i < W; ++i) {
-      if (std::fabs(b[i]) < thr || std::fabs(a[i]) < thr) continue;
-      if (sign_of(b[i]) != sign_of(a[i])) return false;
-    }
-    return true;
-  }
-  bool add_if_new(const double* v) {   // addEquivalenceClassIfNew, src/homotopy_class_planner.cpp:189-212
-    if (!valid(v)) return false;
-    bool has = false;
-    for (const auto& c : classes) if (equal(v, c.data())) { has = true; break; }
-    if (has) {
-      const bool in_best = has_best && equal(best.data(), v);
-      int count = 0;
-      if (has_best) for (const auto& c : classes) if (equal(best.data(), c.data())) ++count;
-      if (!in_best || count >= max_in_best) return false;
-    }
-    classes.emplace_back(v, v + W);
-    return true;
-  }
-};
-
-// GraphSearchInterface::DepthFirst (src/graph_search.cpp:45-91) as a resumable generator of start-goal paths in the reference's order
-struct PathEnumerator {
-  const std::vector<std::vector<int>>* adj;
-  int goal;
-  struct Frame { int v; int phase; size_t k; };
-  std::vector<Frame> stack;
-  std::vector<int> visited;
-  std::vector<char> on_path;
-  int64_t expansions = 0, max_expansions = 0;   // > 0: give up after that many vertex expansions (dead-end subtrees can be exponential)
-  PathEnumerator(const std::vector<std::vector<int>>& a, int start, int goal_) : adj(&a), goal(goal_), on_path(a.size(), 0) {
-    stack.push_back({start, 0, 0}); visited.push_back(start); on_path[start] = 1;
-  }
-  bool next(std::vector<int>& path) {
-    while (!stack.empty()) {
-      if (max_expansions > 0 && ++expansions > max_expansions) return false;
-      Frame& f = stack.back();
-      const std::vector<int>& out = (*adj)[f.v];
-      if (f.phase == 0) {       // first loop: the goal, if adjacent, closes one path
-        f.phase = 1; f.k = 0;
-        if (std::find(out.begin(), out.end(), goal) != out.end()) { path = visited; path.push_back(goal); return true; }
-      }
-      bool descended = false;
-      while (f.k < out.size()) {   // second loop: recursion into every adjacent vertex not yet on the path
-        const int w = out[f.k++];
-        if (on_path[w] || w == goal) continue;
-        visited.push_back(w); on_path[w] = 1;
-        stack.push_back({w, 0, 0});
-        descended = true;
-        break;
-      }
-      if (descended) continue;
-      on_path[f.v] = 0; visited.pop_back(); stack.pop_back();
-    }
-    return false;
-  }
-};
-
-// The vertices of createGraph for ONE planner, on the host (O(M) on the centroids of its obstacle table): lrKeyPointGraph
-// (src/graph_search.cpp:115-153) or ProbRoadmapGraph (:247-290, samples from unit_samples or drawn from the planner's generator).
-// vx / vy: start, key points or samples, goal. ga: everything of the edge kernel's arguments but N, the vertex and the adjacency pointers.
-void graph_vertices(const HostObst& hob, const double* start, const double* goal, double start_goal_dist, double dist_to_obst,
-                    const teb_amd_hcp_params_t* p, std::mt19937& generator, const double* unit_samples, std::vector<double>& vx,
-                    std::vector<double>& vy, GraphArgs& ga) {
-  const int M = (int)hob.rows();
-  const double sx = start[0], sy = start[1], gx = goal[0], gy = goal[1];
-  double dfx = gx - sx, dfy = gy - sy;
-  auto normalize = [](double& x, double& y) { const double z = x * x + y * y; if (z > 0) { const double n = std::sqrt(z); x = x / n; y = y / n; } };
-  vx.assign(1, sx); vy.assign(1, sy);
-  ga.keypoint = p->simple_exploration ? 1 : 0; ga.near_u = ga.near_v = -1; ga.thr = p->obstacle_heading_threshold;
-  ga.sox = std::cos(start[2]); ga.soy = std::sin(start[2]);
-  if (p->simple_exploration) {                                              // lrKeyPointGraph::createGraph, :115-153
-    double nx = -dfy, ny = dfx;
-    normalize(nx, ny);
-    nx = nx * dist_to_obst; ny = ny * dist_to_obst;
-    normalize(dfx, dfy);
-    double min_dist = std::numeric_limits<double>::max();
-    for (int o = 0; o < M; ++o) {
-      const double ox = hob.cx[o] - sx, oy = hob.cy[o] - sy;
-      const double dist = std::sqrt(ox * ox + oy * oy);
-      if ((ox * dfx + oy * dfy) / dist < 0.1) continue;                     // obstacle not in front of the start
-      vx.push_back(hob.cx[o] + nx); vy.push_back(hob.cy[o] + ny);
-      vx.push_back(hob.cx[o] - nx); vy.push_back(hob.cy[o] - ny);
-      if (p->obstacle_heading_threshold && dist < min_dist) { min_dist = dist; ga.near_u = (int)vx.size() - 2; ga.near_v = (int)vx.size() - 1; }
-    }
-    ga.min_dist = 0.5 * dist_to_obst;
-  } else {                                                                  // ProbRoadmapGraph::createGraph, :247-290
-    double nx = -dfy, ny = dfx;
-    normalize(nx, ny);
-    const double area_width = p->roadmap_graph_area_width;
-    const double len = start_goal_dist * p->roadmap_graph_area_length_scale;
-    const double phi = std::atan2(dfy, dfx);
-    double ox, oy;
-    if (p->roadmap_graph_area_length_scale != 1.0) {
-      double ux = dfx, uy = dfy;
-      normalize(ux, uy);
-      const double f = 0.5 * (1.0 - p->roadmap_graph_area_length_scale) * start_goal_dist, w2 = 0.5 * area_width;
-      ox = (sx + f * ux) - w2 * nx; oy = (sy + f * uy) - w2 * ny;
-    } else {
-      const double w2 = 0.5 * area_width;
-      ox = sx - w2 * nx; oy = sy - w2 * ny;
-    }
-    normalize(dfx, dfy);
-    int drawn = 0;
-    auto draw = [&](double a, double b) {    // boost::random::uniform_real_distribution<double>(a, b) on the 32-bit engine
-      if (unit_samples) return unit_samples[drawn++] * (b - a) + a;
-      for (;;) {
-        const double numerator = (double)(generator() - std::mt19937::min());
-        const double divisor = (double)(std::mt19937::max() - std::mt19937::min()) + 1;
-        const double result = numerator / divisor * (b - a) + a;
-        if (result < b) return result;
-      }
-    };
-    const double cphi = std::cos(phi), sphi = std::sin(phi);
-    for (int i = 0; i < p->roadmap_graph_no_samples; ++i) {
-      const double uy = draw(0, area_width);   // GCC evaluates Eigen::Vector2d(distribution_x(g), distribution_y(g)) right to left
-      const double ux = draw(0, len);
-      vx.push_back(ox + (cphi * ux - sphi * uy)); vy.push_back(oy + (sphi * ux + cphi * uy));
-    }
-    ga.min_dist = dist_to_obst;
-  }
-  vx.push_back(gx); vy.push_back(gy);
-  ga.dnx = dfx; ga.dny = dfy;
-}
-}  // namespace
-
-int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
-                               double dist_to_obst, const double* start_vel, int32_t free_goal_vel, int32_t best,
-                               const double* unit_samples, int64_t max_paths, int32_t* n_total, int32_t* n_vertices, int32_t* n_paths,
-                               int32_t n_plan, const double* plan_x, const double* plan_y, const double* plan_yaw,
-                               int32_t* initial_plan_teb) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if ((rc = refuse_in_fleet_mode(h, "teb_amd_explore_candidates"))) return rc;
-  if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
-  if (n_plan > 0 && (!plan_x || !plan_y || !plan_yaw)) return fail(TEB_AMD_ERR_INVALID_ARG, "null initial plan");
-  if (initial_plan_teb) *initial_plan_teb = -1;
-  if ((rc = ensure_candidate_buffers(h))) return rc;
-  const teb_amd_config_t& c = h->cfg;
-  const int M = h->M;
-  const int mode = c.include_dynamic_obstacles ? 3 : 2, W = mode == 3 ? M : 2;
-  const int slots = std::min<int>(p->max_number_classes, h->max_tebs);
-  h->g_cap = 0;
-  if (n_vertices) *n_vertices = 0;
-  if (n_paths) *n_paths = 0;
-  if (n_total) *n_total = h->B;
-  // equivalence_classes_ of the existing bands
-  ClassTable ct;
-  ct.mode = mode; ct.W = W; ct.thr = p->h_signature_threshold; ct.max_in_best = p->max_number_plans_in_current_class;
-  if (h->B > 0) {
-    const bool fresh = h->hsig_mode == mode && h->hsig_B == h->B && h->hsig_M == M && h->hsig_prescaler == p->h_signature_prescaler;
-    if (!fresh && (rc = teb_amd_compute_h_signatures(h, p->h_signature_prescaler, nullptr, nullptr))) return rc;   // else: renew just did
-    for (int b = 0; b < h->B; ++b) ct.classes.emplace_back(h->hsig_host.data() + (size_t)b * W, h->hsig_host.data() + (size_t)(b + 1) * W);
-    if (best >= 0 && best < h->B) { h->best_class = ct.classes[best]; h->best_class_mode = mode; }
-  }
-  if (h->best_class_mode == mode && (int)h->best_class.size() == W) { ct.has_best = true; ct.best = h->best_class; }   // best_teb_eq_class_
-  h->signatures_stale();   // the batch is about to change: signatures have to be recomputed before the next filter call
-  const int n_old = h->B;
-  // tebs_.push_back(candidate) for the accepted candidates of a chunk: scratch bands -> the next slots of the batch, one gather;
-  // default attributes of a new TebOptimalPlanner (fixed zero start / goal velocity), then setVelocityStart / setVelocityGoalFree
-  auto accept_all = [&](const std::vector<int>& cand) -> int {
-    if (cand.empty()) return TEB_AMD_OK;
-    const int slot0 = h->B, cnt = (int)cand.size();
-    int r = extend_batch(h, slot0 + cnt - 1);
-    if (r) return r;
-    HIPCHK(hipMemcpyAsync(h->cand_map.p, cand.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(move_bands_kernel, dim3(cnt), dim3(kThreads), 0, h->stream, candidates_of(h), batch_of(h), h->cand_map.p, slot0, 0);
-    HIPCHK(hipGetLastError());
-    if (start_vel) {
-      std::vector<double> vv;
-      for (int k = 0; k < cnt; ++k) { vv.push_back(start_vel[0]); vv.push_back(start_vel[1]); vv.push_back(start_vel[2]); }
-      HIPCHK(hipMemcpyAsync(h->vs.p + 3 * slot0, vv.data(), vv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    }
-    if (free_goal_vel) HIPCHK(hipMemsetAsync(h->has_vg.p + slot0, 0, cnt * sizeof(int), h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));   // the staging vectors live on this stack frame
-    return TEB_AMD_OK;
-  };
-  std::vector<double> sig((size_t)kCandChunk * (W > 0 ? W : 1));
-  auto classify = [&](int count) -> int {      // signatures of scratch bands 0..count-1 -> sig
-    int r = launch_hsig(h, candidates_of(h), count, p->h_signature_prescaler, h->cand_sig.p);
-    if (r) return r;
-    if ((size_t)count * W > 0) HIPCHK(hipMemcpyAsync(sig.data(), h->cand_sig.p, (size_t)count * W * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    int err = 0;
-    HIPCHK(hipMemcpyAsync(&err, h->err_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (err) return fail(TEB_AMD_ERR_CAPACITY, "candidate band needs more poses than max_poses");
-    return TEB_AMD_OK;
-  };
-  h->consumers_valid = false; h->nmax_known = -1;
-  // ---- the initial plan as a candidate: addAndInitNewTeb(*initial_plan_, ...), src/homotopy_class_planner.cpp:326-329, 412-440
-  int initial_idx = -1;   // initial_plan_teb_
-  if (n_plan > 0 && h->B < slots) {
-    if ((rc = stage(h, n_plan, plan_x, plan_y, plan_yaw))) return rc;
-    hipLaunchKernelGGL(init_plan_kernel, dim3(1), dim3(kThreads), 0, h->stream, candidates_of(h), 0, n_plan, h->stage_x.p, h->stage_y.p,
-                       h->stage_yaw.p, c.max_vel_x, c.max_vel_theta, p->global_plan_overwrite_orientation, c.min_samples,
-                       p->allow_init_with_backwards_motion, h->err_flag.p);
-    HIPCHK(hipGetLastError());
-    if ((rc = classify(1))) return rc;
-    h->initial_class.assign(sig.data(), sig.data() + W); h->initial_class_mode = mode;   // initial_plan_eq_class_
-    if (ct.add_if_new(sig.data())) {
-      if ((rc = accept_all({0}))) return rc;
-      initial_idx = h->B - 1;
-    }
-  }
-  auto body = [&]() -> int {
-  if (h->B >= slots) return TEB_AMD_OK;                                     // src/graph_search.cpp:99-100, 231-232
-  const double dfx = goal[0] - start[0], dfy = goal[1] - start[1];
-  const double start_goal_dist = std::sqrt(dfx * dfx + dfy * dfy);
-  if (start_goal_dist < p->xy_goal_tolerance) {                             // :104-113, :237-246
-    if (h->B == 0) {                                                        // addAndInitNewTeb(start, goal, ...), hcp.cpp:358-384
-      HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-      hipLaunchKernelGGL(init_line_kernel, dim3(1), dim3(kThreads), 0, h->stream, candidates_of(h), 0, start[0], start[1], start[2],
-                         goal[0], goal[1], goal[2], 0.0, c.max_vel_x, c.min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
-      HIPCHK(hipGetLastError());
-      if ((rc = classify(1))) return rc;
-      if (ct.add_if_new(sig.data()) && (rc = accept_all({0}))) return rc;
-    }
-    return TEB_AMD_OK;
-  }
-  // ---- vertices (host: O(M) on the centroids kept from teb_amd_set_obstacles) ------------------------------------------------------
-  std::vector<double> vx, vy;
-  GraphArgs ga;
-  graph_vertices(h->hob, start, goal, start_goal_dist, dist_to_obst, p, h->rnd_generator, unit_samples, vx, vy, ga);
-  const int N = (int)vx.size();
-  if (n_vertices) *n_vertices = N;
-  // ---- edges (device) -------------------------------------------------------------------------------------------------------------
-  if (h->g_vx.n < (size_t)N) { h->g_vx.free(); h->g_vy.free(); HIPCHK(h->g_vx.alloc(N)); HIPCHK(h->g_vy.alloc(N)); }
-  if (h->g_adj.n < (size_t)N * N) { h->g_adj.free(); HIPCHK(h->g_adj.alloc((size_t)N * N)); }
-  HIPCHK(hipMemcpyAsync(h->g_vx.p, vx.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->g_vy.p, vy.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  ga.N = N; ga.gx = h->g_vx.p; ga.gy = h->g_vy.p; ga.adj = h->g_adj.p;
-  const long long pairs = (long long)N * N;
-  hipLaunchKernelGGL(graph_edges_kernel, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, scene_of(h), ga);
-  HIPCHK(hipGetLastError());
-  std::vector<unsigned char> adjm((size_t)pairs);
-  HIPCHK(hipMemcpyAsync(adjm.data(), h->g_adj.p, (size_t)pairs, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  h->g_cap = N;
-  std::vector<std::vector<int>> adj(N);
-  for (int i = 0; i < N; ++i)
-    for (int j = 0; j < N; ++j) if (adjm[(size_t)i * N + j]) adj[i].push_back(j);   // add_edge order of the double loop
-  // ---- paths in depth-first order, a chunk at a time: init + signature on the device, first come first served on the host ----------
-  PathEnumerator en(adj, 0, N - 1);
-  if (max_paths > 0) en.max_expansions = max_paths * 10000;
-  std::vector<int> path, off;
-  std::vector<double> px, py;
-  int64_t examined = 0;
-  bool more = true;
-  while (more && h->B < slots) {
-    off.assign(1, 0); px.clear(); py.clear();
-    int count = 0;
-    while (count < kCandChunk && (max_paths <= 0 || examined + count < max_paths)) {
-      if (!en.next(path)) { more = false; break; }
-      if ((int)path.size() > h->stride + 1) return fail(TEB_AMD_ERR_CAPACITY, "a start-goal path has more vertices than a band has poses (max_poses)");
-      for (int v : path) { px.push_back(vx[v]); py.push_back(vy[v]); }
-      off.push_back((int)px.size());
-      ++count;
-    }
-    if (count == kCandChunk && max_paths > 0 && examined + count >= max_paths) more = false;
-    if (count == 0) break;
-    HIPCHK(hipMemcpyAsync(h->cand_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->cand_px.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->cand_py.p, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-    hipLaunchKernelGGL(init_path_batch_kernel, dim3(count), dim3(kThreads), 0, h->stream, candidates_of(h), h->cand_off.p, h->cand_px.p,
-                       h->cand_py.p, c.max_vel_x, c.acc_lim_x, start[2], goal[2], c.min_samples, p->allow_init_with_backwards_motion,
-                       h->err_flag.p);
-    HIPCHK(hipGetLastError());
-    if ((rc = classify(count))) return rc;
-    std::vector<int> accepted;
-    for (int k = 0; k < count && h->B + (int)accepted.size() < slots; ++k) {
-      ++examined;
-      if (ct.add_if_new(sig.data() + (size_t)k * W)) accepted.push_back(k);
-    }
-    if ((rc = accept_all(accepted))) return rc;
-  }
-  if (n_paths) *n_paths = (int32_t)std::min<int64_t>(examined, std::numeric_limits<int32_t>::max());
-  return TEB_AMD_OK;
-  };
-  if ((rc = body())) return rc;
-  if (n_total) *n_total = h->B;
-  // ---- getInitialPlanTEB (:495-536): the band created from the initial plan, else the first band of the initial plan's class
-  const bool have_initial_class = h->initial_class_mode == mode && (int)h->initial_class.size() == W && ct.valid(h->initial_class.data());
-  if (initial_idx < 0 && have_initial_class)
-    for (int b = 0; b < h->B && b < (int)ct.classes.size(); ++b)
-      if (ct.equal(ct.classes[b].data(), h->initial_class.data())) { initial_idx = b; break; }
-  if (initial_plan_teb) *initial_plan_teb = initial_idx;
-  // ---- updateReferenceTrajectoryViaPoints (:286-315): new candidates are born without via-points (their constructor gets none);
-  //      all candidates get them (viapoints_all_candidates), or - with an initial plan - exactly those of the initial plan's class
-  if (h->B > n_old) HIPCHK(hipMemsetAsync(h->via_en.p + n_old, 0, (h->B - n_old) * sizeof(int), h->stream));
-  if (h->B > 0 && !((!p->viapoints_all_candidates && n_plan <= 0) || h->nvia <= 0 || c.weight_viapoint <= 0)) {
-    std::vector<int> ve(h->B, 1);
-    if (!p->viapoints_all_candidates)
-      for (int b = 0; b < h->B; ++b) ve[b] = have_initial_class && b < (int)ct.classes.size() && ct.equal(h->initial_class.data(), ct.classes[b].data());
-    HIPCHK(hipMemcpyAsync(h->via_en.p, ve.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return TEB_AMD_OK;
-}
-
-int teb_amd_get_exploration_graph(teb_amd_handle_t* h, double* vx, double* vy, unsigned char* adjacency, int32_t capacity_vertices,
-                                  int32_t* n_vertices) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  const int N = (int)h->g_cap;
-  if (n_vertices) *n_vertices = N;
-  if (N == 0 || (!vx && !vy && !adjacency)) return TEB_AMD_OK;
-  if (capacity_vertices < N) return fail(TEB_AMD_ERR_CAPACITY, "graph has more vertices than capacity_vertices");
-  if (vx) HIPCHK(hipMemcpyAsync(vx, h->g_vx.p, N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (vy) HIPCHK(hipMemcpyAsync(vy, h->g_vy.p, N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (adjacency) HIPCHK(hipMemcpyAsync(adjacency, h->g_adj.p, (size_t)N * N, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
-}
-
-// ---- candidate generation per scene of a fleet batch (teb_amd.h, fleet batches; kernels: the fleet forms of teb_graph.hpp) ----------
-namespace {
-constexpr int kExploreQuota = 16;  // paths a scene contributes to a round (teb_amd_debug_set_explore_quota overrides it)
+constexpr int kExploreQuota = 16;  // paths a scene contributes to a round of a fleet (teb_amd_debug_set_explore_quota overrides it)
 
 // the candidate scratch of the scene set, for K candidates and `values` signature values; grows, never shrinks
 int ensure_fleet_candidate_buffers(teb_amd_handle* h, size_t K, size_t values) {
@@ -3273,8 +2874,388 @@ int ensure_fleet_candidate_buffers(teb_amd_handle* h, size_t K, size_t values) {
   if (!ok) { (void)hipGetLastError(); return fail(TEB_AMD_ERR_HIP, "teb_amd_explore_candidates_per_scene: candidate scratch allocation failed"); }
   return TEB_AMD_OK;
 }
+
+// ---- the exploration tick: exploreEquivalenceClassesAndInitTebs (src/homotopy_class_planner.cpp:337-384), getInitialPlanTEB and
+// updateReferenceTrajectoryViaPoints, written once over a list of planners. The decisions are the host rules of teb_hcp_host.hpp; the
+// device steps between them belong to a route: the single scene's kernels and scratch (SingleRoute, one planner) or the fleet forms
+// (FleetRoute, one planner per scene). A route initialises candidates 0 .. who.size() - 1 of its scratch strips, candidate k for
+// planner who[k], and computes their signatures; the candidates of a planner lie together.
+
+// ONE planner of a tick
+struct TickPlanner {
+  const HostObst* tab = nullptr;   // its obstacle table
+  PlannerMemory* mem = nullptr;
+  ClassTable ct;                   // the classes of its bands, in band order
+  std::vector<int> bands;          // its bands in the batch, in band order; grows with the accepted candidates
+  const double *start = nullptr, *goal = nullptr, *start_vel = nullptr;   // [3] each; start_vel may be NULL
+  int n_plan = 0; const double *plan_x = nullptr, *plan_y = nullptr, *plan_yaw = nullptr;   // the initial plan, n_plan <= 0: none
+  const double* unit_samples = nullptr;   // [2 * roadmap_graph_no_samples] or NULL: drawn from mem->rnd
+  int slots = 0, n_via = 0;        // most bands it may hold; its via-points
+  int32_t *n_vertices = nullptr, *n_paths = nullptr, *initial_plan_teb = nullptr;   // output slots, NULL: not asked for
+  // of the running tick
+  int created = -1;                // initial_plan_teb_: the band made from the initial plan, as a position in `bands`
+  std::vector<double> vx, vy;      // its graph; the adjacency matrix goes to mem->g_adj
+  GraphArgs ga;                    // everything of the edge kernel's arguments but N, the vertex and the adjacency pointers
+  PathSource paths;
+  bool full() const { return (int)bands.size() >= slots; }   // src/graph_search.cpp:99-100, 231-232
+};
+
+// The scratch a route initialises its candidates in: strips seen as a batch, gather map, path points and their offsets, signatures
+struct TickScratch { BatchDev cand; int *map, *off; double *px, *py, *sig; };
+
+// tebs_.push_back(candidate) for the accepted candidates acc of a launch: bands of the scratch strips `cand` -> the next slots of the
+// batch in one gather, with the defaults of a new TebOptimalPlanner as arrays - born without via-points, its constructor gets none -,
+// setVelocityStart / setVelocityGoalFree of their planner and, in a scene set, their entries of the band -> scene map
+int append_candidates(teb_amd_handle* h, const TickScratch& sc, const std::vector<int>& acc, const std::vector<int>& who,
+                      std::vector<TickPlanner>& P, int free_goal_vel) {
+  if (acc.empty()) return TEB_AMD_OK;
+  auto& F = h->fleet;
+  const bool scene_map = F.n_scenes > 0;   // a scene set: planner s = scene s (the single scene keeps no map)
+  const int slot0 = h->B, cnt = (int)acc.size();
+  if (slot0 + cnt > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more bands than max_tebs");   // (excluded by the slot limits)
+  std::vector<int> ones(cnt, 1), rot(cnt, TEB_AMD_ROT_NONE), hvg(cnt, free_goal_vel ? 0 : 1), zero(cnt, 0);
+  std::vector<double> vv(3 * (size_t)cnt, 0.0), z3(3 * (size_t)cnt, 0.0);
+  for (int k = 0; k < cnt; ++k) {
+    TickPlanner& t = P[who[acc[k]]];
+    if (t.start_vel) for (int j = 0; j < 3; ++j) vv[3 * k + j] = t.start_vel[j];
+    if (scene_map) F.band_scene[slot0 + k] = who[acc[k]];
+    t.bands.push_back(slot0 + k);
+  }
+  HIPCHK(hipMemcpyAsync(h->has_vs.p + slot0, ones.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->has_vg.p + slot0, hvg.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->rotdir.p + slot0, rot.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->via_en.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->optimized.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->vs.p + 3 * (size_t)slot0, vv.data(), vv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->vg.p + 3 * (size_t)slot0, z3.data(), z3.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (scene_map) HIPCHK(hipMemcpyAsync(F.scene_of.p + slot0, F.band_scene.data() + slot0, cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(sc.map, acc.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  h->B = slot0 + cnt;
+  hipLaunchKernelGGL(move_bands_kernel, dim3(cnt), dim3(kThreads), 0, h->stream, sc.cand, batch_of(h), sc.map, slot0, 0);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipStreamSynchronize(h->stream));   // the staging vectors live on this stack frame
+  return TEB_AMD_OK;
+}
+
+// The single scene: one planner, candidates in chunks of kCandChunk through the cand_* scratch
+struct SingleRoute {
+  teb_amd_handle* h;
+  const teb_amd_hcp_params_t* p;
+  TickScratch sc;
+  int per_round;
+  int plans(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // addAndInitNewTeb(*initial_plan_, ...), hcp.cpp:326-329, 412-440
+    const TickPlanner& t = P[who[0]];
+    if (int rc = stage(h, t.n_plan, t.plan_x, t.plan_y, t.plan_yaw)) return rc;
+    hipLaunchKernelGGL(init_plan_kernel, dim3(1), dim3(kThreads), 0, h->stream, sc.cand, 0, t.n_plan, h->stage_x.p, h->stage_y.p, h->stage_yaw.p,
+                       h->cfg.max_vel_x, h->cfg.max_vel_theta, p->global_plan_overwrite_orientation, h->cfg.min_samples,
+                       p->allow_init_with_backwards_motion, h->err_flag.p);
+    return TEB_AMD_OK;
+  }
+  int lines(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // addAndInitNewTeb(start, goal, ...), hcp.cpp:358-384
+    const TickPlanner& t = P[who[0]];
+    HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
+    hipLaunchKernelGGL(init_line_kernel, dim3(1), dim3(kThreads), 0, h->stream, sc.cand, 0, t.start[0], t.start[1], t.start[2], t.goal[0], t.goal[1],
+                       t.goal[2], 0.0, h->cfg.max_vel_x, h->cfg.min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
+    return TEB_AMD_OK;
+  }
+  int edges(std::vector<TickPlanner>& P, const std::vector<int>& who) {
+    TickPlanner& t = P[who[0]];
+    const int N = (int)t.vx.size();
+    if (h->g_vx.n < (size_t)N) { h->g_vx.free(); h->g_vy.free(); HIPCHK(h->g_vx.alloc(N)); HIPCHK(h->g_vy.alloc(N)); }
+    if (h->g_adj.n < (size_t)N * N) { h->g_adj.free(); HIPCHK(h->g_adj.alloc((size_t)N * N)); }
+    HIPCHK(hipMemcpyAsync(h->g_vx.p, t.vx.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->g_vy.p, t.vy.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const long long pairs = (long long)N * N;
+    t.ga.N = N; t.ga.gx = h->g_vx.p; t.ga.gy = h->g_vy.p; t.ga.adj = h->g_adj.p;
+    hipLaunchKernelGGL(graph_edges_kernel, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, scene_of(h), t.ga);
+    HIPCHK(hipGetLastError());
+    t.mem->g_adj.resize((size_t)pairs);
+    HIPCHK(hipMemcpyAsync(t.mem->g_adj.data(), h->g_adj.p, (size_t)pairs, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return TEB_AMD_OK;
+  }
+  int paths(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // the paths uploaded to sc.off / sc.px / sc.py
+    const TickPlanner& t = P[who[0]];
+    hipLaunchKernelGGL(init_path_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
+                       h->cfg.max_vel_x, h->cfg.acc_lim_x, t.start[2], t.goal[2], h->cfg.min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
+    return TEB_AMD_OK;
+  }
+  int signatures(std::vector<TickPlanner>&, const std::vector<int>& who, const std::vector<int>&) {
+    return launch_hsig(h, sc.cand, (int)who.size(), p->h_signature_prescaler, sc.sig);
+  }
+};
+
+// A scene set: one planner per scene (planner s = scene s), every step one launch over the scenes through the ex_* scratch
+struct FleetRoute {
+  teb_amd_handle* h;
+  const teb_amd_hcp_params_t* p;
+  TickScratch sc;
+  int per_round, widest;   // paths per scene and round; most rows of a table of the set
+  std::vector<int> off;    // staging of plans() and lines(): read by the stream until the synchronisation after the signatures
+  std::vector<double> px, py, pyaw;
+  int plans(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // addAndInitNewTeb(*initial_plan_, ...) of every scene
+    auto& F = h->fleet;
+    off.assign(1, 0); px.clear(); py.clear(); pyaw.clear();
+    for (int s : who) {
+      const TickPlanner& t = P[s];
+      px.insert(px.end(), t.plan_x, t.plan_x + t.n_plan); py.insert(py.end(), t.plan_y, t.plan_y + t.n_plan);
+      pyaw.insert(pyaw.end(), t.plan_yaw, t.plan_yaw + t.n_plan);
+      off.push_back((int)px.size());
+    }
+    HIPCHK(hipMemcpyAsync(sc.off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(sc.px, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(sc.py, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.ex_pyaw.p, pyaw.data(), pyaw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
+    hipLaunchKernelGGL(init_plan_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
+                       F.ex_pyaw.p, h->cfg.max_vel_x, h->cfg.max_vel_theta, p->global_plan_overwrite_orientation, h->cfg.min_samples,
+                       p->allow_init_with_backwards_motion, h->err_flag.p);
+    return TEB_AMD_OK;
+  }
+  int lines(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // addAndInitNewTeb(start, goal, ...) of every scene at its goal
+    auto& F = h->fleet;
+    px.assign(6 * who.size(), 0.0);   // (start, goal) of every line
+    for (size_t k = 0; k < who.size(); ++k)
+      for (int j = 0; j < 3; ++j) { px[6 * k + j] = P[who[k]].start[j]; px[6 * k + 3 + j] = P[who[k]].goal[j]; }
+    HIPCHK(hipMemcpyAsync(F.ex_line.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
+    hipLaunchKernelGGL(init_line_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, F.ex_line.p, 0.0, h->cfg.max_vel_x,
+                       h->cfg.min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
+    return TEB_AMD_OK;
+  }
+  int edges(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // every graph in one launch, one download
+    auto& F = h->fleet;
+    size_t nv = 0, na = 0, most = 0;
+    for (int s : who) { const size_t N = P[s].vx.size(); nv += N; na += N * N; most = std::max(most, N * N); }
+    if (F.ex_gvx.n < nv) { F.ex_gvx.free(); F.ex_gvy.free(); HIPCHK(F.ex_gvx.alloc(nv)); HIPCHK(F.ex_gvy.alloc(nv)); }
+    if (F.ex_gadj.n < na) { F.ex_gadj.free(); HIPCHK(F.ex_gadj.alloc(na)); }
+    std::vector<double> allx, ally, orient(2 * P.size(), 0.0);   // orient: of start and goal, for the path bands of the rounds
+    std::vector<GraphFleetRec> recs(who.size());
+    size_t vo = 0, ao = 0;
+    for (size_t i = 0; i < who.size(); ++i) {
+      TickPlanner& t = P[who[i]];
+      const size_t N = t.vx.size();
+      allx.insert(allx.end(), t.vx.begin(), t.vx.end()); ally.insert(ally.end(), t.vy.begin(), t.vy.end());
+      t.ga.N = (int)N; t.ga.gx = F.ex_gvx.p + vo; t.ga.gy = F.ex_gvy.p + vo; t.ga.adj = F.ex_gadj.p + ao;
+      recs[i].g = t.ga; recs[i].scene = who[i];
+      vo += N; ao += N * N;
+    }
+    for (size_t s = 0; s < P.size(); ++s) { orient[2 * s] = P[s].start[2]; orient[2 * s + 1] = P[s].goal[2]; }
+    HIPCHK(hipMemcpyAsync(F.ex_gvx.p, allx.data(), nv * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.ex_gvy.p, ally.data(), nv * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.ex_rec.p, recs.data(), recs.size() * sizeof(GraphFleetRec), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(F.ex_orient.p, orient.data(), orient.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(graph_edges_fleet_kernel, dim3((unsigned)((most + kThreads - 1) / kThreads), (unsigned)who.size()), dim3(kThreads), 0,
+                       h->stream, F.scenes.p, F.ex_rec.p);
+    HIPCHK(hipGetLastError());
+    std::vector<unsigned char> adjm(na);
+    HIPCHK(hipMemcpyAsync(adjm.data(), F.ex_gadj.p, na, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    ao = 0;
+    for (int s : who) { const size_t NN = P[s].vx.size() * P[s].vx.size(); P[s].mem->g_adj.assign(adjm.begin() + ao, adjm.begin() + ao + NN); ao += NN; }
+    return TEB_AMD_OK;
+  }
+  int paths(std::vector<TickPlanner>&, const std::vector<int>& who) {   // the paths uploaded to sc.off / sc.px / sc.py
+    auto& F = h->fleet;
+    HIPCHK(hipMemcpyAsync(F.ex_scene.p, who.data(), who.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(init_path_fleet_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
+                       F.ex_scene.p, F.ex_orient.p, h->cfg.max_vel_x, h->cfg.acc_lim_x, h->cfg.min_samples, p->allow_init_with_backwards_motion,
+                       h->err_flag.p);
+    return TEB_AMD_OK;
+  }
+  int signatures(std::vector<TickPlanner>&, const std::vector<int>& who, const std::vector<int>& soff) {
+    auto& F = h->fleet;
+    const size_t total = (size_t)soff.back();
+    HIPCHK(hipMemcpyAsync(F.ex_scene.p, who.data(), who.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    FleetHsigDev fl;
+    fl.scenes = F.scenes.p; fl.scene_of = F.ex_scene.p; fl.off = F.ex_soff.p;
+    if (h->cfg.include_dynamic_obstacles && total > 0)
+      HIPCHK(hipMemcpyAsync(F.ex_soff.p, soff.data(), soff.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return launch_hsig_fleet(h, fl, sc.cand, (int)who.size(), total, widest, p->h_signature_prescaler, sc.sig);
+  }
+};
+
+// plans -> vertices -> edges -> rounds -> at-goal lines for the planners P; their class tables are seeded, their outputs initialised
+extern "C++" template <class Route>
+int explore_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, Route& R, std::vector<TickPlanner>& P, double dist_to_obst, int free_goal_vel,
+                 int64_t max_paths) {
+  // the candidates of a launch: planner of every candidate, its signature values at sig[soff[k] ..), the accepted ones, the paths of a round
+  std::vector<int> who, soff, acc, off;
+  std::vector<double> sig, px, py;
+  auto classify = [&]() -> int {
+    const int count = (int)who.size();
+    soff.assign(count + 1, 0);
+    for (int k = 0; k < count; ++k) soff[k + 1] = soff[k] + P[who[k]].ct.sig.W;
+    const size_t total = (size_t)soff[count];
+    sig.assign(std::max<size_t>(total, 1), 0.0);
+    HIPCHK(hipGetLastError());   // of the launch that initialised the candidates
+    if (int rc = R.signatures(P, who, soff)) return rc;
+    if (total > 0) HIPCHK(hipMemcpyAsync(sig.data(), R.sc.sig, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    int err = 0;
+    HIPCHK(hipMemcpyAsync(&err, h->err_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (err) return fail(TEB_AMD_ERR_CAPACITY, "candidate band needs more poses than max_poses");
+    return TEB_AMD_OK;
+  };
+  auto append = [&]() { return append_candidates(h, R.sc, acc, who, P, free_goal_vel); };
+  // one candidate for every planner of `who`, a band where its class is new: the initial plan (addAndInitNewTeb(*initial_plan_, ...),
+  // hcp.cpp:326-329, 412-440; its class is initial_plan_eq_class_) or the line from start to goal (addAndInitNewTeb(start, goal, ...), :358-384)
+  auto one_each = [&](bool plan) -> int {
+    if (who.empty()) return TEB_AMD_OK;
+    acc.clear();
+    int rc = plan ? R.plans(P, who) : R.lines(P, who);
+    if (rc || (rc = classify())) return rc;
+    for (size_t k = 0; k < who.size(); ++k) {
+      TickPlanner& t = P[who[k]];
+      const double* v = sig.data() + soff[k];
+      if (plan) { t.mem->initial_class.assign(v, v + t.ct.sig.W); t.mem->initial_class_mode = t.ct.sig.mode; }
+      if (t.ct.add_if_new(v)) { acc.push_back((int)k); if (plan) t.created = (int)t.bands.size(); }
+    }
+    return append();
+  };
+  // ---- the initial plans as first candidates -----------------------------------------------------------------------------------------
+  for (size_t i = 0; i < P.size(); ++i) if (P[i].n_plan > 0 && !P[i].full()) who.push_back((int)i);
+  if (int rc = one_each(true)) return rc;
+  // ---- vertices, on the host planner by planner; the planners that return before their graph -----------------------------------------
+  std::vector<int> graphs, at_goal;
+  for (size_t i = 0; i < P.size(); ++i) {
+    TickPlanner& t = P[i];
+    if (t.full()) continue;
+    const double dfx = t.goal[0] - t.start[0], dfy = t.goal[1] - t.start[1];
+    const double start_goal_dist = std::sqrt(dfx * dfx + dfy * dfy);
+    if (start_goal_dist < p->xy_goal_tolerance) {                             // src/graph_search.cpp:104-113, 237-246
+      if (t.bands.empty()) at_goal.push_back((int)i);                         // a line band, and only for a planner without any band
+      continue;
+    }
+    graph_vertices(*t.tab, t.start, t.goal, start_goal_dist, dist_to_obst, p, t.mem->rnd, t.unit_samples, t.vx, t.vy, t.ga);
+    if (t.n_vertices) *t.n_vertices = (int32_t)t.vx.size();
+    graphs.push_back((int)i);
+  }
+  // ---- edges (device), then the graph is what the planner remembers ------------------------------------------------------------------
+  if (!graphs.empty()) {
+    if (int rc = R.edges(P, graphs)) return rc;
+    for (int i : graphs) {
+      TickPlanner& t = P[i];
+      t.mem->g_vx = t.vx; t.mem->g_vy = t.vy;
+      t.paths = PathSource(adjacency_lists(t.mem->g_adj.data(), (int)t.vx.size()), max_paths);
+    }
+  }
+  // ---- rounds: up to per_round paths of every planner with room and paths left; init + signature on the device, then first come first served
+  for (;;) {
+    off.assign(1, 0); px.clear(); py.clear(); who.clear(); acc.clear();
+    for (int i : graphs) {
+      TickPlanner& t = P[i];
+      if (!t.paths.more || t.full()) continue;
+      const int count = take_paths(t.paths, R.per_round, max_paths, h->stride + 1, t.vx, t.vy, px, py, off);
+      if (count < 0) return fail(TEB_AMD_ERR_CAPACITY, "a start-goal path has more vertices than a band has poses (max_poses)");
+      who.insert(who.end(), (size_t)count, i);
+    }
+    if (who.empty()) break;
+    HIPCHK(hipMemcpyAsync(R.sc.off, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(R.sc.px, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(R.sc.py, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
+    int rc = R.paths(P, who);
+    if (rc || (rc = classify())) return rc;
+    for (size_t k = 0; k < who.size();) {
+      TickPlanner& t = P[who[k]];
+      const int count = (int)(std::find_if(who.begin() + k, who.end(), [&](int w) { return w != who[k]; }) - (who.begin() + k));
+      t.paths.examined += accept_in_order(t.ct, sig.data() + soff[k], (int)k, count, t.slots - (int)t.bands.size(), acc);
+      k += count;
+    }
+    if ((rc = append())) return rc;
+  }
+  for (int i : graphs)
+    if (P[i].n_paths) *P[i].n_paths = (int32_t)std::min<int64_t>(P[i].paths.examined, std::numeric_limits<int32_t>::max());
+  // ---- the planners at their goal without a band: their line bands ------------------------------------------------------------------
+  who = at_goal;
+  return one_each(false);
+}
+
+// getInitialPlanTEB (:495-536) and updateReferenceTrajectoryViaPoints (:286-315) planner by planner after a tick; one upload of via_en
+int finish_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, std::vector<TickPlanner>& P) {
+  std::vector<std::vector<int>> rule(P.size());
+  bool any = false;
+  for (size_t i = 0; i < P.size(); ++i) {
+    TickPlanner& t = P[i];
+    const int n = (int)t.bands.size();
+    if (t.initial_plan_teb) *t.initial_plan_teb = initial_plan_band(t.ct, *t.mem, n, t.created);
+    if (via_point_rule(t.ct, *t.mem, n, p->viapoints_all_candidates != 0, t.n_plan > 0, t.n_via, h->cfg.weight_viapoint, rule[i])) any = true;
+  }
+  if (!any) return TEB_AMD_OK;
+  std::vector<int> ve(h->B, 0);
+  if (P.size() > 1) {   // the bands of a planner whose rule does not run keep their flags
+    HIPCHK(hipMemcpyAsync(ve.data(), h->via_en.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  for (size_t i = 0; i < P.size(); ++i)
+    for (size_t b = 0; b < rule[i].size(); ++b) ve[P[i].bands[b]] = rule[i][b];
+  HIPCHK(hipMemcpyAsync(h->via_en.p, ve.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return TEB_AMD_OK;
+}
+
+int copy_graph(const PlannerMemory& m, double* vx, double* vy, unsigned char* adjacency, int32_t capacity_vertices, int32_t* n_vertices) {
+  const int N = (int)m.g_vx.size();
+  if (n_vertices) *n_vertices = N;
+  if (N == 0 || (!vx && !vy && !adjacency)) return TEB_AMD_OK;
+  if (capacity_vertices < N) return fail(TEB_AMD_ERR_CAPACITY, "graph has more vertices than capacity_vertices");
+  if (vx) std::copy(m.g_vx.begin(), m.g_vx.end(), vx);
+  if (vy) std::copy(m.g_vy.begin(), m.g_vy.end(), vy);
+  if (adjacency) std::copy(m.g_adj.begin(), m.g_adj.end(), adjacency);
+  return TEB_AMD_OK;
+}
 }  // namespace
 
+int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
+                               double dist_to_obst, const double* start_vel, int32_t free_goal_vel, int32_t best,
+                               const double* unit_samples, int64_t max_paths, int32_t* n_total, int32_t* n_vertices, int32_t* n_paths,
+                               int32_t n_plan, const double* plan_x, const double* plan_y, const double* plan_yaw,
+                               int32_t* initial_plan_teb) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = refuse_in_fleet_mode(h, "teb_amd_explore_candidates"))) return rc;
+  if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
+  if (n_plan > 0 && (!plan_x || !plan_y || !plan_yaw)) return fail(TEB_AMD_ERR_INVALID_ARG, "null initial plan");
+  if (initial_plan_teb) *initial_plan_teb = -1;
+  if ((rc = ensure_candidate_buffers(h))) return rc;
+  const int M = h->M, mode = h->cfg.include_dynamic_obstacles ? 3 : 2, W = mode == 3 ? M : 2;
+  h->memory.forget_graph();
+  if (n_vertices) *n_vertices = 0;
+  if (n_paths) *n_paths = 0;
+  if (n_total) *n_total = h->B;
+  std::vector<TickPlanner> P(1);
+  TickPlanner& t = P[0];
+  t.tab = &h->hob; t.mem = &h->memory; t.start = start; t.goal = goal; t.start_vel = start_vel;
+  t.n_plan = n_plan; t.plan_x = plan_x; t.plan_y = plan_y; t.plan_yaw = plan_yaw; t.unit_samples = unit_samples;
+  t.slots = std::min<int>(p->max_number_classes, h->max_tebs); t.n_via = h->nvia;
+  t.n_vertices = n_vertices; t.n_paths = n_paths; t.initial_plan_teb = initial_plan_teb;
+  // equivalence_classes_ of the existing bands
+  std::vector<const double*> rows;
+  if (h->B > 0) {
+    const bool fresh = h->hsig_mode == mode && h->hsig_B == h->B && h->hsig_M == M && h->hsig_prescaler == p->h_signature_prescaler;
+    if (!fresh && (rc = teb_amd_compute_h_signatures(h, p->h_signature_prescaler, nullptr, nullptr))) return rc;   // else: renew just did
+    for (int b = 0; b < h->B; ++b) { rows.push_back(h->hsig_host.data() + (size_t)b * W); t.bands.push_back(b); }
+  }
+  t.ct = seed_class_table(SignatureRule{mode, W, p->h_signature_threshold}, p->max_number_plans_in_current_class, rows,
+                          best >= 0 && best < h->B ? rows[best] : nullptr, h->memory);
+  h->signatures_stale();   // the batch is about to change: signatures have to be recomputed before the next filter call
+  h->consumers_valid = false; h->nmax_known = -1;
+  SingleRoute R{h, p, {batch_of(h), h->cand_map.p, h->cand_off.p, h->cand_px.p, h->cand_py.p, h->cand_sig.p}, kCandChunk};
+  BatchDev& c = R.sc.cand;   // the scratch strips seen as a batch of kCandChunk bands
+  c.B = kCandChunk; c.n = h->cand_n.p; c.x = h->cand_x.p; c.y = h->cand_y.p; c.th = h->cand_th.p; c.dt = h->cand_dt.p;
+  if ((rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths))) return rc;
+  if (n_total) *n_total = h->B;
+  return finish_tick(h, p, P);
+}
+
+int teb_amd_get_exploration_graph(teb_amd_handle_t* h, double* vx, double* vy, unsigned char* adjacency, int32_t capacity_vertices,
+                                  int32_t* n_vertices) {
+  if (int rc = check_handle(h)) return rc;
+  return copy_graph(h->memory, vx, vy, adjacency, capacity_vertices, n_vertices);
+}
+
+// ---- candidate generation per scene of a fleet batch (teb_amd.h, fleet batches; kernels: the fleet forms of teb_graph.hpp) ----------
 int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
                                          double dist_to_obst, const double* start_vel, int32_t free_goal_vel, const int32_t* best,
                                          const double* unit_samples, int64_t max_paths, int32_t* n_total, int32_t* n_bands,
@@ -3286,7 +3267,6 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
   if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
   auto& F = h->fleet;
   const int ns = F.n_scenes, B0 = h->B;
-  const teb_amd_config_t& c = h->cfg;
   std::vector<int> plan_off(ns + 1, 0);
   for (int s = 0; s < ns; ++s) {
     const int np = plan_count ? plan_count[s] : 0;
@@ -3297,7 +3277,7 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
   }
   if ((rc = check_band_scenes(h, B0))) return rc;
   if ((rc = check_best_per_scene(h, best, B0, "teb_amd_explore_candidates_per_scene"))) return rc;
-  std::vector<std::vector<int>> of;   // the bands of every scene in band order; grows with the accepted candidates
+  std::vector<std::vector<int>> of;   // the bands of every scene in band order
   bands_per_scene(h, B0, of);
   const int slots = p->max_number_classes;   // per scene (the reference handle of the contract has max_tebs >= max_number_classes)
   {
@@ -3309,305 +3289,53 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
       return fail(TEB_AMD_ERR_CAPACITY, buf);
     }
   }
-  const int mode = c.include_dynamic_obstacles ? 3 : 2;
-  auto width = [&](int s) { return mode == 3 ? (int)F.tabs[s].rows() : 2; };
+  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;
   int widest = 0;
   for (const HostObst& t : F.tabs) widest = std::max(widest, (int)t.rows());
   const int q = h->explore_quota > 0 ? h->explore_quota : kExploreQuota;
   const size_t K = std::max<size_t>(kCandChunk, (size_t)q * ns);
   if ((rc = ensure_fleet_candidate_buffers(h, K, K * (size_t)std::max(widest, 2)))) return rc;
   for (int s = 0; s < ns; ++s) {
-    F.g_vx[s].clear(); F.g_vy[s].clear(); F.g_adj[s].clear();
+    F.memory[s].forget_graph();
     if (n_vertices) n_vertices[s] = 0;
     if (n_paths) n_paths[s] = 0;
     if (n_bands) n_bands[s] = (int)of[s].size();
     if (initial_plan_teb) initial_plan_teb[s] = -1;
   }
   if (n_total) *n_total = B0;
-  // ---- 1. equivalence_classes_ of the existing bands, one table per scene -----------------------------------------------------------
-  std::vector<ClassTable> ct(ns);
+  // equivalence_classes_ of the existing bands, one table per scene
   if (B0 > 0) {
     const bool fresh = F.hsig_mode == mode && F.hsig_B == B0 && F.hsig_prescaler == p->h_signature_prescaler;
     if (!fresh && (rc = teb_amd_compute_h_signatures_per_scene(h, p->h_signature_prescaler, nullptr, 0, nullptr, nullptr))) return rc;
   }
+  std::vector<TickPlanner> P(ns);
   for (int s = 0; s < ns; ++s) {
-    ClassTable& t = ct[s];
-    t.mode = mode; t.W = width(s); t.thr = p->h_signature_threshold; t.max_in_best = p->max_number_plans_in_current_class;
-    for (int b : of[s]) t.classes.emplace_back(F.hsig_host.data() + F.hsig_off[b], F.hsig_host.data() + F.hsig_off[b] + t.W);
-    if (best && best[s] >= 0) { F.best_class[s].assign(F.hsig_host.data() + F.hsig_off[best[s]], F.hsig_host.data() + F.hsig_off[best[s]] + t.W); F.best_class_mode[s] = mode; }
-    if (F.best_class_mode[s] == mode && (int)F.best_class[s].size() == t.W) { t.has_best = true; t.best = F.best_class[s]; }   // best_teb_eq_class_
+    TickPlanner& t = P[s];
+    const int np = plan_off[s + 1] - plan_off[s];
+    t.tab = &F.tabs[s]; t.mem = &F.memory[s];
+    t.start = start + 3 * s; t.goal = goal + 3 * s; t.start_vel = start_vel ? start_vel + 3 * s : nullptr;
+    t.n_plan = np;
+    if (np > 0) { t.plan_x = plan_x + plan_off[s]; t.plan_y = plan_y + plan_off[s]; t.plan_yaw = plan_yaw + plan_off[s]; }
+    t.unit_samples = unit_samples ? unit_samples + (size_t)s * 2 * std::max(p->roadmap_graph_no_samples, 0) : nullptr;
+    t.slots = slots; t.n_via = F.via_count[s];
+    t.n_vertices = n_vertices ? n_vertices + s : nullptr; t.n_paths = n_paths ? n_paths + s : nullptr;
+    t.initial_plan_teb = initial_plan_teb ? initial_plan_teb + s : nullptr;
+    std::vector<const double*> rows;
+    for (int b : of[s]) rows.push_back(F.hsig_host.data() + F.hsig_off[b]);
+    t.ct = seed_class_table(SignatureRule{mode, mode == 3 ? (int)F.tabs[s].rows() : 2, p->h_signature_threshold}, p->max_number_plans_in_current_class,
+                            rows, best && best[s] >= 0 ? F.hsig_host.data() + F.hsig_off[best[s]] : nullptr, F.memory[s]);
+    t.bands = std::move(of[s]);
   }
   h->signatures_stale();   // the batch is about to change
   h->consumers_valid = false; h->nmax_known = -1;
-  BatchDev cand = batch_of(h);   // the scratch strips of the scene set seen as a batch of K bands
-  cand.B = (int)K; cand.n = F.ex_n.p; cand.x = F.ex_x.p; cand.y = F.ex_y.p; cand.th = F.ex_th.p; cand.dt = F.ex_dt.p;
-  // the candidates of a launch: scene of every candidate, its signature values at sig[soff[k] ..)
-  std::vector<int> cscene, soff;
-  std::vector<double> sig;
-  auto classify = [&]() -> int {
-    const int count = (int)cscene.size();
-    soff.assign(count + 1, 0);
-    for (int k = 0; k < count; ++k) soff[k + 1] = soff[k] + width(cscene[k]);
-    const size_t total = (size_t)soff[count];
-    sig.assign(std::max<size_t>(total, 1), 0.0);
-    HIPCHK(hipMemcpyAsync(F.ex_scene.p, cscene.data(), count * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    FleetHsigDev fl;
-    fl.scenes = F.scenes.p; fl.scene_of = F.ex_scene.p; fl.off = F.ex_soff.p;
-    if (mode == 3) {
-      if (total > 0) {
-        HIPCHK(hipMemcpyAsync(F.ex_soff.p, soff.data(), soff.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        const bool wide = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE || (h->opt.hsig3d_kernel != TEB_AMD_HSIG3D_SMALL && (long long)total >= 32768);
-        if (wide)
-          hipLaunchKernelGGL(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                             h->stream, fl, cand, F.ex_sig.p);
-        else
-          hipLaunchKernelGGL(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                             h->stream, fl, cand, F.ex_sig.p);
-        HIPCHK(hipGetLastError());
-      }
-    } else {
-      if (widest > 0 && !F.hs_prod_valid) {   // the products of the set, shared with teb_amd_compute_h_signatures_per_scene
-        hipLaunchKernelGGL(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, ns), dim3(kThreads), 0, h->stream, F.scenes.p,
-                           F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p);
-        HIPCHK(hipGetLastError());
-        F.hs_prod_valid = true;
-      }
-      hipLaunchKernelGGL(hsig2d_fleet_kernel, dim3(count), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, cand,
-                         p->h_signature_prescaler, F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p, F.ex_sig.p);
-      HIPCHK(hipGetLastError());
-    }
-    if (total > 0) HIPCHK(hipMemcpyAsync(sig.data(), F.ex_sig.p, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    int err = 0;
-    HIPCHK(hipMemcpyAsync(&err, h->err_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (err) return fail(TEB_AMD_ERR_CAPACITY, "candidate band needs more poses than max_poses");
-    return TEB_AMD_OK;
-  };
-  // tebs_.push_back(candidate) of every scene: the accepted scratch bands -> the next slots of the batch in one gather, with the
-  // defaults of a new TebOptimalPlanner, setVelocityStart / setVelocityGoalFree of their scene, and their entries of the map
-  auto accept_all = [&](const std::vector<int>& acc) -> int {
-    if (acc.empty()) return TEB_AMD_OK;
-    const int slot0 = h->B, cnt = (int)acc.size();
-    if (slot0 + cnt > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more bands than max_tebs");   // (excluded by the capacity rule)
-    std::vector<int> ones(cnt, 1), rot(cnt, TEB_AMD_ROT_NONE), hvg(cnt, free_goal_vel ? 0 : 1), zero(cnt, 0);
-    std::vector<double> vv(3 * (size_t)cnt, 0.0), z3(3 * (size_t)cnt, 0.0);
-    for (int k = 0; k < cnt; ++k) {
-      const int s = cscene[acc[k]];
-      if (start_vel) for (int j = 0; j < 3; ++j) vv[3 * k + j] = start_vel[3 * s + j];
-      F.band_scene[slot0 + k] = s;
-      of[s].push_back(slot0 + k);
-    }
-    HIPCHK(hipMemcpyAsync(h->has_vs.p + slot0, ones.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->has_vg.p + slot0, hvg.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->rotdir.p + slot0, rot.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->via_en.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));   // born without via-points
-    HIPCHK(hipMemcpyAsync(h->optimized.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->vs.p + 3 * (size_t)slot0, vv.data(), vv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->vg.p + 3 * (size_t)slot0, z3.data(), z3.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(F.scene_of.p + slot0, F.band_scene.data() + slot0, cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(F.ex_map.p, acc.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    h->B = slot0 + cnt;
-    hipLaunchKernelGGL(move_bands_kernel, dim3(cnt), dim3(kThreads), 0, h->stream, cand, batch_of(h), F.ex_map.p, slot0, 0);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));   // the staging vectors live on this stack frame
-    return TEB_AMD_OK;
-  };
-  auto sig_of = [&](int k) { return sig.data() + soff[k]; };
-  std::vector<int> initial_idx(ns, -1);   // initial_plan_teb_ of every scene: position among the scene's bands
-  auto body = [&]() -> int {
-    // ---- 2. the initial plans as candidates: addAndInitNewTeb(*initial_plan_, ...), one launch ---------------------------------------
-    cscene.clear();
-    std::vector<int> off(1, 0);
-    std::vector<double> px, py, pyaw;
-    for (int s = 0; s < ns; ++s) {
-      const int np = plan_off[s + 1] - plan_off[s];
-      if (np <= 0 || (int)of[s].size() >= slots) continue;
-      px.insert(px.end(), plan_x + plan_off[s], plan_x + plan_off[s + 1]);
-      py.insert(py.end(), plan_y + plan_off[s], plan_y + plan_off[s + 1]);
-      pyaw.insert(pyaw.end(), plan_yaw + plan_off[s], plan_yaw + plan_off[s + 1]);
-      off.push_back((int)px.size());
-      cscene.push_back(s);
-    }
-    if (!cscene.empty()) {
-      const int count = (int)cscene.size();
-      HIPCHK(hipMemcpyAsync(F.ex_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_px.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_py.p, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_pyaw.p, pyaw.data(), pyaw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-      hipLaunchKernelGGL(init_plan_batch_kernel, dim3(count), dim3(kThreads), 0, h->stream, cand, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_pyaw.p,
-                         c.max_vel_x, c.max_vel_theta, p->global_plan_overwrite_orientation, c.min_samples, p->allow_init_with_backwards_motion,
-                         h->err_flag.p);
-      HIPCHK(hipGetLastError());
-      if (int r = classify()) return r;
-      std::vector<int> acc;
-      for (int k = 0; k < count; ++k) {
-        const int s = cscene[k];
-        F.initial_class[s].assign(sig_of(k), sig_of(k) + ct[s].W); F.initial_class_mode[s] = mode;   // initial_plan_eq_class_
-        if (ct[s].add_if_new(sig_of(k))) { acc.push_back(k); initial_idx[s] = (int)of[s].size(); }
-      }
-      if (int r = accept_all(acc)) return r;
-    }
-    // ---- 3. vertices, on the host scene by scene; the scenes that return before their graph -------------------------------------------
-    struct Graph { int s; std::vector<double> vx, vy; GraphArgs ga; std::vector<std::vector<int>> adj; };
-    std::vector<Graph> graphs;
-    std::vector<int> at_goal;   // at their goal without a band: a line band (addAndInitNewTeb(start, goal, ...), hcp.cpp:358-384)
-    for (int s = 0; s < ns; ++s) {
-      if ((int)of[s].size() >= slots) continue;                                 // src/graph_search.cpp:99-100, 231-232
-      const double* st = start + 3 * s; const double* gl = goal + 3 * s;
-      const double dfx = gl[0] - st[0], dfy = gl[1] - st[1];
-      const double start_goal_dist = std::sqrt(dfx * dfx + dfy * dfy);
-      if (start_goal_dist < p->xy_goal_tolerance) {                             // :104-113, :237-246
-        if (of[s].empty()) at_goal.push_back(s);
-        continue;
-      }
-      graphs.emplace_back();
-      Graph& g = graphs.back();
-      g.s = s;
-      graph_vertices(F.tabs[s], st, gl, start_goal_dist, dist_to_obst, p, F.rnd[s],
-                     unit_samples ? unit_samples + (size_t)s * 2 * std::max(p->roadmap_graph_no_samples, 0) : nullptr, g.vx, g.vy, g.ga);
-      g.ga.N = (int)g.vx.size();
-      if (n_vertices) n_vertices[s] = g.ga.N;
-    }
-    // ---- 4. edges: every graph in one launch, one download --------------------------------------------------------------------------
-    if (!graphs.empty()) {
-      size_t nv = 0, na = 0;
-      long long most = 0;
-      for (const Graph& g : graphs) { nv += g.vx.size(); na += g.vx.size() * g.vx.size(); most = std::max(most, (long long)g.ga.N * g.ga.N); }
-      if (F.ex_gvx.n < nv) { F.ex_gvx.free(); F.ex_gvy.free(); HIPCHK(F.ex_gvx.alloc(nv)); HIPCHK(F.ex_gvy.alloc(nv)); }
-      if (F.ex_gadj.n < na) { F.ex_gadj.free(); HIPCHK(F.ex_gadj.alloc(na)); }
-      std::vector<double> allx, ally;
-      std::vector<GraphFleetRec> recs(graphs.size());
-      size_t vo = 0, ao = 0;
-      for (size_t i = 0; i < graphs.size(); ++i) {
-        Graph& g = graphs[i];
-        allx.insert(allx.end(), g.vx.begin(), g.vx.end()); ally.insert(ally.end(), g.vy.begin(), g.vy.end());
-        g.ga.gx = F.ex_gvx.p + vo; g.ga.gy = F.ex_gvy.p + vo; g.ga.adj = F.ex_gadj.p + ao;
-        recs[i].g = g.ga; recs[i].scene = g.s;
-        vo += g.vx.size(); ao += g.vx.size() * g.vx.size();
-      }
-      HIPCHK(hipMemcpyAsync(F.ex_gvx.p, allx.data(), nv * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_gvy.p, ally.data(), nv * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_rec.p, recs.data(), recs.size() * sizeof(GraphFleetRec), hipMemcpyHostToDevice, h->stream));
-      hipLaunchKernelGGL(graph_edges_fleet_kernel, dim3((unsigned)((most + kThreads - 1) / kThreads), (unsigned)graphs.size()), dim3(kThreads), 0,
-                         h->stream, F.scenes.p, F.ex_rec.p);
-      HIPCHK(hipGetLastError());
-      std::vector<unsigned char> adjm(na);
-      HIPCHK(hipMemcpyAsync(adjm.data(), F.ex_gadj.p, na, hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-      ao = 0;
-      for (Graph& g : graphs) {
-        const int N = g.ga.N;
-        g.adj.assign(N, {});
-        for (int i = 0; i < N; ++i)
-          for (int j = 0; j < N; ++j) if (adjm[ao + (size_t)i * N + j]) g.adj[i].push_back(j);   // add_edge order of the double loop
-        F.g_vx[g.s] = g.vx; F.g_vy[g.s] = g.vy;
-        F.g_adj[g.s].assign(adjm.begin() + ao, adjm.begin() + ao + (size_t)N * N);
-        ao += (size_t)N * N;
-      }
-    }
-    // ---- 5. rounds: up to q paths of every scene that has room and paths left; init, classify, first come first served per scene -------
-    std::vector<double> orient(2 * (size_t)ns, 0.0);
-    for (int s = 0; s < ns; ++s) { orient[2 * s] = start[3 * s + 2]; orient[2 * s + 1] = goal[3 * s + 2]; }
-    if (!graphs.empty()) HIPCHK(hipMemcpyAsync(F.ex_orient.p, orient.data(), orient.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    std::vector<PathEnumerator> en;
-    en.reserve(graphs.size());
-    for (Graph& g : graphs) {
-      en.emplace_back(g.adj, 0, g.ga.N - 1);
-      if (max_paths > 0) en.back().max_expansions = max_paths * 10000;
-    }
-    std::vector<int64_t> examined(graphs.size(), 0);
-    std::vector<char> more(graphs.size(), 1);
-    std::vector<int> path, cgraph;
-    for (;;) {
-      off.assign(1, 0); px.clear(); py.clear(); cscene.clear(); cgraph.clear();
-      for (size_t i = 0; i < graphs.size(); ++i) {
-        const int s = graphs[i].s;
-        if (!more[i] || (int)of[s].size() >= slots) continue;
-        int count = 0;
-        while (count < q && (max_paths <= 0 || examined[i] + count < max_paths)) {
-          if (!en[i].next(path)) { more[i] = 0; break; }
-          if ((int)path.size() > h->stride + 1) return fail(TEB_AMD_ERR_CAPACITY, "a start-goal path has more vertices than a band has poses (max_poses)");
-          for (int v : path) { px.push_back(graphs[i].vx[v]); py.push_back(graphs[i].vy[v]); }
-          off.push_back((int)px.size());
-          cscene.push_back(s); cgraph.push_back((int)i);
-          ++count;
-        }
-        if (max_paths > 0 && examined[i] + count >= max_paths) more[i] = 0;
-      }
-      const int count = (int)cscene.size();
-      if (count == 0) break;
-      HIPCHK(hipMemcpyAsync(F.ex_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_px.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_py.p, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(F.ex_scene.p, cscene.data(), count * sizeof(int), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-      hipLaunchKernelGGL(init_path_fleet_kernel, dim3(count), dim3(kThreads), 0, h->stream, cand, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_scene.p,
-                         F.ex_orient.p, c.max_vel_x, c.acc_lim_x, c.min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
-      HIPCHK(hipGetLastError());
-      if (int r = classify()) return r;
-      std::vector<int> acc;
-      for (int k = 0; k < count; ++k) {   // the candidates of a scene lie together, in path order
-        const int s = cscene[k], i = cgraph[k];
-        int pending = 0;
-        for (int a : acc) pending += cscene[a] == s;
-        if ((int)of[s].size() + pending >= slots) continue;
-        ++examined[i];
-        if (ct[s].add_if_new(sig_of(k))) acc.push_back(k);
-      }
-      if (int r = accept_all(acc)) return r;
-    }
-    for (size_t i = 0; i < graphs.size(); ++i)
-      if (n_paths) n_paths[graphs[i].s] = (int32_t)std::min<int64_t>(examined[i], std::numeric_limits<int32_t>::max());
-    // ---- 6. the scenes at their goal without a band: their line bands in one launch ---------------------------------------------------
-    if (!at_goal.empty()) {
-      const int count = (int)at_goal.size();
-      cscene = at_goal;
-      std::vector<double> pose(6 * (size_t)count);
-      for (int k = 0; k < count; ++k)
-        for (int j = 0; j < 3; ++j) { pose[6 * k + j] = start[3 * at_goal[k] + j]; pose[6 * k + 3 + j] = goal[3 * at_goal[k] + j]; }
-      HIPCHK(hipMemcpyAsync(F.ex_line.p, pose.data(), pose.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-      hipLaunchKernelGGL(init_line_batch_kernel, dim3(count), dim3(kThreads), 0, h->stream, cand, F.ex_line.p, 0.0, c.max_vel_x, c.min_samples,
-                         p->allow_init_with_backwards_motion, h->err_flag.p);
-      HIPCHK(hipGetLastError());
-      if (int r = classify()) return r;
-      std::vector<int> acc;
-      for (int k = 0; k < count; ++k) if (ct[at_goal[k]].add_if_new(sig_of(k))) acc.push_back(k);
-      if (int r = accept_all(acc)) return r;
-    }
-    return TEB_AMD_OK;
-  };
-  rc = body();
+  FleetRoute R{h, p, {batch_of(h), F.ex_map.p, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_sig.p}, q, widest, {}, {}, {}, {}};
+  BatchDev& c = R.sc.cand;   // the scratch strips of the scene set seen as a batch of K bands
+  c.B = (int)K; c.n = F.ex_n.p; c.x = F.ex_x.p; c.y = F.ex_y.p; c.th = F.ex_th.p; c.dt = F.ex_dt.p;
+  rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths);
   if (n_total) *n_total = h->B;
-  for (int s = 0; s < ns; ++s) if (n_bands) n_bands[s] = (int)of[s].size();
+  for (int s = 0; s < ns; ++s) if (n_bands) n_bands[s] = (int)P[s].bands.size();
   if (rc) return rc;
-  // ---- 7. getInitialPlanTEB (:495-536) and updateReferenceTrajectoryViaPoints (:286-315) scene by scene, one upload of via_en ---------
-  const int B = h->B;
-  std::vector<int> ve(std::max(B, 1), 0);
-  bool any_rule = false;
-  if (B > 0) HIPCHK(hipMemcpyAsync(ve.data(), h->via_en.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  for (int s = 0; s < ns; ++s) {
-    const ClassTable& t = ct[s];
-    const int Bs = (int)of[s].size();
-    const bool have_initial_class = F.initial_class_mode[s] == mode && (int)F.initial_class[s].size() == t.W && t.valid(F.initial_class[s].data());
-    if (initial_idx[s] < 0 && have_initial_class)
-      for (int b = 0; b < Bs && b < (int)t.classes.size(); ++b)
-        if (t.equal(t.classes[b].data(), F.initial_class[s].data())) { initial_idx[s] = b; break; }
-    if (initial_plan_teb) initial_plan_teb[s] = initial_idx[s];
-    const int np = plan_off[s + 1] - plan_off[s];
-    if (Bs > 0 && !((!p->viapoints_all_candidates && np <= 0) || F.via_count[s] <= 0 || c.weight_viapoint <= 0)) {
-      any_rule = true;
-      for (int b = 0; b < Bs; ++b)
-        ve[of[s][b]] = p->viapoints_all_candidates ? 1 : (have_initial_class && b < (int)t.classes.size() && t.equal(F.initial_class[s].data(), t.classes[b].data()));
-    }
-  }
-  if (any_rule) {
-    HIPCHK(hipMemcpyAsync(h->via_en.p, ve.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  return TEB_AMD_OK;
+  return finish_tick(h, p, P);
 }
 
 int teb_amd_get_exploration_graph_per_scene(teb_amd_handle_t* h, int32_t scene, double* vx, double* vy, unsigned char* adjacency,
@@ -3615,16 +3343,8 @@ int teb_amd_get_exploration_graph_per_scene(teb_amd_handle_t* h, int32_t scene, 
   int rc = check_handle(h);
   if (rc) return rc;
   if ((rc = require_fleet_mode(h, "teb_amd_get_exploration_graph_per_scene"))) return rc;
-  auto& F = h->fleet;
-  if (scene < 0 || scene >= F.n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_exploration_graph_per_scene: scene out of range");
-  const int N = (int)F.g_vx[scene].size();
-  if (n_vertices) *n_vertices = N;
-  if (N == 0 || (!vx && !vy && !adjacency)) return TEB_AMD_OK;
-  if (capacity_vertices < N) return fail(TEB_AMD_ERR_CAPACITY, "graph has more vertices than capacity_vertices");
-  if (vx) std::copy(F.g_vx[scene].begin(), F.g_vx[scene].end(), vx);
-  if (vy) std::copy(F.g_vy[scene].begin(), F.g_vy[scene].end(), vy);
-  if (adjacency) std::copy(F.g_adj[scene].begin(), F.g_adj[scene].end(), adjacency);
-  return TEB_AMD_OK;
+  if (scene < 0 || scene >= h->fleet.n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_exploration_graph_per_scene: scene out of range");
+  return copy_graph(h->fleet.memory[scene], vx, vy, adjacency, capacity_vertices, n_vertices);
 }
 
 namespace {
@@ -3742,38 +3462,6 @@ int teb_amd_compact_bands_per_scene(teb_amd_handle_t* h, const int32_t* keep, co
 }
 
 namespace {
-// deletePlansDetouringBackwards over the bands `order` of ONE planner (src/homotopy_class_planner.cpp:760-820), in two halves: whether
-// the rule runs at all - it needs two kept bands and a kept best one - and the rule over the statistics of detour_stats_kernel
-// (st [4 * band]) and the optimized flags (opt [band]).
-bool detour_rule_runs(const std::vector<int>& order, int best, const int32_t* keep) {
-  int kept = 0;
-  for (int b : order) kept += keep[b] != 0;
-  return kept >= 2 && std::find(order.begin(), order.end(), best) != order.end() && keep[best];   // "a moving direction wasn't chosen yet", :769-773
-}
-void apply_detour_rule(const std::vector<int>& order, int best, const teb_amd_hcp_params_t* p, const double* st, const int* opt, int32_t* keep) {
-  auto found = [&](int b) { return st[4 * b] != 0; };
-  auto orient = [&](int b) { return st[4 * b + 1]; };
-  auto duration = [&](int b) { return st[4 * b + 2]; };
-  auto poses = [&](int b) { return (int)st[4 * b + 3]; };
-  if (poses(best) < 2) return;
-  const double best_plan_duration = std::max(duration(best), 1.0);
-  if (!found(best)) return;   // the plan is shorter than len_orientation_vector
-  auto normalize_theta = [](double theta) {   // g2o::normalize_theta (misc.h)
-    if (theta >= -M_PI && theta < M_PI) return theta;
-    const double multiplier = std::floor(theta / (2 * M_PI));
-    theta = theta - multiplier * 2 * M_PI;
-    if (theta >= M_PI) theta -= 2 * M_PI;
-    if (theta < -M_PI) theta += 2 * M_PI;
-    return theta;
-  };
-  for (int b : order) {
-    if (!keep[b] || b == best) continue;
-    if (poses(b) < 2 || !found(b)) { keep[b] = 0; continue; }
-    if (std::fabs(normalize_theta(orient(b) - orient(best))) > p->detours_orientation_tolerance) { keep[b] = 0; continue; }
-    if (!opt[b]) { keep[b] = 0; continue; }
-    if (duration(b) / best_plan_duration > p->max_ratio_detours_duration_best_duration) { keep[b] = 0; continue; }
-  }
-}
 // detour_stats_kernel over all B bands: st [4 * B], opt [B]
 int detour_statistics(teb_amd_handle* h, const teb_amd_hcp_params_t* p, int B, std::vector<double>& st, std::vector<int>& opt) {
   if (int rc = ensure_candidate_buffers(h)) return rc;

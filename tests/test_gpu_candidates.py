@@ -383,3 +383,79 @@ def test_argument_errors_are_reported_not_ignored():
         t.explore_candidates(case["start"], case["goal"])
     assert e.value.code == _abi.ERR_CAPACITY
     s.close(); t.close()
+
+
+def test_one_handle_remembers_across_calls_and_forgets_its_graph_at_the_goal(oracle):
+    """What the single scene's planner keeps between exploration calls - best_teb_eq_class_, initial_plan_eq_class_, the roadmap's
+    generator - survives teb_amd_set_obstacles of the same table, and an exploration that returns before its graph (start at the goal)
+    leaves no graph behind. Two fresh handles driven through the same calls agree bit for bit; the expected values are the oracle's, which
+    is GIVEN what the handle has to remember (the class of the first call's first band as stale best and stale initial class, six skipped
+    draws). Two point obstacles, 32 poses, roadmap of 3 samples, 3 classes, two plans in the best class: on this scene every remembered
+    item changes the second call's outcome, which the oracle itself shows below."""
+    from teb_local_planner_amd.config import TebConfig
+    cfg = TebConfig()
+    cfg.obstacles.include_dynamic_obstacles = True
+    h = cfg.hcp
+    h.simple_exploration = False; h.roadmap_graph_no_samples = 3; h.max_number_classes = 3; h.max_number_plans_in_current_class = 2
+    obst = _abi.ObstacleTable()
+    obst.add_point(4.0, 0.25); obst.add_point(4.0, -2.5)
+    start, goal, d2o, stride = [0.0, 0.0, 0.1], [8.0, 0.5, -0.2], 0.3, 32
+    xs = np.linspace(start[0], goal[0], 9)
+    ys = goal[1] * xs / goal[0] - 1.6 * np.sin(np.pi * xs / goal[0])   # a coarse global plan swinging right of the first obstacle
+    plan = (xs, ys, np.arctan2(np.gradient(ys), np.gradient(xs)))
+    empty = _abi.TebBatchHost(h.max_number_classes, stride)
+    # ---- expected: the oracle, call by call
+    o1 = oracle.explore_candidates(cfg, obst, empty, 0, -1, start, goal, dist_to_obst=d2o, initial_plan=plan)
+    assert o1["n_total"] == 2 and o1["initial_plan_teb"] == 0
+    first = stale_signature(oracle, dict(cfg=cfg, obst=obst, stale_band=o1["batch"].get_teb(0)))
+    second = lambda **kw: oracle.explore_candidates(cfg, obst, empty, 0, -1, start, goal, dist_to_obst=d2o, **kw)
+    o2 = second(skip_draws=2 * h.roadmap_graph_no_samples, stale_best_sig=first, stale_initial_sig=first)
+    assert o2["n_total"] == 3 and o2["initial_plan_teb"] == 1
+    assert second(skip_draws=6, stale_initial_sig=first)["n_total"] == 2             # without the best class: its second plan is refused
+    assert second(skip_draws=6, stale_best_sig=first)["initial_plan_teb"] == -1      # without the initial plan's class
+    assert second(stale_best_sig=first, stale_initial_sig=first)["n_total"] == 1     # with the first call's samples again
+
+    def drive():
+        s = planner.TebBatchSolver(cfg, h.max_number_classes, stride, 2, 1, 1)
+        s.set_obstacles(obst); s.set_via_points([])
+        seen = []
+
+        def look(r):
+            V, A = s.exploration_graph()
+            seen.append((r["n_total"], r["n_vertices"], r["n_paths"], r["initial_plan_teb"], V, A, [tuple(np.copy(a) for a in b) for b in _bands(s, stride)]))
+
+        look(s.explore_candidates(start, goal, dist_to_obst=d2o, initial_plan=plan))
+        s.h_signatures(h.h_signature_prescaler)
+        s.filter_equivalence_classes(h.h_signature_threshold, 0, h.max_number_plans_in_current_class)   # band 0 is the best band
+        s.compact_bands(np.zeros(s.count, np.int32))                                                    # tebs_.clear()
+        assert s.count == 0
+        s.set_obstacles(obst)
+        look(s.explore_candidates(start, goal, dist_to_obst=d2o))
+        s.compact_bands(np.array([1, 1, 0], np.int32))             # a free slot again: the next call gets past the slot limit
+        look(s.explore_candidates(goal, goal, dist_to_obst=d2o))   # at the goal with bands: nothing new, and no graph
+        s.close()
+        return seen
+
+    a, b = drive(), drive()
+    for got in (a, b):
+        for (n_total, n_vertices, n_paths, ipt, V, A, bands), o in zip(got[:2], (o1, o2)):
+            assert (n_total, ipt) == (o["n_total"], o["initial_plan_teb"])
+            assert n_vertices == len(V) == len(o["vertices"]) == 5   # start, 3 samples, goal
+            assert np.abs(V - o["vertices"]).max() <= TOL
+            want = np.zeros((5, 5), A.dtype)
+            for i, out in enumerate(o["adjacency"]):
+                want[i, out] = 1
+            np.testing.assert_array_equal(A, want)
+            for k in range(n_total):
+                for u, v in zip(bands[k], o["batch"].get_teb(k)):
+                    assert len(u) == len(v) and np.abs(u - v).max(initial=0) <= TOL
+        n_total, n_vertices, n_paths, ipt, V, A, bands = got[2]
+        assert (n_total, n_vertices, n_paths, len(V), A.size) == (2, 0, 0, 0, 0)
+        assert ipt == 1   # no plan in this call either: the band is still found by its class
+    assert not np.array_equal(a[0][4], a[1][4])   # the second roadmap continues the generator
+    for x, y in zip(a, b):
+        assert x[:4] == y[:4]
+        np.testing.assert_array_equal(x[4], y[4]); np.testing.assert_array_equal(x[5], y[5])
+        for p, q in zip(x[6], y[6]):
+            for u, v in zip(p, q):
+                np.testing.assert_array_equal(u, v)
