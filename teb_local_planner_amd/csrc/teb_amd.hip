@@ -31,6 +31,7 @@
 #include "teb_plan_window.hpp"
 #include "teb_scene_store.hpp"
 #include "teb_hcp_host.hpp"
+#include "teb_costmap_host.hpp"
 
 using namespace tebamd;
 
@@ -59,6 +60,8 @@ int fail(int code, const std::string& msg) {
     if (_e != hipSuccess)                                                                              \
       return fail(TEB_AMD_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(_e));               \
   } while (0)
+// a kernel launch (the arguments of hipLaunchKernelGGL) and its launch error
+#define LAUNCH(...) do { hipLaunchKernelGGL(__VA_ARGS__); HIPCHK(hipGetLastError()); } while (0)
 
 // K9: selectBestTeb on the resident cost array (src/homotopy_class_planner.cpp:564-667)
 __global__ void select_best_kernel(const double* cost, int count, int last_best, int initial_plan, double hyst,
@@ -199,9 +202,7 @@ struct teb_amd_handle {
   DevBuf<unsigned char> cm_cells;
   DevBuf<double> cm_fp;
   DevBuf<int> cm_out;
-  int cm_sx = 0, cm_sy = 0;
-  double cm_res = 0, cm_ox = 0, cm_oy = 0;
-  DevBuf<int> cmo_cnt;   // teb_amd_set_obstacles_from_costmap: kept cells per (column, chunk of rows), then their offsets + the total
+  GridDev cm{};   // the single costmap (teb_amd_set_costmap) over cm_cells; sx = 0: none
   // the costmap set (teb_amd_set_costmaps): one grid per scene of a fleet, beside the single costmap above, which it never touches. The
   // grids lie one after the other in ONE buffer; grids_host holds the GridDev records of the device array (device pointers).
   struct CostmapSet {
@@ -210,19 +211,25 @@ struct teb_amd_handle {
     DevBuf<GridDev> grids;
     std::vector<GridDev> grids_host;
   } cms;
-  // scratch of the per-scene calls at both ends of a fleet tick: the records and totals of teb_amd_set_scenes_from_costmaps and its
-  // points, the bands of teb_amd_is_trajectory_feasible_per_scene, the message of teb_amd_update_and_prune_per_scene
-  DevBuf<CmoSceneRec> cms_rec;
-  DevBuf<int> cms_tot, cms_bands;
-  DevBuf<double> cms_px, cms_py, prune_msg;
-  // teb_amd_set_obstacles_from_costmap_polygons: rows / vertices / polygon vertices per block (then their offsets + totals), and the
-  // converted rows (first-vertex offsets, vertex coordinates) before the host builds the table from them
-  DevBuf<int> cmp_cnt, cmp_off;
-  DevBuf<double> cmp_x, cmp_y;
-  // teb_amd_set_scenes_from_costmap_polygons shares them and adds the records of the scenes, the prefix array of their block counts
-  // and the 3 x n_scenes totals
-  DevBuf<CmpSceneRec> cmp_rec;
-  DevBuf<int> cmp_blk, cmp_tot;
+  // scratch of the costmap conversion (convert_costmaps), shared by its two row kinds and two routes
+  struct CostmapScratch {
+    // point route: kept cells per lane, then their offsets + a total per scene; of a set also the records and totals of the scenes
+    // (max_tebs each, allocated once) and the points of the write pass (max_obstacles, allocated once)
+    DevBuf<int> cnt, tot;
+    DevBuf<CmoSceneRec> rec;
+    DevBuf<double> px, py;
+    // polygon route: rows / vertices / polygon vertices per block (then their offsets + totals) and the converted rows (first-vertex
+    // offsets, vertex coordinates) before the host builds the tables from them; of a set also the records of the scenes, the prefix
+    // array of their block counts and the 3 x n_scenes totals (by max_tebs, allocated once)
+    DevBuf<int> pcnt, poff, blk, ptot;
+    DevBuf<CmpSceneRec> prec;
+    DevBuf<double> pvx, pvy;
+    void free() { free_all(cnt, tot, rec, px, py, pcnt, poff, blk, ptot, prec, pvx, pvy); }
+  } cmx;
+  // scratch of the per-scene calls at the far end of a fleet tick: the bands of teb_amd_is_trajectory_feasible_per_scene, the message
+  // of teb_amd_update_and_prune_per_scene
+  DevBuf<int> cms_bands;
+  DevBuf<double> prune_msg;
   // the global plans (teb_amd_set_global_plans): the plans of every robot one after the other in ONE buffer (x | y | yaw planes of
   // `total` poses), their first poses, counts and pruning cursors, and the scratch of teb_amd_plan_windows: the poses / transforms /
   // thresholds of a call, the per-robot records, the pack buffer of the windows and via-points and its ticket. Beside the costmap set
@@ -287,6 +294,11 @@ namespace {
 int check_handle(teb_amd_handle* h) {
   if (!h) return fail(TEB_AMD_ERR_INVALID_ARG, "null handle");
   if (hipSetDevice(h->device) != hipSuccess) return fail(TEB_AMD_ERR_HIP, "hipSetDevice failed");
+  return TEB_AMD_OK;
+}
+
+int synced(teb_amd_handle* h) {
+  HIPCHK(hipStreamSynchronize(h->stream));
   return TEB_AMD_OK;
 }
 
@@ -533,9 +545,7 @@ struct Strips { double *x, *y, *th, *dt; int* n; };
 static int copy_strips(teb_amd_handle_t* h, const Strips& dst, const Strips& src, int bands) {
   const size_t count = (size_t)bands * h->stride;   // >= bands
   const int grid = (int)std::min<size_t>(2048, (count + 255) / 256);
-  hipLaunchKernelGGL(copy_state_kernel, dim3(grid), dim3(256), 0, h->stream, dst.x, dst.y, dst.th, dst.dt, dst.n, src.x, src.y, src.th,
-                     src.dt, src.n, count, bands);
-  HIPCHK(hipGetLastError());
+  LAUNCH(copy_state_kernel, dim3(grid), dim3(256), 0, h->stream, dst.x, dst.y, dst.th, dst.dt, dst.n, src.x, src.y, src.th, src.dt, src.n, count, bands);
   return TEB_AMD_OK;
 }
 
@@ -858,14 +868,14 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   h->scene.free();
   h->fleet.release();
+  h->cmx.free();
   free_all(h->n, h->has_vs, h->has_vg, h->rotdir, h->via_en, h->status, h->optimized, h->iters, h->last_iters, h->trials, h->assoc_cnt, h->assoc, h->assoc_ovf,
            h->via_pose, h->legacy_idx, h->snap_n, h->sel_idx, h->err_flag, h->hs_pex, h->x, h->y, h->th, h->dt, h->vs, h->vg, h->chi2, h->cost, h->lambda,
            h->Hbackup, h->Hband, h->ob_x, h->ob_y, h->ob_th, h->ob_dt, h->ob_n, h->snap_x, h->snap_y, h->snap_th, h->snap_dt, h->dbg_H, h->dbg_b, h->dbg_chi2,
            h->sel_cost, h->stage_x, h->stage_y, h->stage_yaw, h->out_cmd, h->out_prof, h->out_traj, h->hsig, h->hs_pre, h->hs_pim, h->g_vx, h->g_vy, h->cand_x,
            h->cand_y, h->cand_th, h->cand_dt, h->cand_sig, h->cand_px, h->cand_py, h->tmp_x, h->tmp_y, h->tmp_th, h->tmp_dt, h->tmp_vs, h->tmp_vg, h->tmp_chi2,
            h->tmp_cost, h->tmp_lambda, h->cand_n, h->cand_off, h->cand_map, h->tmp_n, h->tmp_i, h->iter_log, h->phase_log, h->mcu_ctl, h->mcu_pub, h->mcu_items,
-           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cmo_cnt, h->cmp_cnt, h->cmp_off, h->cmp_x, h->cmp_y, h->cmp_rec, h->cmp_blk, h->cmp_tot,
-           h->cms.cells, h->cms.grids, h->cms_rec, h->cms_tot, h->cms_bands, h->cms_px, h->cms_py, h->prune_msg,
+           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cms.cells, h->cms.grids, h->cms_bands, h->prune_msg,
            h->plans.poses, h->plans.in, h->plans.pack, h->plans.first, h->plans.count, h->plans.cursor, h->plans.rec, h->plans.ticket);
   if (h->mcu_trace) (void)hipHostFree(h->mcu_trace);
   if (h->pack_host) (void)hipHostFree(h->pack_host);
@@ -1087,6 +1097,8 @@ int install_scene_set(teb_amd_handle* h, std::vector<HostObst>&& tabs, std::vect
   if (F.memory.size() != (size_t)n_scenes) F.new_planners(n_scenes);   // a remembered class belongs to a robot: kept while the fleet keeps its size
   return TEB_AMD_OK;
 }
+// what the tables and via-points of a scene set may hold together (parse_scene_inputs, teb_costmap_host.hpp)
+extern "C++" SceneCaps handle_caps(const teb_amd_handle* h) { return SceneCaps{(size_t)h->max_obst, (size_t)h->max_verts, (size_t)h->max_via}; }
 }  // namespace
 
 int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obstacles_t* obstacles, const int32_t* via_count, const double* via_x,
@@ -1096,23 +1108,9 @@ int teb_amd_set_scenes(teb_amd_handle_t* h, int32_t n_scenes, const teb_amd_obst
   if (n_scenes < 1 || !obstacles) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scenes: needs at least one scene");
   if (n_scenes > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more scenes than max_tebs");
   // everything is parsed and checked before the first upload: on an error the previous scene set stays installed
-  std::vector<HostObst> tabs(n_scenes);
-  std::vector<int> vc(n_scenes, 0);
-  size_t rows = 0, verts = 0, vias = 0;
-  for (int s = 0; s < n_scenes; ++s) {
-    if (obstacles[s].count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "null obstacle table");
-    if (const char* bad = parse_obstacle_table(&obstacles[s], tabs[s])) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
-    rows += tabs[s].rows(); verts += tabs[s].verts();
-    if (via_count) {
-      if (via_count[s] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
-      vc[s] = via_count[s]; vias += (size_t)via_count[s];
-    }
-  }
-  if (vias > 0 && (!via_x || !via_y)) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
-  if (rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
-  if (verts > (size_t)h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
-  if (vias > (size_t)h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
-  return install_scene_set(h, std::move(tabs), std::move(vc), via_x, via_y, vias);
+  SceneInputs in;
+  if (Refusal r = parse_scene_inputs(n_scenes, obstacles, "null obstacle table", via_count, via_x, via_y, handle_caps(h), in)) return fail(r.code, r.text);
+  return install_scene_set(h, std::move(in.tabs), std::move(in.vc), via_x, via_y, in.vias);
 }
 
 int teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_t count) {
@@ -1176,9 +1174,8 @@ int teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best,
   }
   HIPCHK(hipMemcpyAsync(F.sel_last.p, lb.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(F.sel_init.p, ip.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(select_best_per_scene_kernel, dim3(ns), dim3(kThreads), 0, h->stream, h->cost.p, F.scene_of.p, h->B, F.sel_last.p, F.sel_init.p,
-                     h->cfg.selection_cost_hysteresis, h->cfg.selection_prefer_initial_plan, F.sel_cost.p, F.sel_idx.p);
-  HIPCHK(hipGetLastError());
+  LAUNCH(select_best_per_scene_kernel, dim3(ns), dim3(kThreads), 0, h->stream, h->cost.p, F.scene_of.p, h->B, F.sel_last.p, F.sel_init.p,
+         h->cfg.selection_cost_hysteresis, h->cfg.selection_prefer_initial_plan, F.sel_cost.p, F.sel_idx.p);
   std::vector<double> cst(ns);
   HIPCHK(hipMemcpyAsync(best, F.sel_idx.p, ns * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(cst.data(), F.sel_cost.p, ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1226,9 +1223,8 @@ int teb_amd_upload_tebs(teb_amd_handle_t* h, const teb_amd_teb_batch_t* bt) {
     const size_t count = 11 * (size_t)B + 4 * plane;
     HIPCHK(hipMemcpyAsync(h->pack_dev.p, m, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const int grid = (int)std::min<size_t>(256, (std::max<size_t>(plane, 3 * (size_t)B) + 255) / 256);
-    hipLaunchKernelGGL(unpack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->n.p, h->has_vs.p, h->has_vg.p, h->rotdir.p,
-                       h->via_en.p, h->vs.p, h->vg.p, h->x.p, h->y.p, h->th.p, h->dt.p, h->optimized.p);
-    HIPCHK(hipGetLastError());
+    LAUNCH(unpack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->n.p, h->has_vs.p, h->has_vg.p, h->rotdir.p,
+           h->via_en.p, h->vs.p, h->vg.p, h->x.p, h->y.p, h->th.p, h->dt.p, h->optimized.p);
     HIPCHK(hipStreamSynchronize(h->stream));   // (the pinned buffer is reused by the next call)
     h->B = B;
     h->consumers_valid = false; h->nmax_known = nmax;
@@ -1280,8 +1276,7 @@ int teb_amd_download_tebs(teb_amd_handle_t* h, teb_amd_teb_batch_t* bt) {
     const size_t plane = (size_t)B * wc, count = (size_t)B + 4 * plane;
     if (h->pack_host && count <= kPackMaxDoubles) {   // small batch: one gather kernel, one copy
       const int grid = (int)std::min<size_t>(256, (plane + 255) / 256);
-      hipLaunchKernelGGL(pack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->n.p, h->x.p, h->y.p, h->th.p, h->dt.p);
-      HIPCHK(hipGetLastError());
+      LAUNCH(pack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->n.p, h->x.p, h->y.p, h->th.p, h->dt.p);
       HIPCHK(hipMemcpyAsync(h->pack_host, h->pack_dev.p, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
       const double* m = h->pack_host;
@@ -1405,8 +1400,7 @@ int teb_amd_get_iteration_log(teb_amd_handle_t* h, int32_t b, double* rows, int3
 int teb_amd_synchronize(teb_amd_handle_t* h) {
   int rc = check_handle(h);
   if (rc) return rc;
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int teb_amd_get_results(teb_amd_handle_t* h, teb_amd_results_t* out) {
@@ -1416,9 +1410,8 @@ int teb_amd_get_results(teb_amd_handle_t* h, teb_amd_results_t* out) {
   const int B = h->B;
   if (B == 0) return TEB_AMD_OK;   // an empty handle has no results to copy (a grid of 0 workgroups would be a launch error)
   if (h->pack_host && 6 * (size_t)B <= kPackMaxDoubles) {   // six result columns in one gather + one copy
-    hipLaunchKernelGGL(pack_results_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->pack_dev.p, B, h->status.p, h->iters.p, h->trials.p, h->chi2.p, h->cost.p,
-                       h->lambda.p);
-    HIPCHK(hipGetLastError());
+    LAUNCH(pack_results_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->pack_dev.p, B, h->status.p, h->iters.p, h->trials.p, h->chi2.p, h->cost.p,
+           h->lambda.p);
     HIPCHK(hipMemcpyAsync(h->pack_host, h->pack_dev.p, 6 * (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const double* m = h->pack_host;
@@ -1438,8 +1431,7 @@ int teb_amd_get_results(teb_amd_handle_t* h, teb_amd_results_t* out) {
   if (out->chi2) HIPCHK(hipMemcpyAsync(out->chi2, h->chi2.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (out->cost) HIPCHK(hipMemcpyAsync(out->cost, h->cost.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   if (out->lambda) HIPCHK(hipMemcpyAsync(out->lambda, h->lambda.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int teb_amd_select_best(teb_amd_handle_t* h, int32_t last_best, int32_t initial_plan, int32_t* best, double* best_cost) {
@@ -1450,9 +1442,8 @@ int teb_amd_select_best(teb_amd_handle_t* h, int32_t last_best, int32_t initial_
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs uploaded");
   if (last_best >= h->B) last_best = -1;
   if (initial_plan >= h->B) initial_plan = -1;
-  hipLaunchKernelGGL(select_best_kernel, dim3(1), dim3(kThreads), 0, h->stream, h->cost.p, h->B, last_best, initial_plan,
-                     h->cfg.selection_cost_hysteresis, h->cfg.selection_prefer_initial_plan, h->sel_cost.p, h->sel_idx.p);
-  HIPCHK(hipGetLastError());
+  LAUNCH(select_best_kernel, dim3(1), dim3(kThreads), 0, h->stream, h->cost.p, h->B, last_best, initial_plan, h->cfg.selection_cost_hysteresis,
+         h->cfg.selection_prefer_initial_plan, h->sel_cost.p, h->sel_idx.p);
   double rec[2];   // one 16-byte copy
   HIPCHK(hipMemcpyAsync(rec, h->sel_cost.p, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -1687,9 +1678,7 @@ int stage(teb_amd_handle* h, int n, const double* px, const double* py, const do
 int run_consumers(teb_amd_handle* h, int look_ahead, int prevent) {
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
   if (h->consumers_valid && h->consumers_la == look_ahead && h->consumers_prevent == prevent) return TEB_AMD_OK;
-  hipLaunchKernelGGL(consumers_kernel, dim3(h->B), dim3(kThreads), 0, h->stream, h->cfg, batch_of(h), look_ahead, prevent,
-                     h->out_cmd.p, h->out_prof.p, h->out_traj.p);
-  HIPCHK(hipGetLastError());
+  LAUNCH(consumers_kernel, dim3(h->B), dim3(kThreads), 0, h->stream, h->cfg, batch_of(h), look_ahead, prevent, h->out_cmd.p, h->out_prof.p, h->out_traj.p);
   h->consumers_valid = true; h->consumers_la = look_ahead; h->consumers_prevent = prevent;
   return TEB_AMD_OK;
 }
@@ -1697,8 +1686,7 @@ int run_consumers(teb_amd_handle* h, int look_ahead, int prevent) {
 int band_n(teb_amd_handle* h, int b, int* n) {
   if (b < 0 || b >= h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
   HIPCHK(hipMemcpyAsync(n, h->n.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 }  // namespace
@@ -1751,9 +1739,8 @@ int teb_amd_update_and_prune(teb_amd_handle_t* h, int32_t b, const double* new_s
   const double z[3] = {0, 0, 0};
   const double* s = new_start ? new_start : z;
   const double* g = new_goal ? new_goal : z;
-  hipLaunchKernelGGL(prune_kernel, dim3(b < 0 ? h->B : 1), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream,
-                     batch_of(h), b < 0 ? 0 : b, new_start ? 1 : 0, s[0], s[1], s[2], new_goal ? 1 : 0, g[0], g[1], g[2], min_samples);
-  HIPCHK(hipGetLastError());
+  LAUNCH(prune_kernel, dim3(b < 0 ? h->B : 1), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), b < 0 ? 0 : b, new_start ? 1 : 0,
+         s[0], s[1], s[2], new_goal ? 1 : 0, g[0], g[1], g[2], min_samples);
   h->consumers_valid = false; h->nmax_known = -1;
   h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
   return TEB_AMD_OK;
@@ -1823,8 +1810,7 @@ int teb_amd_get_velocity_profile(teb_amd_handle_t* h, int32_t b, double* out, in
   if (capacity_rows < n + 1) return fail(TEB_AMD_ERR_CAPACITY, "velocity profile needs n+1 rows");
   if ((rc = run_consumers(h, h->consumers_valid ? h->consumers_la : 1, h->consumers_valid ? h->consumers_prevent : 0))) return rc;
   HIPCHK(hipMemcpyAsync(out, h->out_prof.p + (size_t)b * (h->stride + 1) * 3, (size_t)(n + 1) * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int teb_amd_get_full_trajectory(teb_amd_handle_t* h, int32_t b, double* out, int32_t capacity_rows, int32_t* rows) {
@@ -1837,8 +1823,7 @@ int teb_amd_get_full_trajectory(teb_amd_handle_t* h, int32_t b, double* out, int
   if (capacity_rows < n) return fail(TEB_AMD_ERR_CAPACITY, "trajectory needs n rows");
   if ((rc = run_consumers(h, h->consumers_valid ? h->consumers_la : 1, h->consumers_valid ? h->consumers_prevent : 0))) return rc;
   HIPCHK(hipMemcpyAsync(out, h->out_traj.p + (size_t)b * h->stride * 7, (size_t)n * 7 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 // TebOptimalPlanner::hasDiverged (src/optimal_planner.cpp:1023-1039) reads optimizer_->batchStatistics().back().chi2. g2o sizes that
@@ -1896,10 +1881,11 @@ int teb_amd_set_costmap(teb_amd_handle_t* h, const uint8_t* cells, int32_t size_
   if (rc) return rc;
   if (!cells || size_x <= 0 || size_y <= 0 || !(resolution > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_costmap: bad grid");
   const size_t bytes = (size_t)size_x * size_y;
-  if (h->cm_cells.n < bytes) { h->cm_cells.free(); HIPCHK(h->cm_cells.alloc(bytes)); }
+  h->cm = GridDev{};   // (it holds the address of the cells, which may move now: a HIP error from here on leaves no costmap)
+  HIPCHK(ensure(h->cm_cells, bytes));
   HIPCHK(hipMemcpyAsync(h->cm_cells.p, cells, bytes, hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // the caller's buffer may go away
-  h->cm_sx = size_x; h->cm_sy = size_y; h->cm_res = resolution; h->cm_ox = origin_x; h->cm_oy = origin_y;
+  h->cm = GridDev{h->cm_cells.p, size_x, size_y, resolution, origin_x, origin_y};
   return TEB_AMD_OK;
 }
 
@@ -1908,23 +1894,22 @@ int teb_amd_is_trajectory_feasible(teb_amd_handle_t* h, int32_t b, int32_t nf, c
                                    int32_t* first_infeasible) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_is_trajectory_feasible: no costmap (teb_amd_set_costmap)");
+  if (h->cm.sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_is_trajectory_feasible: no costmap (teb_amd_set_costmap)");
   if (!feasible || nf < 1 || nf > kMaxFeasFootprint || !fx || !fy) return fail(TEB_AMD_ERR_INVALID_ARG, "bad footprint / output");
   if (!(inscribed_radius > 0) || !(min_res_angular > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "inscribed_radius and the angular resolution must be > 0");
   if (h->B <= 0 || b >= h->B || b < -1) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
   if (h->stride > 1024) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check supports bands up to 1024 poses");
   const int first = b < 0 ? 0 : b, count = b < 0 ? h->B : 1;
-  if (h->cm_fp.n < 2 * (size_t)kMaxFeasFootprint) { h->cm_fp.free(); HIPCHK(h->cm_fp.alloc(2 * (size_t)kMaxFeasFootprint)); }
-  if (h->cm_out.n < 2 * (size_t)h->max_tebs + 1) { h->cm_out.free(); HIPCHK(h->cm_out.alloc(2 * (size_t)h->max_tebs + 1)); }
+  HIPCHK(ensure(h->cm_fp, 2 * (size_t)kMaxFeasFootprint));
+  HIPCHK(ensure(h->cm_out, 2 * (size_t)h->max_tebs + 1));
   HIPCHK(hipMemcpyAsync(h->cm_fp.p, fx, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->cm_fp.p + kMaxFeasFootprint, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
   int* ovf = h->cm_out.p + 2 * (size_t)h->max_tebs;
   HIPCHK(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
-  GridDev g{h->cm_cells.p, h->cm_sx, h->cm_sy, h->cm_res, h->cm_ox, h->cm_oy};
-  hipLaunchKernelGGL(feasibility_kernel, dim3(count), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, first, g, nf,
-                     h->cm_fp.p, h->cm_fp.p + kMaxFeasFootprint, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance,
-                     1 << 22, h->cm_out.p, h->cm_out.p + h->max_tebs, ovf);
-  HIPCHK(hipGetLastError());
+  const GridDev& g = h->cm;
+  LAUNCH(feasibility_kernel, dim3(count), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, first, g, nf, h->cm_fp.p,
+         h->cm_fp.p + kMaxFeasFootprint, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, h->cm_out.p, h->cm_out.p + h->max_tebs,
+         ovf);
   std::vector<int> fe(count), fi(count);
   int o = 0;
   HIPCHK(hipMemcpyAsync(fe.data(), h->cm_out.p, count * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1934,172 +1919,6 @@ int teb_amd_is_trajectory_feasible(teb_amd_handle_t* h, int32_t b, int32_t nf, c
   if (o) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check: more than 2^22 interpolated samples requested (inscribed radius / angular resolution too small)");
   for (int k = 0; k < count; ++k) { feasible[k] = fe[k]; if (first_infeasible) first_infeasible[k] = fi[k]; }
   return TEB_AMD_OK;
-}
-
-// updateObstacleContainerWithCostmap (kernels in teb_costmap_obstacles.hpp) + the caller's obstacles as the handle's obstacle table
-int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
-                                       const teb_amd_obstacles_t* custom, int32_t* n_costmap, double* out_x, double* out_y,
-                                       int32_t capacity) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if ((rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles_from_costmap"))) return rc;
-  if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: no costmap (teb_amd_set_costmap)");
-  if (!robot_pose || capacity < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_obstacles_from_costmap: null pose / negative capacity");
-  if (custom && custom->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
-  HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
-  teb_amd_obstacles_t none{};
-  if (const char* bad = parse_obstacle_table(custom ? custom : &none, tc)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
-  if ((int)tc.pvx.size() > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
-  const int mc = (int)tc.type.size();
-
-  // count + scan into scratch: nothing of the live table is touched before the total is known to fit
-  const int ncols = h->cm_sx - 1, nrows = h->cm_sy - 1;
-  int n = 0, chunk = 4, nchunks = 0;
-  const GridDev g{h->cm_cells.p, h->cm_sx, h->cm_sy, h->cm_res, h->cm_ox, h->cm_oy};
-  const CmoFilter f{robot_pose[0], robot_pose[1], std::cos(robot_pose[2]), std::sin(robot_pose[2]), costmap_obstacles_behind_robot_dist};
-  if (ncols > 0 && nrows > 0) {
-    // rows per lane: the smallest of 4, 8, .. 64 that keeps the lanes (= values to scan) within 64 K - a 120 x 120 grid gets 4 rows per
-    // lane (3570 lanes, 56 waves), a 1000 x 1000 grid 16 (62937 lanes); from 4096 x 4096 on the chunk stays 64 and the lanes grow
-    while (chunk < 64 && (size_t)ncols * (size_t)((nrows + chunk - 1) / chunk) > 65536) chunk *= 2;
-    nchunks = (nrows + chunk - 1) / chunk;
-    const size_t lanes = (size_t)ncols * nchunks;
-    if (h->cmo_cnt.n < lanes + 1) { h->cmo_cnt.free(); HIPCHK(h->cmo_cnt.alloc(lanes + 1)); }
-    const dim3 grid((unsigned)((lanes + kCmoThreads - 1) / kCmoThreads));
-    hipLaunchKernelGGL(costmap_obstacles_count_kernel, grid, dim3(kCmoThreads), 0, h->stream, g, f, ncols, nrows, chunk, nchunks, h->cmo_cnt.p);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(costmap_obstacles_scan_kernel, dim3(1), dim3(kCmoScanThreads), 0, h->stream, h->cmo_cnt.p, (int)lanes);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(&n, h->cmo_cnt.p + lanes, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  if (n_costmap) *n_costmap = n;
-  if ((long long)n + mc > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "costmap cells + custom obstacles exceed max_obstacles");
-
-  // the cell rows on the device, the custom rows behind them from the host
-  if (n > 0) {
-    const size_t lanes = (size_t)ncols * nchunks;
-    hipLaunchKernelGGL(costmap_obstacles_write_kernel, dim3((unsigned)((lanes + kCmoThreads - 1) / kCmoThreads)), dim3(kCmoThreads), 0,
-                       h->stream, g, f, ncols, nrows, chunk, nchunks, h->cmo_cnt.p, h->scene.rows());
-    HIPCHK(hipGetLastError());
-  }
-  rc = upload_obstacle_rows(h, tc, (size_t)n);   // (ends in a stream synchronisation)
-  if (rc) return rc;
-
-  // host copy: the n cell centres (one copy back) ++ the custom rows, exactly what teb_amd_set_obstacles would hold
-  static_assert(TEB_AMD_OBST_POINT == 0, "zeroed rows are point rows");
-  HostObst t;
-  t.reset_rows(n);   // points, radius 0, velocity 0, not dynamic
-  if (n > 0) {
-    HIPCHK(hipMemcpyAsync(t.ax.data(), h->scene.ax.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(t.ay.data(), h->scene.ay.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  t.cx = t.ax; t.cy = t.ay;
-  if (out_x) std::copy(t.ax.begin(), t.ax.begin() + std::min(capacity, n), out_x);
-  if (out_y) std::copy(t.ay.begin(), t.ay.begin() + std::min(capacity, n), out_y);
-  t.append(tc);
-  return install_obstacles(h, std::move(t));
-}
-
-// A polygon list (row i has the vertices off[i] .. off[i + 1] - 1 of px / py) as an obstacle table: 1 vertex a point, 2 a line, more a
-// polygon; radius 0, velocity 0, not dynamic. Through teb_amd_set_obstacles' parse, so that centroids and bounding radii are the same
-// code. What both polygon routes of the costmap (single scene, scene set) make their converted rows with. Returns null or what is wrong.
-static const char* polygon_list_table(const int* off, const double* px, const double* py, int nr, HostObst& t) {
-  std::vector<int> type(nr), voff(nr + 1, 0);
-  std::vector<double> ax(nr), ay(nr), bx(nr, 0.0), by(nr, 0.0), pgx, pgy;
-  for (int i = 0; i < nr; ++i) {
-    const int k0 = off[i], k = off[i + 1] - k0;
-    type[i] = k == 1 ? TEB_AMD_OBST_POINT : k == 2 ? TEB_AMD_OBST_LINE : TEB_AMD_OBST_POLYGON;
-    ax[i] = k <= 2 ? px[k0] : 0.0; ay[i] = k <= 2 ? py[k0] : 0.0;   // a polygon is its vertices (ObstacleTable.add_polygon)
-    if (k == 2) { bx[i] = px[k0 + 1]; by[i] = py[k0 + 1]; }
-    if (k >= 3) { pgx.insert(pgx.end(), px + k0, px + k0 + k); pgy.insert(pgy.end(), py + k0, py + k0 + k); }
-    voff[i + 1] = (int)pgx.size();
-  }
-  teb_amd_obstacles_t ct{};
-  ct.count = nr; ct.type = type.data(); ct.ax = ax.data(); ct.ay = ay.data(); ct.bx = bx.data(); ct.by = by.data();
-  ct.vert_offset = voff.data(); ct.vert_x = pgx.data(); ct.vert_y = pgy.data();
-  return parse_obstacle_table(&ct, t);
-}
-
-// The converter slot of computeVelocityCommands (updateObstacleContainerWithCostmapConverter, src/teb_local_planner_ros.cpp:506-549)
-// fed by the device: the costmap's lethal cells as convex points / lines / polygons (kernels in teb_costmap_polygons.hpp) + the
-// caller's obstacles as the handle's obstacle table
-int teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
-                                                int32_t tile_cells, const teb_amd_obstacles_t* custom, int32_t* n_obstacles,
-                                                int32_t* n_points, int32_t* out_offset, double* out_x, double* out_y,
-                                                int32_t capacity_obstacles, int32_t capacity_points) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if ((rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles_from_costmap_polygons"))) return rc;
-  const char* fn = "teb_amd_set_obstacles_from_costmap_polygons: ";
-  if (h->cm_sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "no costmap (teb_amd_set_costmap)");
-  if (!robot_pose || capacity_obstacles < 0 || capacity_points < 0)
-    return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null pose / negative capacity");
-  if (tile_cells < 1 || tile_cells > kCmpMaxTile) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "tile_cells outside 1 .. 64");
-  if (custom && custom->count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
-  HostObst tc;   // the custom rows (teb_amd_set_obstacles' parse: same centroids, radii, vertex offsets from 0)
-  teb_amd_obstacles_t none{};
-  if (const char* bad = parse_obstacle_table(custom ? custom : &none, tc)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
-  const int mc = (int)tc.type.size();
-
-  // count + scan over blocks into scratch; the host reads the three totals back and decides whether the table fits
-  const int ncols = h->cm_sx - 1, nrows = h->cm_sy - 1, T = tile_cells;
-  int tot[3] = {0, 0, 0};   // rows, vertices, polygon vertices
-  const GridDev g{h->cm_cells.p, h->cm_sx, h->cm_sy, h->cm_res, h->cm_ox, h->cm_oy};
-  const CmoFilter f{robot_pose[0], robot_pose[1], std::cos(robot_pose[2]), std::sin(robot_pose[2]), costmap_obstacles_behind_robot_dist};
-  CmpGeom q{ncols, nrows, T, kCmpSlots / (T * T), 0, 0};
-  int nblk = 0;
-  if (ncols > 0 && nrows > 0) {
-    q.nty = (nrows + T - 1) / T;
-    q.nby = (q.nty + q.k - 1) / q.k;
-    const long long nb = (long long)((ncols + T - 1) / T) * q.nby;
-    if (nb > (1 << 30)) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "grid too large");
-    nblk = (int)nb;
-    const size_t need = 3 * ((size_t)nblk + 1);
-    if (h->cmp_cnt.n < need) { h->cmp_cnt.free(); HIPCHK(h->cmp_cnt.alloc(need)); }
-    hipLaunchKernelGGL(costmap_polygons_count_kernel, dim3((unsigned)nblk), dim3(kCmpThreads), 0, h->stream, g, f, q, nblk, h->cmp_cnt.p);
-    HIPCHK(hipGetLastError());
-    for (int a = 0; a < 3; ++a) {
-      int* c = h->cmp_cnt.p + (size_t)a * (nblk + 1);
-      hipLaunchKernelGGL(costmap_obstacles_scan_kernel, dim3(1), dim3(kCmoScanThreads), 0, h->stream, c, nblk);
-      HIPCHK(hipGetLastError());
-      HIPCHK(hipMemcpyAsync(&tot[a], c + nblk, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  const int nr = tot[0], nv = tot[1];
-  if (n_obstacles) *n_obstacles = nr;
-  if (n_points) *n_points = nv;
-  if ((long long)nr + mc > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "converted costmap rows + custom obstacles exceed max_obstacles");
-  if ((long long)tot[2] + (long long)tc.pvx.size() > h->max_verts)
-    return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
-
-  // the converted rows into scratch and back: first-vertex offsets and vertex coordinates (world), in table order
-  std::vector<int> off(nr + 1, nv);
-  std::vector<double> px(nv), py(nv);
-  if (nr > 0) {
-    if (h->cmp_off.n < (size_t)nr) { h->cmp_off.free(); HIPCHK(h->cmp_off.alloc(nr)); }
-    if (h->cmp_x.n < (size_t)nv) { h->cmp_x.free(); h->cmp_y.free(); HIPCHK(h->cmp_x.alloc(nv)); HIPCHK(h->cmp_y.alloc(nv)); }
-    const CmpOut o{h->cmp_off.p, h->cmp_x.p, h->cmp_y.p};
-    hipLaunchKernelGGL(costmap_polygons_write_kernel, dim3((unsigned)nblk), dim3(kCmpThreads), 0, h->stream, g, f, q, nblk, h->cmp_cnt.p, o);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(off.data(), h->cmp_off.p, nr * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(px.data(), h->cmp_x.p, nv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(py.data(), h->cmp_y.p, nv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-
-  HostObst t;
-  if (const char* bad = polygon_list_table(off.data(), px.data(), py.data(), nr, t)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
-  t.append(tc);
-  if (out_offset && out_x && out_y && nr <= capacity_obstacles && nv <= capacity_points) {
-    std::copy(off.begin(), off.end(), out_offset);
-    std::copy(px.begin(), px.end(), out_x);
-    std::copy(py.begin(), py.end(), out_y);
-  }
-  rc = upload_obstacle_rows(h, t, 0);
-  if (rc) return rc;
-  return install_obstacles(h, std::move(t));
 }
 
 namespace {
@@ -2114,23 +1933,17 @@ int launch_hsig(teb_amd_handle* h, const BatchDev& bt, int B, double prescaler, 
       const char* force = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE ? "wide" : h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_SMALL ? "small" : nullptr;   // teb_amd_options_t::hsig3d_kernel pins one of the two kernels (tests, tools/hsig_bench.py)
       const bool wide = force ? std::strcmp(force, "wide") == 0 : (long long)B * M >= 32768;
       if (wide)
-        hipLaunchKernelGGL(hsig3d_kernel, dim3((M + kThreads - 1) / kThreads, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                           h->stream, sc, bt, out);
+        LAUNCH(hsig3d_kernel, dim3((M + kThreads - 1) / kThreads, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, sc, bt, out);
       else
-        hipLaunchKernelGGL(hsig3d_small_kernel, dim3((M + kHsTile - 1) / kHsTile, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                           h->stream, sc, bt, out);
-      HIPCHK(hipGetLastError());
+        LAUNCH(hsig3d_small_kernel, dim3((M + kHsTile - 1) / kHsTile, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, sc, bt, out);
     }
   } else {
     if (M > 0 && !h->hs_prod_valid) {   // the band-independent factor of A_l: once per obstacle table (O(M^2))
-      hipLaunchKernelGGL(hsig2d_prod_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, sc, h->hs_pre.p,
-                         h->hs_pim.p, h->hs_pex.p);
-      HIPCHK(hipGetLastError());
+      LAUNCH(hsig2d_prod_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, sc, h->hs_pre.p, h->hs_pim.p, h->hs_pex.p);
       h->hs_prod_valid = true;
     }
-    hipLaunchKernelGGL(hsig2d_kernel, dim3(B), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, sc, bt, prescaler,
-                       h->hs_pre.p, h->hs_pim.p, h->hs_pex.p, out);
-    HIPCHK(hipGetLastError());
+    LAUNCH(hsig2d_kernel, dim3(B), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, sc, bt, prescaler, h->hs_pre.p, h->hs_pim.p, h->hs_pex.p,
+           out);
   }
   return TEB_AMD_OK;
 }
@@ -2146,23 +1959,20 @@ int launch_hsig_fleet(teb_amd_handle* h, const FleetHsigDev& fl, const BatchDev&
       // the rule of the single-scene launch on the total number of values; teb_amd_options_t::hsig3d_kernel pins one of the two
       const bool wide = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE || (h->opt.hsig3d_kernel != TEB_AMD_HSIG3D_SMALL && (long long)total >= 32768);
       if (wide)
-        hipLaunchKernelGGL(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                           h->stream, fl, bt, out);
+        LAUNCH(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, fl,
+               bt, out);
       else
-        hipLaunchKernelGGL(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double),
-                           h->stream, fl, bt, out);
-      HIPCHK(hipGetLastError());
+        LAUNCH(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, fl,
+               bt, out);
     }
   } else {
     if (widest > 0 && !F.hs_prod_valid) {   // the band-independent factor of A_l: once per scene set, every scene over its own rows
-      hipLaunchKernelGGL(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, F.n_scenes), dim3(kThreads), 0, h->stream, F.scenes.p,
-                         F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p);
-      HIPCHK(hipGetLastError());
+      LAUNCH(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, F.n_scenes), dim3(kThreads), 0, h->stream, F.scenes.p, F.store.cx.p, F.hs_pre.p,
+             F.hs_pim.p, F.hs_pex.p);
       F.hs_prod_valid = true;
     }
-    hipLaunchKernelGGL(hsig2d_fleet_kernel, dim3(count), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, bt, prescaler,
-                       F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p, out);
-    HIPCHK(hipGetLastError());
+    LAUNCH(hsig2d_fleet_kernel, dim3(count), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, bt, prescaler, F.store.cx.p, F.hs_pre.p,
+           F.hs_pim.p, F.hs_pex.p, out);
   }
   return TEB_AMD_OK;
 }
@@ -2331,232 +2141,233 @@ int teb_amd_set_costmaps(teb_amd_handle_t* h, int32_t n, const uint8_t* cells, c
   return TEB_AMD_OK;
 }
 
+// ---- a costmap becomes an obstacle table: updateObstacleContainerWithCostmap (src/teb_local_planner_ros.cpp:478-504, kernels in
+// teb_costmap_obstacles.hpp) and the converter slot updateObstacleContainerWithCostmapConverter (:506-549, kernels in
+// teb_costmap_polygons.hpp), for the single scene and for a scene set. ONE procedure (convert_costmaps) over a row kind and a route;
+// its host rules are teb_costmap_host.hpp --------------------------------------------------------------------------------------------
+namespace {
+// The write pass of the polygon route and its read-back, the same on both routes but for the launch: the converted rows of the set at
+// their prefix offsets of one scratch - first-vertex offsets (from the scene's first vertex on) and vertex coordinates (world), in
+// table order - read back once.
+extern "C++" template <class Launch>
+int write_polygon_rows(teb_amd_handle* h, PolygonRows& K, Launch&& launch) {
+  auto& S = h->cmx;
+  const size_t rows = (size_t)K.rows, verts = (size_t)K.verts;
+  if (rows == 0) return TEB_AMD_OK;
+  HIPCHK(ensure(S.poff, rows));
+  HIPCHK(ensure(S.pvx, verts));
+  HIPCHK(ensure(S.pvy, verts));
+  if (int rc = launch(CmpOut{S.poff.p, S.pvx.p, S.pvy.p})) return rc;
+  HIPCHK(hipMemcpyAsync(K.off.data(), S.poff.p, rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(K.px.data(), S.pvx.p, verts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(K.py.data(), S.pvy.p, verts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  return synced(h);
+}
+
+// A route: which kernels carry the passes of a row kind (PointRows, PolygonRows: teb_costmap_host.hpp), where the write pass puts its
+// rows, how the tables are installed. The single scene: the by-value kernels on the one record of the handle's costmap; its table is
+// the handle's; no via-points.
+struct OneSceneRoute {
+  const int32_t* via_count = nullptr;
+  const double *via_x = nullptr, *via_y = nullptr;
+  bool rows_live = false;   // the write pass filled the rows of the live table itself
+
+  int count(teb_amd_handle* h, PointRows& K) {
+    auto& S = h->cmx;
+    const CmoSceneRec& q = K.rec[0];
+    const size_t lanes = K.max_lanes;
+    if (lanes == 0) return TEB_AMD_OK;
+    HIPCHK(ensure(S.cnt, lanes + 1));
+    LAUNCH(costmap_obstacles_count_kernel, dim3((unsigned)((lanes + kCmoThreads - 1) / kCmoThreads)), dim3(kCmoThreads), 0, h->stream, q.g, q.f, q.ncols,
+           q.nrows, q.chunk, q.nchunks, S.cnt.p);
+    LAUNCH(costmap_obstacles_scan_kernel, dim3(1), dim3(kCmoScanThreads), 0, h->stream, S.cnt.p, (int)lanes);
+    HIPCHK(hipMemcpyAsync(&K.tot[0], S.cnt.p + lanes, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return synced(h);
+  }
+  // the cell rows straight into the live table (they are known to fit), the custom rows behind them from the host; only the centres
+  // come back, for the host copy and the out arrays
+  int write(teb_amd_handle* h, PointRows& K, const SceneInputs& in) {
+    const CmoSceneRec& q = K.rec[0];
+    const size_t n = K.rows;
+    if (n > 0)
+      LAUNCH(costmap_obstacles_write_kernel, dim3((unsigned)((K.max_lanes + kCmoThreads - 1) / kCmoThreads)), dim3(kCmoThreads), 0, h->stream, q.g, q.f,
+             q.ncols, q.nrows, q.chunk, q.nchunks, h->cmx.cnt.p, h->scene.rows());
+    if (int rc = upload_obstacle_rows(h, in.tabs[0], n)) return rc;   // (ends in a stream synchronisation)
+    rows_live = true;
+    if (n == 0) return TEB_AMD_OK;
+    HIPCHK(hipMemcpyAsync(K.px.data(), h->scene.ax.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(K.py.data(), h->scene.ay.p, n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return synced(h);
+  }
+  // count + a scan over blocks per total; the host reads the three totals back
+  int count(teb_amd_handle* h, PolygonRows& K) {
+    auto& S = h->cmx;
+    const CmpSceneRec& r = K.rec[0];
+    if (r.nblk == 0) return TEB_AMD_OK;
+    HIPCHK(ensure(S.pcnt, 3 * ((size_t)r.nblk + 1)));
+    LAUNCH(costmap_polygons_count_kernel, dim3((unsigned)r.nblk), dim3(kCmpThreads), 0, h->stream, r.g, r.f, r.q, r.nblk, S.pcnt.p);
+    for (int a = 0; a < 3; ++a) {
+      int* c = S.pcnt.p + (size_t)a * (r.nblk + 1);
+      LAUNCH(costmap_obstacles_scan_kernel, dim3(1), dim3(kCmoScanThreads), 0, h->stream, c, r.nblk);
+      HIPCHK(hipMemcpyAsync(&K.tot[a], c + r.nblk, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    }
+    return synced(h);
+  }
+  int write(teb_amd_handle* h, PolygonRows& K, const SceneInputs&) {
+    const CmpSceneRec& r = K.rec[0];
+    return write_polygon_rows(h, K, [&](const CmpOut& o) -> int {
+      LAUNCH(costmap_polygons_write_kernel, dim3((unsigned)r.nblk), dim3(kCmpThreads), 0, h->stream, r.g, r.f, r.q, r.nblk, h->cmx.pcnt.p, o);
+      return TEB_AMD_OK;
+    });
+  }
+  int install(teb_amd_handle* h, std::vector<HostObst>&& tabs, SceneInputs&&) {
+    if (!rows_live)
+      if (int rc = upload_obstacle_rows(h, tabs[0], 0)) return rc;
+    return install_obstacles(h, std::move(tabs[0]));
+  }
+};
+
+// The scenes of a set over the grids of the costmap set: the records of the scenes on the device, every pass ONE launch of the
+// record-reading kernels, one copy of the totals, one read-back; the tables become the scene set of the handle. The records travel
+// before the count pass and again before the write pass: they carry the prefixes then.
+struct SceneSetRoute {
+  const int32_t* via_count;
+  const double *via_x, *via_y;
+
+  int count(teb_amd_handle* h, PointRows& K) {
+    auto& S = h->cmx;
+    const unsigned n = (unsigned)K.rec.size(), blocks = (unsigned)((K.max_lanes + kCmoThreads - 1) / kCmoThreads);
+    HIPCHK(ensure(S.cnt, K.counters));
+    HIPCHK(ensure(S.rec, (size_t)h->max_tebs));
+    HIPCHK(ensure(S.tot, (size_t)h->max_tebs));
+    HIPCHK(hipMemcpyAsync(S.rec.p, K.rec.data(), n * sizeof(CmoSceneRec), hipMemcpyHostToDevice, h->stream));
+    if (blocks > 0) LAUNCH(costmap_obstacles_count_fleet_kernel, dim3(blocks, n), dim3(kCmoThreads), 0, h->stream, S.rec.p, S.cnt.p);
+    LAUNCH(costmap_obstacles_scan_fleet_kernel, dim3(n), dim3(kCmoScanThreads), 0, h->stream, S.rec.p, S.cnt.p, S.tot.p);
+    HIPCHK(hipMemcpyAsync(K.tot.data(), S.tot.p, n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return synced(h);
+  }
+  // every scene's points at its prefix offset of one scratch buffer
+  int write(teb_amd_handle* h, PointRows& K, const SceneInputs&) {
+    auto& S = h->cmx;
+    const unsigned n = (unsigned)K.rec.size(), blocks = (unsigned)((K.max_lanes + kCmoThreads - 1) / kCmoThreads);
+    if (K.rows == 0) return TEB_AMD_OK;
+    HIPCHK(ensure(S.px, (size_t)std::max(h->max_obst, 1)));
+    HIPCHK(ensure(S.py, (size_t)std::max(h->max_obst, 1)));
+    HIPCHK(hipMemcpyAsync(S.rec.p, K.rec.data(), n * sizeof(CmoSceneRec), hipMemcpyHostToDevice, h->stream));
+    LAUNCH(costmap_obstacles_write_fleet_kernel, dim3(blocks, n), dim3(kCmoThreads), 0, h->stream, S.rec.p, S.cnt.p, S.px.p, S.py.p);
+    HIPCHK(hipMemcpyAsync(K.px.data(), S.px.p, K.rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(K.py.data(), S.py.p, K.rows * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    return synced(h);
+  }
+  int count(teb_amd_handle* h, PolygonRows& K) {
+    auto& S = h->cmx;
+    const unsigned n = (unsigned)K.rec.size();
+    HIPCHK(ensure(S.pcnt, 3 * (size_t)K.ncnt));
+    HIPCHK(ensure(S.prec, (size_t)h->max_tebs));
+    HIPCHK(ensure(S.blk, (size_t)h->max_tebs + 1));
+    HIPCHK(ensure(S.ptot, 3 * (size_t)h->max_tebs));
+    HIPCHK(hipMemcpyAsync(S.prec.p, K.rec.data(), n * sizeof(CmpSceneRec), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(S.blk.p, K.blk0.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (K.blocks > 0)
+      LAUNCH(costmap_polygons_count_fleet_kernel, dim3((unsigned)K.blocks), dim3(kCmpThreads), 0, h->stream, S.prec.p, S.blk.p, (int)n, (int)K.ncnt, S.pcnt.p);
+    LAUNCH(costmap_polygons_scan_fleet_kernel, dim3(3 * n), dim3(kCmoScanThreads), 0, h->stream, S.prec.p, (int)n, (int)K.ncnt, S.pcnt.p, S.ptot.p);
+    HIPCHK(hipMemcpyAsync(K.tot.data(), S.ptot.p, K.tot.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return synced(h);
+  }
+  int write(teb_amd_handle* h, PolygonRows& K, const SceneInputs&) {
+    auto& S = h->cmx;
+    const int n = (int)K.rec.size();
+    return write_polygon_rows(h, K, [&](const CmpOut& o) -> int {
+      HIPCHK(hipMemcpyAsync(S.prec.p, K.rec.data(), (size_t)n * sizeof(CmpSceneRec), hipMemcpyHostToDevice, h->stream));
+      LAUNCH(costmap_polygons_write_fleet_kernel, dim3((unsigned)K.blocks), dim3(kCmpThreads), 0, h->stream, S.prec.p, S.blk.p, n, (int)K.ncnt, S.pcnt.p, o);
+      return TEB_AMD_OK;
+    });
+  }
+  int install(teb_amd_handle* h, std::vector<HostObst>&& tabs, SceneInputs&& in) {
+    return install_scene_set(h, std::move(tabs), std::move(in.vc), via_x, via_y, in.vias);
+  }
+};
+
+// The conversion, after the entry point's own argument checks (step 1 of 7). grids / poses / tiles: one per scene; custom: the caller's
+// tables (null: none), which with the route's via-points may hold at most `early` - what a call checks only together with its
+// converted rows is SIZE_MAX there. Nothing live is touched before the converted rows are known to fit.
+extern "C++" template <class Rows, class Route>
+int convert_costmaps(teb_amd_handle* h, const char* fn, Route route, const GridDev* grids, int n, const double* poses, double behind_robot_dist,
+                     const int32_t* tiles, const teb_amd_obstacles_t* custom, const SceneCaps& early, const typename Rows::Out& out) {
+  SceneInputs in;                                                                             // 2. the caller's tables and via-points
+  if (Refusal r = parse_scene_inputs(n, custom, "bad custom obstacle table", route.via_count, route.via_x, route.via_y, early, in)) return fail(r.code, r.text);
+  Rows K;                                                                                     // 3. the launch geometry per grid
+  if (Refusal r = K.layout(grids, n, poses, behind_robot_dist, tiles)) return fail(r.code, std::string(fn) + r.text);
+  if (int rc = route.count(h, K)) return rc;                                                  // 4. count + scan into scratch, totals back
+  if (Refusal r = K.place(in, handle_caps(h), out)) return fail(r.code, r.text);              // 5. counts reported; refused if they do not fit
+  if (int rc = route.write(h, K, in)) return rc;                                              // 6. the write pass and its read-back
+  std::vector<HostObst> tabs;                                                                 // 7. host tables, out arrays, install
+  if (const char* bad = K.finish(in, out, tabs)) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
+  return route.install(h, std::move(tabs), std::move(in));
+}
+}  // namespace
+
+int teb_amd_set_obstacles_from_costmap(teb_amd_handle_t* h, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
+                                       const teb_amd_obstacles_t* custom, int32_t* n_costmap, double* out_x, double* out_y,
+                                       int32_t capacity) {
+  if (int rc = check_handle(h)) return rc;
+  if (int rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles_from_costmap")) return rc;
+  const char* fn = "teb_amd_set_obstacles_from_costmap: ";
+  if (h->cm.sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "no costmap (teb_amd_set_costmap)");
+  if (!robot_pose || capacity < 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null pose / negative capacity");
+  // Early, before any launch: only the custom polygon vertices against max_obstacle_vertices - the point route adds none. The custom
+  // rows are checked after the count pass, together with the cells (one refusal, n_costmap written before it).
+  return convert_costmaps<PointRows>(h, fn, OneSceneRoute{}, &h->cm, 1, robot_pose, costmap_obstacles_behind_robot_dist, nullptr, custom,
+                                     SceneCaps{SIZE_MAX, (size_t)h->max_verts, SIZE_MAX}, PointRows::Out{n_costmap, out_x, out_y, capacity});
+}
+
+int teb_amd_set_obstacles_from_costmap_polygons(teb_amd_handle_t* h, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
+                                                int32_t tile_cells, const teb_amd_obstacles_t* custom, int32_t* n_obstacles,
+                                                int32_t* n_points, int32_t* out_offset, double* out_x, double* out_y,
+                                                int32_t capacity_obstacles, int32_t capacity_points) {
+  if (int rc = check_handle(h)) return rc;
+  if (int rc = refuse_in_fleet_mode(h, "teb_amd_set_obstacles_from_costmap_polygons")) return rc;
+  const char* fn = "teb_amd_set_obstacles_from_costmap_polygons: ";
+  if (h->cm.sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "no costmap (teb_amd_set_costmap)");
+  if (!robot_pose || capacity_obstacles < 0 || capacity_points < 0)
+    return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null pose / negative capacity");
+  if (tile_cells < 1 || tile_cells > kCmpMaxTile) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "tile_cells outside 1 .. 64");
+  // Early, before any launch: nothing. Custom rows and custom polygon vertices are both checked after the count pass, each together
+  // with the converted ones (n_obstacles / n_points written before either refusal).
+  return convert_costmaps<PolygonRows>(h, fn, OneSceneRoute{}, &h->cm, 1, robot_pose, costmap_obstacles_behind_robot_dist, &tile_cells, custom, SceneCaps{},
+                                       PolygonRows::Out{n_obstacles, n_points, out_offset, out_x, out_y, capacity_obstacles, capacity_points});
+}
+
 int teb_amd_set_scenes_from_costmaps(teb_amd_handle_t* h, int32_t n_scenes, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
                                      const teb_amd_obstacles_t* custom, const int32_t* via_count, const double* via_x, const double* via_y,
                                      int32_t* n_costmap, double* out_x, double* out_y, int32_t capacity) {
-  int rc = check_handle(h);
-  if (rc) return rc;
+  if (int rc = check_handle(h)) return rc;
+  const char* fn = "teb_amd_set_scenes_from_costmaps: ";
   if (n_scenes < 1 || !robot_pose || capacity < 0)
-    return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scenes_from_costmaps: needs at least one scene, the robot poses and a capacity >= 0");
-  if (h->cms.n != n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scenes_from_costmaps: needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
-  // the custom rows of every scene (teb_amd_set_scenes' parse) and the via-points: checked before anything runs
-  std::vector<HostObst> tc(n_scenes);
-  std::vector<int> vc(n_scenes, 0);
-  size_t custom_rows = 0, verts = 0, vias = 0;
-  teb_amd_obstacles_t none{};
-  for (int s = 0; s < n_scenes; ++s) {
-    if (custom && custom[s].count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
-    if (const char* bad = parse_obstacle_table(custom ? &custom[s] : &none, tc[s])) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
-    custom_rows += tc[s].rows(); verts += tc[s].verts();
-    if (via_count) {
-      if (via_count[s] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
-      vc[s] = via_count[s]; vias += (size_t)via_count[s];
-    }
-  }
-  if (vias > 0 && (!via_x || !via_y)) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
-  if (custom_rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
-  if (verts > (size_t)h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
-  if (vias > (size_t)h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
-
-  // one record per scene: its grid, its filter (cos / sin from the host's libm, as for the single scene) and the single-scene lane rule
-  std::vector<CmoSceneRec> rec(n_scenes);
-  size_t counters = 0, max_lanes = 0;
-  for (int s = 0; s < n_scenes; ++s) {
-    CmoSceneRec& q = rec[s];
-    const double* pose = robot_pose + 3 * (size_t)s;
-    q.g = h->cms.grids_host[s];
-    q.f = CmoFilter{pose[0], pose[1], std::cos(pose[2]), std::sin(pose[2]), costmap_obstacles_behind_robot_dist};
-    q.ncols = q.g.sx - 1; q.nrows = q.g.sy - 1; q.chunk = 4; q.nchunks = 0;
-    if (q.ncols > 0 && q.nrows > 0) {   // rows per lane: the rule of teb_amd_set_obstacles_from_costmap
-      while (q.chunk < 64 && (size_t)q.ncols * (size_t)((q.nrows + q.chunk - 1) / q.chunk) > 65536) q.chunk *= 2;
-      q.nchunks = (q.nrows + q.chunk - 1) / q.chunk;
-    } else { q.ncols = 0; q.nrows = 0; }
-    const size_t lanes = (size_t)q.ncols * q.nchunks;
-    q.cnt_off = (int)counters; q.out_off = 0;
-    counters += lanes + 1;
-    max_lanes = std::max(max_lanes, lanes);
-    if (counters > (size_t)std::numeric_limits<int>::max()) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_set_scenes_from_costmaps: the grids of the set are too large for one call");
-  }
-  if (h->cmo_cnt.n < counters) { h->cmo_cnt.free(); HIPCHK(h->cmo_cnt.alloc(counters)); }
-  if (!h->cms_rec.p) { HIPCHK(h->cms_rec.alloc((size_t)h->max_tebs)); HIPCHK(h->cms_tot.alloc((size_t)h->max_tebs)); }
-
-  // count + scan into scratch: nothing of the live set is touched before the totals are known to fit
-  std::vector<int> tot(n_scenes, 0);
-  const unsigned blocks = (unsigned)((max_lanes + kCmoThreads - 1) / kCmoThreads);
-  HIPCHK(hipMemcpyAsync(h->cms_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmoSceneRec), hipMemcpyHostToDevice, h->stream));
-  if (blocks > 0) {
-    hipLaunchKernelGGL(costmap_obstacles_count_fleet_kernel, dim3(blocks, (unsigned)n_scenes), dim3(kCmoThreads), 0, h->stream, h->cms_rec.p, h->cmo_cnt.p);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(costmap_obstacles_scan_fleet_kernel, dim3((unsigned)n_scenes), dim3(kCmoScanThreads), 0, h->stream, h->cms_rec.p, h->cmo_cnt.p, h->cms_tot.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(tot.data(), h->cms_tot.p, (size_t)n_scenes * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  size_t cells_kept = 0;
-  for (int s = 0; s < n_scenes; ++s) {
-    if (n_costmap) n_costmap[s] = tot[s];
-    rec[s].out_off = (int)std::min<size_t>(cells_kept, (size_t)std::numeric_limits<int>::max());
-    cells_kept += (size_t)tot[s];
-  }
-  if (cells_kept + custom_rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "costmap cells + custom obstacles exceed max_obstacles");
-
-  // every scene's points at its prefix offset of one scratch buffer, read back once
-  std::vector<double> px(cells_kept), py(cells_kept);
-  if (cells_kept > 0) {
-    if (h->cms_px.n < cells_kept) { free_all(h->cms_px, h->cms_py); HIPCHK(h->cms_px.alloc((size_t)std::max(h->max_obst, 1))); HIPCHK(h->cms_py.alloc((size_t)std::max(h->max_obst, 1))); }
-    HIPCHK(hipMemcpyAsync(h->cms_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmoSceneRec), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(costmap_obstacles_write_fleet_kernel, dim3(blocks, (unsigned)n_scenes), dim3(kCmoThreads), 0, h->stream, h->cms_rec.p, h->cmo_cnt.p,
-                       h->cms_px.p, h->cms_py.p);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(px.data(), h->cms_px.p, cells_kept * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(py.data(), h->cms_py.p, cells_kept * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-  const size_t give = std::min((size_t)capacity, cells_kept);
-  if (out_x) std::copy(px.begin(), px.begin() + give, out_x);
-  if (out_y) std::copy(py.begin(), py.begin() + give, out_y);
-
-  // host tables: the cell centres of scene s ++ its custom rows, exactly what teb_amd_set_scenes would parse
-  static_assert(TEB_AMD_OBST_POINT == 0, "zeroed rows are point rows");
-  std::vector<HostObst> tabs(n_scenes);
-  for (int s = 0; s < n_scenes; ++s) {
-    HostObst& t = tabs[s];
-    t.reset_rows((size_t)tot[s]);   // points, radius 0, velocity 0, not dynamic
-    std::copy(px.begin() + rec[s].out_off, px.begin() + rec[s].out_off + tot[s], t.ax.begin());
-    std::copy(py.begin() + rec[s].out_off, py.begin() + rec[s].out_off + tot[s], t.ay.begin());
-    t.cx = t.ax; t.cy = t.ay;
-    t.append(tc[s]);
-  }
-  return install_scene_set(h, std::move(tabs), std::move(vc), via_x, via_y, vias);
+    return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "needs at least one scene, the robot poses and a capacity >= 0");
+  if (h->cms.n != n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
+  // Early, as teb_amd_set_scenes: custom rows, custom polygon vertices and via-points each against the handle's capacity; after the
+  // count pass the rows again, together with the cells.
+  return convert_costmaps<PointRows>(h, fn, SceneSetRoute{via_count, via_x, via_y}, h->cms.grids_host.data(), n_scenes, robot_pose,
+                                     costmap_obstacles_behind_robot_dist, nullptr, custom, handle_caps(h), PointRows::Out{n_costmap, out_x, out_y, capacity});
 }
 
-// teb_amd_set_scenes_from_costmaps on the polygon route: every scene's grid through the kernels of teb_costmap_polygons.hpp with the
-// scene's own tile size, three launches for the whole set
+// teb_amd_set_scenes_from_costmaps on the polygon route: every scene's grid at the scene's own tile size
 int teb_amd_set_scenes_from_costmap_polygons(teb_amd_handle_t* h, int32_t n_scenes, const double* robot_pose, double costmap_obstacles_behind_robot_dist,
                                              const int32_t* tile_cells, const teb_amd_obstacles_t* custom, const int32_t* via_count, const double* via_x,
                                              const double* via_y, int32_t* n_obstacles, int32_t* n_points, int32_t* out_offset, double* out_x,
                                              double* out_y, int32_t capacity_obstacles, int32_t capacity_points) {
-  int rc = check_handle(h);
-  if (rc) return rc;
+  if (int rc = check_handle(h)) return rc;
   const char* fn = "teb_amd_set_scenes_from_costmap_polygons: ";
   if (n_scenes < 1 || !robot_pose || !tile_cells || capacity_obstacles < 0 || capacity_points < 0)
     return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "needs at least one scene, the robot poses, the tile sizes and capacities >= 0");
   if (h->cms.n != n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
   for (int s = 0; s < n_scenes; ++s)
     if (tile_cells[s] < 1 || tile_cells[s] > kCmpMaxTile) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "tile_cells outside 1 .. 64");
-  // the custom rows of every scene (teb_amd_set_scenes' parse) and the via-points: checked before anything runs
-  std::vector<HostObst> tc(n_scenes);
-  std::vector<int> vc(n_scenes, 0);
-  size_t custom_rows = 0, custom_verts = 0, vias = 0;
-  teb_amd_obstacles_t none{};
-  for (int s = 0; s < n_scenes; ++s) {
-    if (custom && custom[s].count < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad custom obstacle table");
-    if (const char* bad = parse_obstacle_table(custom ? &custom[s] : &none, tc[s])) return fail(TEB_AMD_ERR_INVALID_ARG, bad);
-    custom_rows += tc[s].rows(); custom_verts += tc[s].verts();
-    if (via_count) {
-      if (via_count[s] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
-      vc[s] = via_count[s]; vias += (size_t)via_count[s];
-    }
-  }
-  if (vias > 0 && (!via_x || !via_y)) return fail(TEB_AMD_ERR_INVALID_ARG, "bad via-point arrays");
-  if (custom_rows > (size_t)h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "more obstacles than max_obstacles");
-  if (custom_verts > (size_t)h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
-  if (vias > (size_t)h->max_via) return fail(TEB_AMD_ERR_CAPACITY, "more via-points than max_via_points");
-
-  // one record per scene: its grid, its filter (cos / sin from the host's libm, as for the single scene), the single-scene block
-  // geometry at its own tile size, and its place in the flat block list and in the count arrays
-  std::vector<CmpSceneRec> rec(n_scenes);
-  std::vector<int> blk0(n_scenes + 1, 0);
-  long long blocks = 0, ncnt = 0;
-  const long long int_max = std::numeric_limits<int>::max();
-  for (int s = 0; s < n_scenes; ++s) {
-    CmpSceneRec& r = rec[s];
-    const double* pose = robot_pose + 3 * (size_t)s;
-    const int T = tile_cells[s];
-    r.g = h->cms.grids_host[s];
-    r.f = CmoFilter{pose[0], pose[1], std::cos(pose[2]), std::sin(pose[2]), costmap_obstacles_behind_robot_dist};
-    r.q = CmpGeom{r.g.sx - 1, r.g.sy - 1, T, kCmpSlots / (T * T), 0, 0};
-    long long nb = 0;
-    if (r.q.ncols > 0 && r.q.nrows > 0) {
-      r.q.nty = (r.q.nrows + T - 1) / T;
-      r.q.nby = (r.q.nty + r.q.k - 1) / r.q.k;
-      nb = (long long)((r.q.ncols + T - 1) / T) * r.q.nby;
-      if (nb > (1 << 30)) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "grid too large");
-    }
-    r.blk0 = (int)blocks; r.nblk = (int)nb; r.cnt0 = (int)ncnt; r.row0 = 0; r.vtx0 = 0;
-    blk0[s] = (int)blocks;
-    blocks += nb; ncnt += nb + 1;
-    if (blocks > int_max || 3 * ncnt > int_max) return fail(TEB_AMD_ERR_CAPACITY, std::string(fn) + "the grids of the set are too large for one call");
-  }
-  blk0[n_scenes] = (int)blocks;
-  if (h->cmp_cnt.n < 3 * (size_t)ncnt) { h->cmp_cnt.free(); HIPCHK(h->cmp_cnt.alloc(3 * (size_t)ncnt)); }
-  if (!h->cmp_rec.p) {
-    HIPCHK(h->cmp_rec.alloc((size_t)h->max_tebs)); HIPCHK(h->cmp_blk.alloc((size_t)h->max_tebs + 1)); HIPCHK(h->cmp_tot.alloc(3 * (size_t)h->max_tebs));
-  }
-
-  // count + scan into scratch: nothing of the live set is touched before the totals are known to fit
-  std::vector<int> tot(3 * (size_t)n_scenes, 0);   // rows, vertices, polygon vertices: [array][scene]
-  HIPCHK(hipMemcpyAsync(h->cmp_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmpSceneRec), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->cmp_blk.p, blk0.data(), ((size_t)n_scenes + 1) * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if (blocks > 0) {
-    hipLaunchKernelGGL(costmap_polygons_count_fleet_kernel, dim3((unsigned)blocks), dim3(kCmpThreads), 0, h->stream, h->cmp_rec.p, h->cmp_blk.p, n_scenes,
-                       (int)ncnt, h->cmp_cnt.p);
-    HIPCHK(hipGetLastError());
-  }
-  hipLaunchKernelGGL(costmap_polygons_scan_fleet_kernel, dim3(3 * (unsigned)n_scenes), dim3(kCmoScanThreads), 0, h->stream, h->cmp_rec.p, n_scenes, (int)ncnt,
-                     h->cmp_cnt.p, h->cmp_tot.p);
-  HIPCHK(hipGetLastError());
-  HIPCHK(hipMemcpyAsync(tot.data(), h->cmp_tot.p, tot.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  const int* nrs = tot.data();
-  const int* nvs = tot.data() + n_scenes;
-  long long rows = 0, verts = 0, pverts = 0;
-  for (int s = 0; s < n_scenes; ++s) {
-    if (n_obstacles) n_obstacles[s] = nrs[s];
-    if (n_points) n_points[s] = nvs[s];
-    rec[s].row0 = (int)std::min(rows, int_max); rec[s].vtx0 = (int)std::min(verts, int_max);
-    rows += nrs[s]; verts += nvs[s]; pverts += tot[2 * (size_t)n_scenes + s];
-  }
-  if (rows + (long long)custom_rows > h->max_obst) return fail(TEB_AMD_ERR_CAPACITY, "converted costmap rows + custom obstacles exceed max_obstacles");
-  if (pverts + (long long)custom_verts > h->max_verts) return fail(TEB_AMD_ERR_CAPACITY, "more polygon vertices than max_obstacle_vertices");
-
-  // every scene's converted rows at its prefix offsets of one scratch: first-vertex offsets (from the scene's first vertex on) and
-  // vertex coordinates (world), in table order; read back once
-  std::vector<int> off((size_t)rows + 1, 0);
-  std::vector<double> px((size_t)verts), py((size_t)verts);
-  if (rows > 0) {   // (rows <= max_obstacles; a point or line row has at most 2 vertices: verts <= 2 max_obstacles + max_obstacle_vertices)
-    if (h->cmp_off.n < (size_t)rows) { h->cmp_off.free(); HIPCHK(h->cmp_off.alloc((size_t)rows)); }
-    if (h->cmp_x.n < (size_t)verts) { h->cmp_x.free(); h->cmp_y.free(); HIPCHK(h->cmp_x.alloc((size_t)verts)); HIPCHK(h->cmp_y.alloc((size_t)verts)); }
-    HIPCHK(hipMemcpyAsync(h->cmp_rec.p, rec.data(), (size_t)n_scenes * sizeof(CmpSceneRec), hipMemcpyHostToDevice, h->stream));
-    const CmpOut o{h->cmp_off.p, h->cmp_x.p, h->cmp_y.p};
-    hipLaunchKernelGGL(costmap_polygons_write_fleet_kernel, dim3((unsigned)blocks), dim3(kCmpThreads), 0, h->stream, h->cmp_rec.p, h->cmp_blk.p, n_scenes,
-                       (int)ncnt, h->cmp_cnt.p, o);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(off.data(), h->cmp_off.p, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(px.data(), h->cmp_x.p, (size_t)verts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(py.data(), h->cmp_y.p, (size_t)verts * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-  }
-
-  // host tables: the converted rows of scene s (teb_amd_set_obstacles_from_costmap_polygons' table of its grid) ++ its custom rows,
-  // exactly what teb_amd_set_scenes would parse
-  std::vector<HostObst> tabs(n_scenes);
-  std::vector<int> so;
-  for (int s = 0; s < n_scenes; ++s) {
-    so.assign(off.begin() + rec[s].row0, off.begin() + rec[s].row0 + nrs[s]);
-    so.push_back(nvs[s]);
-    if (const char* bad = polygon_list_table(so.data(), px.data() + rec[s].vtx0, py.data() + rec[s].vtx0, nrs[s], tabs[s]))
-      return fail(TEB_AMD_ERR_INVALID_ARG, bad);
-    tabs[s].append(tc[s]);
-    for (int i = 0; i < nrs[s]; ++i) off[(size_t)rec[s].row0 + i] += rec[s].vtx0;   // the polygon list of the scenes one after the other
-  }
-  off[(size_t)rows] = (int)verts;
-  if (out_offset && out_x && out_y && rows <= capacity_obstacles && verts <= capacity_points) {
-    std::copy(off.begin(), off.end(), out_offset);
-    std::copy(px.begin(), px.end(), out_x);
-    std::copy(py.begin(), py.end(), out_y);
-  }
-  return install_scene_set(h, std::move(tabs), std::move(vc), via_x, via_y, vias);
+  // Early, as teb_amd_set_scenes: all three capacities; after the count pass rows and polygon vertices again, with the converted ones.
+  return convert_costmaps<PolygonRows>(h, fn, SceneSetRoute{via_count, via_x, via_y}, h->cms.grids_host.data(), n_scenes, robot_pose,
+                                       costmap_obstacles_behind_robot_dist, tile_cells, custom, handle_caps(h),
+                                       PolygonRows::Out{n_obstacles, n_points, out_offset, out_x, out_y, capacity_obstacles, capacity_points});
 }
 
 int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t* bands, int32_t nf, const double* fx, const double* fy,
@@ -2576,8 +2387,8 @@ int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t*
       return fail(TEB_AMD_ERR_INVALID_ARG, buf);
     }
   if (h->stride > 1024) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check supports bands up to 1024 poses");
-  if (h->cm_fp.n < 2 * (size_t)kMaxFeasFootprint) { h->cm_fp.free(); HIPCHK(h->cm_fp.alloc(2 * (size_t)kMaxFeasFootprint)); }
-  if (h->cm_out.n < 2 * (size_t)h->max_tebs + 1) { h->cm_out.free(); HIPCHK(h->cm_out.alloc(2 * (size_t)h->max_tebs + 1)); }
+  HIPCHK(ensure(h->cm_fp, 2 * (size_t)kMaxFeasFootprint));
+  HIPCHK(ensure(h->cm_out, 2 * (size_t)h->max_tebs + 1));
   if (!h->cms_bands.p) HIPCHK(h->cms_bands.alloc((size_t)h->max_tebs));
   // [feasible | first_infeasible] ns each, then the overflow flag: one download
   int* ovf = h->cm_out.p + 2 * (size_t)ns;
@@ -2585,10 +2396,9 @@ int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t*
   HIPCHK(hipMemcpyAsync(h->cm_fp.p, fx, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(h->cm_fp.p + kMaxFeasFootprint, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
-  hipLaunchKernelGGL(feasibility_fleet_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, h->cms_bands.p,
-                     h->cms.grids.p, nf, h->cm_fp.p, h->cm_fp.p + kMaxFeasFootprint, inscribed_radius, min_res_angular, look_ahead_idx,
-                     lookahead_distance, 1 << 22, h->cm_out.p, h->cm_out.p + ns, ovf);
-  HIPCHK(hipGetLastError());
+  LAUNCH(feasibility_fleet_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, h->cms_bands.p, h->cms.grids.p, nf,
+         h->cm_fp.p, h->cm_fp.p + kMaxFeasFootprint, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, h->cm_out.p,
+         h->cm_out.p + ns, ovf);
   std::vector<int> out(2 * (size_t)ns + 1);
   HIPCHK(hipMemcpyAsync(out.data(), h->cm_out.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // (the caller's bands and footprint are read until here)
@@ -2616,9 +2426,8 @@ int teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_st
   if (!h->prune_msg.p) HIPCHK(h->prune_msg.alloc(10 * (size_t)h->max_tebs));
   HIPCHK(hipMemcpyAsync(h->prune_msg.p, msg.data(), msg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // the upload reads msg; nothing waits for the kernel
-  hipLaunchKernelGGL(prune_fleet_kernel, dim3(h->B), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), h->fleet.scene_of.p,
-                     h->prune_msg.p, (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples, h->has_vs.p, h->vs.p);
-  HIPCHK(hipGetLastError());
+  LAUNCH(prune_fleet_kernel, dim3(h->B), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), h->fleet.scene_of.p, h->prune_msg.p,
+         (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples, h->has_vs.p, h->vs.p);
   h->consumers_valid = false; h->nmax_known = -1;
   h->signatures_stale();   // the bands change: the single scene's signatures and the per-scene signatures are stale
   return TEB_AMD_OK;
@@ -2726,8 +2535,7 @@ int teb_amd_get_plan_cursors(teb_amd_handle_t* h, int32_t* begin) {
   if (h->plans.n == 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_plan_cursors: no global plans set (teb_amd_set_global_plans)");
   if (!begin) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_plan_cursors: null argument");
   HIPCHK(hipMemcpyAsync(begin, h->plans.cursor.p, (size_t)h->plans.n * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int teb_amd_plan_windows(teb_amd_handle_t* h, int32_t n, const teb_amd_plan_window_params_t* params, const double* robot_pose,
@@ -2765,8 +2573,7 @@ int teb_amd_plan_windows(teb_amd_handle_t* h, int32_t n, const teb_amd_plan_wind
   a.via_sep = prm.global_plan_viapoint_sep;
   a.overwrite_orientation = prm.global_plan_overwrite_orientation; a.moving_average_length = prm.moving_average_length;
   a.out = P.rec.p; a.pack = P.pack.p; a.ticket = P.ticket.p; a.pack_capacity = (long long)P.pack.n;
-  hipLaunchKernelGGL(plan_window_kernel, dim3((unsigned)n), dim3(kPwThreads), 0, h->stream, a);
-  HIPCHK(hipGetLastError());
+  LAUNCH(plan_window_kernel, dim3((unsigned)n), dim3(kPwThreads), 0, h->stream, a);
   std::vector<PlanWinOut> rec(N);
   HIPCHK(hipMemcpyAsync(rec.data(), P.rec.p, N * sizeof(PlanWinOut), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
@@ -2931,8 +2738,7 @@ int append_candidates(teb_amd_handle* h, const TickScratch& sc, const std::vecto
   if (scene_map) HIPCHK(hipMemcpyAsync(F.scene_of.p + slot0, F.band_scene.data() + slot0, cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(sc.map, acc.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
   h->B = slot0 + cnt;
-  hipLaunchKernelGGL(move_bands_kernel, dim3(cnt), dim3(kThreads), 0, h->stream, sc.cand, batch_of(h), sc.map, slot0, 0);
-  HIPCHK(hipGetLastError());
+  LAUNCH(move_bands_kernel, dim3(cnt), dim3(kThreads), 0, h->stream, sc.cand, batch_of(h), sc.map, slot0, 0);
   HIPCHK(hipStreamSynchronize(h->stream));   // the staging vectors live on this stack frame
   return TEB_AMD_OK;
 }
@@ -2967,12 +2773,10 @@ struct SingleRoute {
     HIPCHK(hipMemcpyAsync(h->g_vy.p, t.vy.data(), N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const long long pairs = (long long)N * N;
     t.ga.N = N; t.ga.gx = h->g_vx.p; t.ga.gy = h->g_vy.p; t.ga.adj = h->g_adj.p;
-    hipLaunchKernelGGL(graph_edges_kernel, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, scene_of(h), t.ga);
-    HIPCHK(hipGetLastError());
+    LAUNCH(graph_edges_kernel, dim3((unsigned)((pairs + kThreads - 1) / kThreads)), dim3(kThreads), 0, h->stream, scene_of(h), t.ga);
     t.mem->g_adj.resize((size_t)pairs);
     HIPCHK(hipMemcpyAsync(t.mem->g_adj.data(), h->g_adj.p, (size_t)pairs, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return TEB_AMD_OK;
+    return synced(h);
   }
   int paths(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // the paths uploaded to sc.off / sc.px / sc.py
     const TickPlanner& t = P[who[0]];
@@ -3045,9 +2849,8 @@ struct FleetRoute {
     HIPCHK(hipMemcpyAsync(F.ex_gvy.p, ally.data(), nv * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(F.ex_rec.p, recs.data(), recs.size() * sizeof(GraphFleetRec), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(F.ex_orient.p, orient.data(), orient.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(graph_edges_fleet_kernel, dim3((unsigned)((most + kThreads - 1) / kThreads), (unsigned)who.size()), dim3(kThreads), 0,
-                       h->stream, F.scenes.p, F.ex_rec.p);
-    HIPCHK(hipGetLastError());
+    LAUNCH(graph_edges_fleet_kernel, dim3((unsigned)((most + kThreads - 1) / kThreads), (unsigned)who.size()), dim3(kThreads), 0, h->stream, F.scenes.p,
+           F.ex_rec.p);
     std::vector<unsigned char> adjm(na);
     HIPCHK(hipMemcpyAsync(adjm.data(), F.ex_gadj.p, na, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -3191,8 +2994,7 @@ int finish_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, std::vector<Ti
   for (size_t i = 0; i < P.size(); ++i)
     for (size_t b = 0; b < rule[i].size(); ++b) ve[P[i].bands[b]] = rule[i][b];
   HIPCHK(hipMemcpyAsync(h->via_en.p, ve.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int copy_graph(const PlannerMemory& m, double* vx, double* vy, unsigned char* adjacency, int32_t capacity_vertices, int32_t* n_vertices) {
@@ -3377,12 +3179,10 @@ int compact_by_map(teb_amd_handle* h, const std::vector<int>& map) {
     std::vector<int> ident(K);
     for (int k = 0; k < K; ++k) ident[k] = k;
     HIPCHK(hipMemcpyAsync(h->cand_map.p, map.data(), K * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(move_bands_kernel, dim3(K), dim3(kThreads), 0, h->stream, src, tmp, h->cand_map.p, 0, 1);
-    HIPCHK(hipGetLastError());
+    LAUNCH(move_bands_kernel, dim3(K), dim3(kThreads), 0, h->stream, src, tmp, h->cand_map.p, 0, 1);
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpyAsync(h->cand_map.p, ident.data(), K * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(move_bands_kernel, dim3(K), dim3(kThreads), 0, h->stream, tmp, src, h->cand_map.p, 0, 1);
-    HIPCHK(hipGetLastError());
+    LAUNCH(move_bands_kernel, dim3(K), dim3(kThreads), 0, h->stream, tmp, src, h->cand_map.p, 0, 1);
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   if (h->hsig_mode != 0 && h->hsig_B == B) {   // the kept bands' signatures stay valid: same rows, new order
@@ -3465,14 +3265,12 @@ namespace {
 // detour_stats_kernel over all B bands: st [4 * B], opt [B]
 int detour_statistics(teb_amd_handle* h, const teb_amd_hcp_params_t* p, int B, std::vector<double>& st, std::vector<int>& opt) {
   if (int rc = ensure_candidate_buffers(h)) return rc;
-  hipLaunchKernelGGL(detour_stats_kernel, dim3(B), dim3(kThreads), 0, h->stream, batch_of(h), p->length_start_orientation_vector, h->cand_sig.p);
-  HIPCHK(hipGetLastError());
+  LAUNCH(detour_stats_kernel, dim3(B), dim3(kThreads), 0, h->stream, batch_of(h), p->length_start_orientation_vector, h->cand_sig.p);
   st.assign((size_t)4 * B, 0.0);
   opt.assign(B, 0);
   HIPCHK(hipMemcpyAsync(st.data(), h->cand_sig.p, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(opt.data(), h->optimized.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 }  // namespace
 
@@ -3523,8 +3321,7 @@ int teb_amd_set_optimized_flags(teb_amd_handle_t* h, const int32_t* flags) {
   std::vector<int> f(h->B);
   for (int b = 0; b < h->B; ++b) f[b] = flags[b] != 0;
   HIPCHK(hipMemcpyAsync(h->optimized.p, f.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int teb_amd_get_optimized_flags(teb_amd_handle_t* h, int32_t* flags) {
@@ -3533,8 +3330,7 @@ int teb_amd_get_optimized_flags(teb_amd_handle_t* h, int32_t* flags) {
   if (!flags) return fail(TEB_AMD_ERR_INVALID_ARG, "null flags");
   if (h->B <= 0) return TEB_AMD_OK;
   HIPCHK(hipMemcpyAsync(flags, h->optimized.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int teb_amd_get_band_flags(teb_amd_handle_t* h, int32_t* via_points_enabled, int32_t* has_vel_start, int32_t* has_vel_goal) {
@@ -3544,8 +3340,7 @@ int teb_amd_get_band_flags(teb_amd_handle_t* h, int32_t* via_points_enabled, int
   if (via_points_enabled) HIPCHK(hipMemcpyAsync(via_points_enabled, h->via_en.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (has_vel_start) HIPCHK(hipMemcpyAsync(has_vel_start, h->has_vs.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   if (has_vel_goal) HIPCHK(hipMemcpyAsync(has_vel_goal, h->has_vg.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 int teb_amd_device_state(teb_amd_handle_t* h, void** x, void** y, void** theta, void** dt, void** n, int32_t* stride) {
@@ -3711,9 +3506,7 @@ int teb_amd_debug_distance(teb_amd_handle_t* h, int32_t nq, const int32_t* obst_
   HIPCHK(hipMemcpy(d_th.p, theta, nq * sizeof(double), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_t.p, t, nq * sizeof(double), hipMemcpyHostToDevice));
   SceneDev sc = scene_of(h);
-  hipLaunchKernelGGL(distance_kernel, dim3((nq + 255) / 256), dim3(256), 0, h->stream, h->cfg, sc, nq, d_oi.p, d_x.p, d_y.p, d_th.p,
-                     d_st.p, d_t.p, d_dist.p, d_grad.p);
-  HIPCHK(hipGetLastError());
+  LAUNCH(distance_kernel, dim3((nq + 255) / 256), dim3(256), 0, h->stream, h->cfg, sc, nq, d_oi.p, d_x.p, d_y.p, d_th.p, d_st.p, d_t.p, d_dist.p, d_grad.p);
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(dist, d_dist.p, nq * sizeof(double), hipMemcpyDeviceToHost));
   if (grad) HIPCHK(hipMemcpy(grad, d_grad.p, 3 * (size_t)nq * sizeof(double), hipMemcpyDeviceToHost));
@@ -3788,8 +3581,7 @@ int teb_amd_debug_mfma_selftest(teb_amd_handle_t* h, const double* A, const doub
   HIPCHK(hipMalloc(reinterpret_cast<void**>(&dC), 256 * sizeof(double))); HIPCHK(hipMalloc(reinterpret_cast<void**>(&dT), 2 * sizeof(long long)));
   HIPCHK(hipMemcpyAsync(dA, A, 128 * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(dB, B, 128 * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  hipLaunchKernelGGL(mfma_selftest_kernel, dim3(1), dim3(64), 0, h->stream, dA, dB, dC, reps, dT);
-  HIPCHK(hipGetLastError());
+  LAUNCH(mfma_selftest_kernel, dim3(1), dim3(64), 0, h->stream, dA, dB, dC, reps, dT);
   long long t[2] = {0, 0};
   HIPCHK(hipMemcpyAsync(C, dC, 256 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(t, dT, sizeof(t), hipMemcpyDeviceToHost, h->stream));
@@ -3811,8 +3603,7 @@ int teb_amd_debug_stream(teb_amd_handle_t* h, int64_t n_doubles, int32_t repeats
   HIPCHK(a.alloc((size_t)n_doubles)); HIPCHK(b.alloc((size_t)n_doubles));
   HIPCHK(hipMemsetAsync(a.p, 0, sizeof(double) * (size_t)n_doubles, h->stream));
   for (int r = 0; r < repeats; ++r) {
-    hipLaunchKernelGGL(stream_kernel, dim3(2048), dim3(256), 0, h->stream, a.p, b.p, (size_t)n_doubles);
-    HIPCHK(hipGetLastError());
+    LAUNCH(stream_kernel, dim3(2048), dim3(256), 0, h->stream, a.p, b.p, (size_t)n_doubles);
   }
   HIPCHK(hipStreamSynchronize(h->stream));
   a.free(); b.free();
@@ -3826,8 +3617,7 @@ int teb_amd_debug_poke_pose_count(teb_amd_handle_t* h, int32_t b, int32_t n) {
   if (rc) return rc;
   if (b < 0 || b >= h->max_tebs) return fail(TEB_AMD_ERR_INVALID_ARG, "band index out of range");
   HIPCHK(hipMemcpyAsync(h->n.p + b, &n, sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  return TEB_AMD_OK;
+  return synced(h);
 }
 
 // diagnostic of the multi-CU mode: from now on every multi-CU launch leaves host-visible breadcrumbs, and one that is still running after

@@ -13,23 +13,11 @@
 // __forceinline__ body; the forms for a scene set (at the end of this file) run the same bodies behind a per-scene record.
 #pragma once
 #include "teb_feasibility.hpp"
+#include "teb_costmap_pods.hpp"
 
 namespace tebamd {
 
-constexpr int kCmoThreads = 256;
-constexpr int kCmoScanThreads = 1024;
-
-// robot_pose_ and costmap_obstacles_behind_robot_dist; (c, s) = PoseSE2::orientationUnitVec (pose_se2.h:215), computed on the host
-// with std::cos / std::sin so that the bits are glibc's
-struct CmoFilter {
-  double rx, ry, c, s, dist;
-};
-
-// The rows of the obstacle table the write pass fills (SceneDev order of teb_amd_set_obstacles).
-struct CmoRows {
-  int *type, *dyn, *voff;
-  double *ax, *ay, *bx, *by, *rad, *vx, *vy, *cx, *cy, *brad;
-};
+// GridDev, CmoFilter, CmoRows, CmoSceneRec and kCmoThreads / kCmoScanThreads: teb_costmap_pods.hpp; the rules that fill them: teb_costmap_host.hpp
 
 // costmap_2d::Costmap2D::mapToWorld: the centre of cell (mx, my) (also the vertices of teb_costmap_polygons.hpp)
 __device__ __forceinline__ void costmap_cell_centre(const GridDev& g, int mx, int my, double& wx, double& wy) {
@@ -121,13 +109,7 @@ __global__ void __launch_bounds__(kCmoThreads) costmap_obstacles_write_kernel(Gr
 // launch each. Every scene has a record; blockIdx.y (count, write) or blockIdx.x (scan) selects it, so the record is uniform over the
 // workgroup and arrives through scalar loads. The lanes are the single-scene lanes: a scene's counts, offsets and points are those of
 // a handle that holds only its grid.
-struct CmoSceneRec {
-  GridDev g;
-  CmoFilter f;
-  int ncols, nrows, chunk, nchunks;   // the single-scene rule on this grid (0 lanes: a grid without interior columns / rows)
-  int cnt_off;                        // first of the scene's ncols * nchunks + 1 counters
-  int out_off;                        // first point of the scene in the scratch of the write pass (prefix of the totals)
-};
+// (CmoSceneRec: the lanes are point_lanes of teb_costmap_host.hpp on the scene's grid, laid out by PointRows::layout.)
 // grid = (blocks over the scene with the most lanes, scenes): a workgroup beyond its scene's lanes returns at once
 __global__ void __launch_bounds__(kCmoThreads) costmap_obstacles_count_fleet_kernel(const CmoSceneRec* __restrict__ recs, int* cnt) {
   const CmoSceneRec& q = recs[blockIdx.y];

@@ -33,15 +33,7 @@
 
 namespace tebamd {
 
-constexpr int kCmpThreads = 256;
-constexpr int kCmpSlots = 4096;                       // cells of a block: one 64 x 64 tile at most
-constexpr int kCmpPer = kCmpSlots / kCmpThreads;      // slots per lane in the block scans
-constexpr int kCmpMaxTile = 64;
-
-// The block geometry: tiles of T cells, k tiles per block, ntx x nby blocks over the visit domain ncols x nrows.
-struct CmpGeom {
-  int ncols, nrows, T, k, nty, nby;
-};
+// CmpGeom, CmpSceneRec and the kCmp* constants: teb_costmap_pods.hpp; the rules that fill them: teb_costmap_host.hpp (polygon_blocks, PolygonRows::layout)
 
 // The converted rows in scratch: off[row] = its first vertex, x / y the vertices (world coordinates) of all rows in row order.
 struct CmpOut {
@@ -250,16 +242,6 @@ __global__ void __launch_bounds__(kCmpThreads) costmap_polygons_write_kernel(Gri
 // holds 97 KB of LDS and so runs alone on its CU: none is started for nothing). A workgroup finds its scene by a search over the prefix
 // array of block counts that depends on blockIdx.x alone, so the scene's record is uniform over the workgroup and arrives through scalar
 // loads. The blocks are the single-scene blocks: a scene's counts, offsets and vertices are those of a handle that holds only its grid.
-struct CmpSceneRec {
-  GridDev g;
-  CmoFilter f;
-  CmpGeom q;      // the scene's own tile size: T, k = kCmpSlots / T^2
-  int blk0;       // the scene's first block in the flat block list of the set
-  int nblk;       // its blocks (0: a grid without a visit domain)
-  int cnt0;       // first of the scene's nblk + 1 counters in each of the three count arrays
-  int row0, vtx0; // write pass: the scene's first row / first vertex in the scratch of the whole set
-};
-
 // The scene of flat block b: the last s with blk0[s] <= b (blk0: n + 1 entries, blk0[n] = blocks of the set > b), which skips the scenes
 // without blocks.
 __device__ __forceinline__ int cmp_scene_of_block(const int* __restrict__ blk0, int n, int b) {

@@ -15,14 +15,9 @@
 // the lane from the segment's first pose so that every sample has the reference's bits.
 #pragma once
 #include "teb_edges.hpp"
+#include "teb_costmap_pods.hpp"   // GridDev
 
 namespace tebamd {
-
-struct GridDev {
-  const unsigned char* cells;
-  int sx, sy;
-  double res, ox, oy;
-};
 
 // costmap_2d::Costmap2D::worldToMap
 __device__ __forceinline__ bool world_to_map(const GridDev& g, double wx, double wy, int& mx, int& my) {

@@ -1,7 +1,7 @@
 // teb_scene_store.hpp — ONE obstacle table, host side and device side, for the single scene of a handle and for a scene set (fleet
 // batches, teb_fleet.hpp) alike. The host part (HostObst, its parse, the lists derived from it, the segments of a scene set) is plain
 // C++ over include/teb_amd.h: tests/host/scene_table_check.cpp compiles it alone with -DTEB_SCENE_STORE_HOST_ONLY. The device part
-// (DevBuf, DevSceneStore) needs the HIP runtime, SceneDev and CmoRows.
+// (DevBuf, DevSceneStore) needs the HIP runtime and SceneDev.
 #pragma once
 
 #include <algorithm>
@@ -177,7 +177,7 @@ inline std::vector<SceneSegment> scene_segments(const HostObst* tabs, const int*
 #include <hip/hip_runtime.h>
 
 #include "teb_device.hpp"
-#include "teb_costmap_obstacles.hpp"
+#include "teb_costmap_pods.hpp"   // CmoRows
 
 namespace tebamd {
 
@@ -197,6 +197,13 @@ struct DevBuf {
 };
 template <class... Bufs>
 void free_all(Bufs&... bufs) { (bufs.free(), ...); }
+// scratch that only grows: b holds at least count elements afterwards (its contents are lost when it grows)
+template <typename T>
+hipError_t ensure(DevBuf<T>& b, size_t count) {
+  if (b.n >= count) return hipSuccess;
+  b.free();
+  return b.alloc(count);
+}
 
 // count elements to the device on the stream (none: nothing enqueued); src is read until the stream is synchronised
 template <typename T>
@@ -264,7 +271,7 @@ struct DevSceneStore {
     s.lox = list.p + g.list; s.loy = s.lox + M; s.lor = s.lox + 2 * (size_t)M; s.lovx = s.lox + 3 * (size_t)M; s.lovy = s.lox + 4 * (size_t)M;
     return s;
   }
-  // the rows the costmap writer fills (teb_costmap_obstacles.hpp)
+  // the rows the costmap writer fills (costmap_obstacles_write_kernel, teb_costmap_obstacles.hpp)
   CmoRows rows() const { return CmoRows{type.p, dyn.p, voff.p, ax.p, ay.p, bx.p, by.p, rad.p, vx.p, vy.p, cx.p, cy.p, brad.p}; }
 };
 
