@@ -19,7 +19,9 @@
 // hold; the sweep checks afterwards that they did at every point of the sequence - T_in + all splits < max_samples and T_in - all merges
 // > min_samples bound the count from both sides - and otherwise (or when a member gave up: chain longer than kArChainSteps evaluations,
 // more than kArChainStack halves waiting) the sequential machine runs the sweep. Same rules, same order, same edit script: the bands
-// are bit-identical (tests/test_autoresize_chains.py on the host, the autoResize parity tests and the bit fingerprints on the device).
+// are bit-identical (tests/test_autoresize_chains.py on the host, the autoResize parity tests and the bit fingerprints on the device;
+// tests/test_gpu_hp_autoresize.py pins both machines sweep by sweep to a plain restatement of the reference's loop, at the thresholds,
+// the guards, the limits below and every wave, slot and capacity boundary).
 //
 // This header has no device-only construct: the host test compiles it with TEB_AR_HD empty and emulates the lanes one after the other.
 #pragma once
