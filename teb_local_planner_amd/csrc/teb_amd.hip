@@ -32,8 +32,19 @@
 #include "teb_scene_store.hpp"
 #include "teb_hcp_host.hpp"
 #include "teb_costmap_host.hpp"
+#include "teb_launch_host.hpp"
 
 using namespace tebamd;
+
+// teb_launch_host.hpp names the layouts, the scene kinds and the limits of its rules itself: they are the kernel's
+static_assert(LAYOUT_BAND == SOLVER_BAND && LAYOUT_BLOCKS == SOLVER_CR && LAYOUT_BAND_HBM == SOLVER_BANDG, "teb_launch_host.hpp numbers the layouts");
+static_assert(KIND_POINTS == SCENE_POINTS && KIND_GENERIC == SCENE_GENERIC && KIND_POINTS_SMALL == SCENE_POINTS_SMALL && KIND_GENERIC_SMALL == SCENE_GENERIC_SMALL &&
+              KIND_POINTS_DEFAULTS == SCENE_POINTS_DEFAULTS && KIND_POINTS_SMALL_DEFAULTS == SCENE_POINTS_SMALL_DEFAULTS && KIND_GENERIC_DEFAULTS == SCENE_GENERIC_DEFAULTS &&
+              KIND_GENERIC_SMALL_DEFAULTS == SCENE_GENERIC_SMALL_DEFAULTS && KIND_POINTS_WIDE == SCENE_POINTS_WIDE && KIND_POINTS_SMALL_WIDE == SCENE_POINTS_SMALL_WIDE &&
+              KIND_POINTS_LIGHT == SCENE_POINTS_LIGHT && KIND_POINTS_SMALL_LIGHT == SCENE_POINTS_SMALL_LIGHT && KIND_POINTS_CUSTOM == SCENE_POINTS_CUSTOM &&
+              KIND_POINTS_SMALL_CUSTOM == SCENE_POINTS_SMALL_CUSTOM && KIND_GENERIC_CUSTOM == SCENE_GENERIC_CUSTOM && KIND_GENERIC_SMALL_CUSTOM == SCENE_GENERIC_SMALL_CUSTOM,
+              "teb_launch_host.hpp numbers the scene kinds");
+static_assert(kMaxSolverHelpers == kMcuMaxSpec, "teb_launch_host.hpp: one solver helper per speculative trial of teb_multicu.hpp");
 
 // the instantiations of teb_optimize_kernel live in translation units of their own (teb_opt_launch.hpp)
 TEB_OPT_FOR_ALL(TEB_OPT_DECLARE)
@@ -117,6 +128,7 @@ struct SceneLayout {
   LdsPlan plan;
   int cache_entries() const { return fast_points ? max_cache : 0; }   // 0: generic distance path
 };
+struct Strips { double *x, *y, *th, *dt; int* n; };   // the four strips of a set of bands and their pose counts
 
 struct teb_amd_handle {
   int device = 0;
@@ -148,6 +160,8 @@ struct teb_amd_handle {
   DevBuf<int> n, has_vs, has_vg, rotdir, via_en, status, optimized, iters, last_iters, trials, assoc_cnt, assoc, assoc_ovf, via_pose, legacy_idx;
   DevBuf<double> x, y, th, dt, vs, vg, chi2, cost, lambda, Hbackup, Hband, ob_x, ob_y, ob_th, ob_dt;   // ob_*: strips before an optimistic launch
   DevBuf<int> ob_n;
+  Strips live() const { return Strips{x.p, y.p, th.p, dt.p, n.p}; }               // the bands the kernels work on
+  Strips saved() const { return Strips{ob_x.p, ob_y.p, ob_th.p, ob_dt.p, ob_n.p}; }   // their copy from before a checked launch
   DevBuf<long long> clk;   // BatchDev::clk
   // multi-CU mode (teb_multicu.hpp): control words, published poses, distance records; sized on first use
   DevBuf<unsigned> mcu_ctl;
@@ -158,11 +172,7 @@ struct teb_amd_handle {
   int mcu_last_helpers = 0;   // distance helpers per band of the last launch (0: none), teb_amd_last_launch_info
   int mcu_last_solvers = 0;   // solver helpers per band of the last launch
   int mcu_last_repeated = 0;  // that launch timed out waiting for its helpers and was repeated on one CU per band
-  // back-off of the distance helpers: after a launch whose helpers came late (a device busy with other work) the next
-  // mcu_backoff_left launches run on one CU per band without asking; then one launch probes again. Every further miss doubles the pause
-  // (4, 8, .. 256 launches), a probe that succeeds clears it.
-  int mcu_backoff_left = 0;
-  int mcu_backoff_len = 0;
+  HelperBackoff mcu_backoff;  // the pause of the distance helpers after a launch they came late to (teb_launch_host.hpp)
   unsigned* mcu_trace = nullptr;   // teb_amd_debug_mcu_watchdog: host-pinned breadcrumbs of the multi-CU launch, one word per workgroup
   int mcu_watchdog_ms = 0;
   int mcu_debug_flags = 0;
@@ -175,6 +185,7 @@ struct teb_amd_handle {
   // snapshot
   DevBuf<int> snap_n;
   DevBuf<double> snap_x, snap_y, snap_th, snap_dt;
+  Strips snapshot() const { return Strips{snap_x.p, snap_y.p, snap_th.p, snap_dt.p, snap_n.p}; }
   // debug / select
   DevBuf<double> dbg_H, dbg_b, dbg_chi2, sel_cost;
   DevBuf<int> sel_idx, err_flag;
@@ -376,10 +387,9 @@ std::shared_ptr<RtcKernel> rtc_lookup(const teb_amd_handle* h, const OptArgs& ar
 #define TEB_PF_BIT(ID) key.flags |= (unsigned long long)((TEB_PF_EXPR_##ID) ? 1 : 0) << bit; ++bit;
   TEB_PF_ALL(TEB_PF_BIT)
 #undef TEB_PF_BIT
-  const bool sm = small && c.jacobian_mode == TEB_AMD_JACOBIAN_ANALYTIC;
-  if (small && !sm) return nullptr;   // (helper workgroups exist in the small-batch kinds only, which exist for closed-form Jacobians)
   key.solver = solver; key.jmode = c.jacobian_mode;
-  key.scene = sc.fast_points ? (sm ? SCENE_POINTS_SMALL_CUSTOM : SCENE_POINTS_CUSTOM) : (sm ? SCENE_GENERIC_SMALL_CUSTOM : SCENE_GENERIC_CUSTOM);
+  key.scene = scene_kinds(pf, sc.fast_points != 0, small, c.jacobian_mode).custom;
+  if (key.scene == KIND_NONE) return nullptr;   // (helper workgroups exist in the small-batch kinds only, which exist for closed-form Jacobians)
   std::string why;
   std::shared_ptr<RtcKernel> rk = rtc_request(key, wait, &why);
   return (rk && rk->state.load() == RtcKernel::READY) ? rk : nullptr;
@@ -416,19 +426,10 @@ hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const Bat
   std::memset(&none, 0, sizeof none);
   const McuDev* mc = mcu ? mcu : &none;
   const bool small = mc->K + mc->D > 0;   // helper workgroups: the small-batch instantiation of the scene kind
-  const void* k = nullptr;
+  const int pf = profile_matches(h, a, sc);
+  const SceneKinds kinds = scene_kinds(pf, sc.fast_points != 0, small, h->cfg.jacobian_mode);
   h->last_defaults_profile = 0;
-  const int pf = profile_matches(h, a, sc);   // (a build without the twins, or a mode they do not exist for, returns null: generic instantiation)
-  int scene_kind = -1;   // which instantiation runs (teb_amd_debug_last_instantiation)
-  if (pf != 0) {
-    const bool sm = small && h->cfg.jacobian_mode == TEB_AMD_JACOBIAN_ANALYTIC;
-    if (pf == 1) scene_kind = sc.fast_points ? (sm ? SCENE_POINTS_SMALL_DEFAULTS : SCENE_POINTS_DEFAULTS) : (sm ? SCENE_GENERIC_SMALL_DEFAULTS : SCENE_GENERIC_DEFAULTS);
-    else if (pf == 2) scene_kind = sm ? SCENE_POINTS_SMALL_WIDE : SCENE_POINTS_WIDE;
-    else scene_kind = sm ? SCENE_POINTS_SMALL_LIGHT : SCENE_POINTS_LIGHT;
-    k = opt_kernel(solver, h->cfg.jacobian_mode, scene_kind);
-    if (k) h->last_defaults_profile = pf;
-  }
-  h->last_inst[0] = solver; h->last_inst[1] = h->cfg.jacobian_mode; h->last_inst[2] = -1;
+  h->last_inst[0] = solver; h->last_inst[1] = h->cfg.jacobian_mode; h->last_inst[2] = -1;   // which instantiation runs (teb_amd_debug_last_instantiation)
   void* params[] = {const_cast<teb_amd_config_t*>(&h->cfg), const_cast<SceneDev*>(&sc), const_cast<BatchDev*>(&bt), const_cast<OptArgs*>(&a),
                     const_cast<LdsPlan*>(&plan), const_cast<McuDev*>(mc)};
   // a configuration off the defaults: the instantiation compiled for IT at run time, once it is ready (teb_rtc.hpp)
@@ -437,62 +438,30 @@ hipError_t launch_opt(teb_amd_handle* h, int grid, const SceneDev& sc, const Bat
     hipFunction_t f = rtc_function(*rk, h->device, h->lds_limit, &why);
     if (f) {
       h->last_defaults_profile = 4;
-      h->last_inst[2] = sc.fast_points ? (small ? SCENE_POINTS_SMALL_CUSTOM : SCENE_POINTS_CUSTOM) : (small ? SCENE_GENERIC_SMALL_CUSTOM : SCENE_GENERIC_CUSTOM);
+      h->last_inst[2] = kinds.custom;
       return hipModuleLaunchKernel(f, grid * (1 + mc->K + mc->D), 1, 1, kThreads, 1, 1, plan.total_bytes, h->stream, params, nullptr);
     }
   }
-  if (!k) {
-    scene_kind = sc.fast_points ? (small ? SCENE_POINTS_SMALL : SCENE_POINTS) : (small ? SCENE_GENERIC_SMALL : SCENE_GENERIC);
-    k = opt_kernel(solver, h->cfg.jacobian_mode, scene_kind);
-    h->last_defaults_profile = 0;
-  }
-  if (!k) return hipErrorInvalidDeviceFunction;
-  h->last_inst[2] = scene_kind;
-  return hipLaunchKernel(k, dim3(grid * (1 + mc->K + mc->D)), dim3(kThreads), params, plan.total_bytes, h->stream);
+  const Prebuilt pre = pick_prebuilt(kinds, pf, [&](int kind) { return opt_kernel(solver, h->cfg.jacobian_mode, kind); });
+  if (!pre.fn) return hipErrorInvalidDeviceFunction;
+  h->last_defaults_profile = pre.profile;
+  h->last_inst[2] = pre.kind;
+  return hipLaunchKernel(pre.fn, dim3(grid * (1 + mc->K + mc->D)), dim3(kThreads), params, plan.total_bytes, h->stream);
 }
 
-// Multi-CU mode (teb_multicu.hpp): helper workgroups per band of this launch - K solver helpers (speculative LM trials, any scene kind)
-// and D distance helpers (generic scenes: association + distance records). Small batches only: one workgroup per CU (the LDS footprint
-// of the layouts) means B (1 + K + D) <= number of CUs keeps every workgroup resident. Closed-form Jacobians (the small-batch
-// instantiations); the solver helpers need a layout whose normal matrix another workgroup can pick up (blocks in LDS with their HBM
-// backup, or the band copy of the hybrid solve), the distance helpers the new association.
-constexpr size_t kMcuItemsMaxBytes = (size_t)1 << 30;   // distance records of the multi-CU mode: beyond 1 GiB the launch stays on one CU per band
-void mcu_helpers_for(teb_amd_handle* h, const OptArgs& args, int eff_solver, int* K_out, int* D_out) {
-  *K_out = 0; *D_out = 0;
-  if (args.debug_linearize || h->cfg.jacobian_mode != TEB_AMD_JACOBIAN_ANALYTIC || h->B <= 0) return;
-  const int cus = h->num_cus > 0 ? h->num_cus : 256;
-  const int room = cus / h->B - 1;   // helper workgroups per band that still leave every workgroup its own CU
-  int K = 0, D = 0;
-  if (h->opt.speculative_trials >= 0 && eff_solver != SOLVER_BANDG && !(eff_solver == SOLVER_BAND && h->band_ldlt) && args.inner > 0) {
-    // automatic: as many of the three retries as the batch leaves CUs for (<= 64 bands: all three, <= 128: the first - the common - one)
-    K = h->opt.speculative_trials > 0 ? std::min((int)h->opt.speculative_trials, kMcuMaxSpec) : kMcuMaxSpec;
-    K = std::max(0, std::min(K, room));
-  }
-  if (h->opt.multi_cu >= 0 && !h->layout.fast_points && !h->cfg.legacy_obstacle_association && h->M > 0) {
-    D = std::min(room - K, 60);                               // beyond ~ 5 poses per helper the hand-off costs more than the tile
-    // ... and that holds for short bands as well: at most one helper per 6 poses of the handle's capacity (round 6; until then a 60-pose
-    // band could be given 60 helpers with a pose each). This is also where the one known defect of the mode lives: with 40 - 60 helpers on
-    // 57 .. 62-pose bands 0.4 - 2.4 % of the launches returned ONE band off the single-CU result by |d chi2| ~ 1e-3 .. 1e-1 (rounds 4 - 6
-    // binaries alike; more often the faster the kernel). Not found in round 6: agent-scope release / acquire fences at every hand-over,
-    // fine-grained (uncached) hand-over buffers, returning atomics for the records, a poisoned pose buffer (never read stale) and an exact
-    // arrival count changed nothing; a 14 us pause in front of the replay reduces it 20 x. At <= 20 helpers: 0 - 2 of 2000 launches, at
-    // <= 12 none observed; C5 (53 - 60 helpers x 5 - 6 poses): 0 of 1400 (profiles/mcu_race_r06.txt).
-    D = std::min(D, std::max(2, h->stride / 6));   // (the pose capacity: the bands grow under autoResize, what the host knows is where they started)
-    if (h->opt.multi_cu > 0) D = std::min(D, (int)h->opt.multi_cu);
-    // auto: enough (pose, obstacle) work - and ONE band: the defect above needs at least two bands in the launch (any single band of that
-    // scene with 60 helpers: 0 of 9000 launches; two bands 8 of 3000, three 18 of 3000; the bands' buffers do not overlap - padding them
-    // changed nothing - so what the bands share is not understood). multi_cu > 0 still asks for helpers on any batch (the tests do).
-    else if (h->B > 1 || (size_t)h->M * (size_t)(h->nmax_known > 0 ? h->nmax_known : h->stride) < 4096) D = 0;
-    if (D < 2) D = 0;
-  }
-  *K_out = K; *D_out = D;
+// bytes(S, layout, cache entries) of the LDS plan on a device whose workgroups may use lds_limit bytes: what the rules of teb_launch_host.hpp ask
+auto plan_bytes_of(size_t lds_limit) {
+  return [lds_limit](int S, int solver, int ob) { return (size_t)make_lds_plan(S, solver, ob, lds_limit).total_bytes; };
 }
-
-// largest pose capacity whose LDS plan (with the obstacle cache of this scene, if it is in use) fits
-int max_capacity_of(teb_amd_handle* h, int solver, int upto, int ob) {
-  int S = upto;
-  while (S > 8 && (size_t)make_lds_plan(S, solver, ob, h->lds_limit).total_bytes > h->lds_limit) --S;
-  return (size_t)make_lds_plan(S, solver, ob, h->lds_limit).total_bytes <= h->lds_limit ? S : 0;
+// what helpers_wanted reads of the handle and the call (h->layout, h->M: helpers exist against the single scene only)
+HelperInputs helper_inputs(const teb_amd_handle* h, const OptArgs& args, bool fleet, int layout) {
+  HelperInputs in;
+  in.fleet = fleet; in.debug_linearize = args.debug_linearize != 0; in.jacobian_mode = h->cfg.jacobian_mode;
+  in.B = h->B; in.M = h->M; in.stride = h->stride; in.nmax_known = h->nmax_known; in.num_cus = h->num_cus;
+  in.speculative_trials = h->opt.speculative_trials; in.multi_cu = h->opt.multi_cu;
+  in.layout = layout; in.band_ldlt = h->band_ldlt != 0; in.inner = args.inner;
+  in.fast_points = h->layout.fast_points != 0; in.legacy_association = h->cfg.legacy_obstacle_association != 0;
+  return in;
 }
 
 // the four strips and the pose counts in ONE launch (five copy commands cost more in launch gaps than in bytes: 2.4 MB at the headline)
@@ -541,7 +510,6 @@ __global__ void __launch_bounds__(256) pack_results_kernel(double* __restrict__ 
   if (t < B) { msg[t] = (double)status[t]; msg[B + t] = (double)iters[t]; msg[2 * B + t] = (double)trials[t]; msg[3 * B + t] = chi2[t]; msg[4 * B + t] = cost[t]; msg[5 * B + t] = lambda[t]; }
 }
 
-struct Strips { double *x, *y, *th, *dt; int* n; };
 static int copy_strips(teb_amd_handle_t* h, const Strips& dst, const Strips& src, int bands) {
   const size_t count = (size_t)bands * h->stride;   // >= bands
   const int grid = (int)std::min<size_t>(2048, (count + 255) / 256);
@@ -549,6 +517,81 @@ static int copy_strips(teb_amd_handle_t* h, const Strips& dst, const Strips& src
   return TEB_AMD_OK;
 }
 
+// The per-band flags of the launch that just ran - a band outgrew the layout (2), the helpers of the multi-CU mode came late (4) - and,
+// if asked for, the longest band. Synchronous: the flags decide whether the launch has to be repeated (documented in teb_amd.h).
+int read_flags(teb_amd_handle* h, bool* outgrown, bool* helpers_late, int* nmax) {
+  std::vector<int> ovf(h->B), nn(nmax ? h->B : 0);
+  HIPCHK(hipMemcpyAsync(ovf.data(), h->assoc_ovf.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (nmax) HIPCHK(hipMemcpyAsync(nn.data(), h->n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  int flags = 0;
+  for (int v : ovf) flags |= v;
+  *outgrown = (flags & 2) != 0;
+  if (helpers_late) *helpers_late = (flags & 4) != 0;
+  if (nmax) *nmax = nn.empty() ? 0 : std::max(0, *std::max_element(nn.begin(), nn.end()));
+  return TEB_AMD_OK;
+}
+// diagnostic (teb_amd_debug_mcu_watchdog): a multi-CU launch that does not finish in time is reported with the breadcrumbs of its
+// workgroups, and the process ends (a kernel cannot be cancelled; the bounded spins of the kernel make this unreachable unless the
+// protocol itself is broken)
+void mcu_watchdog(teb_amd_handle* h, int H) {
+  const auto t0 = std::chrono::steady_clock::now();
+  while (hipStreamQuery(h->stream) == hipErrorNotReady) {
+    if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > h->mcu_watchdog_ms) {
+      fprintf(stderr, "[teb_amd multi-CU watchdog] launch of %d bands x (1 + %d) workgroups still running after %d ms; breadcrumbs (epoch << 8 | code):\n", h->B, H, h->mcu_watchdog_ms);
+      for (int w = 0; w < h->B * (1 + H) && w < 1024; ++w) fprintf(stderr, " wg%d:%x", w, h->mcu_trace[w]);
+      fprintf(stderr, "\n");
+      fflush(stderr);
+      _exit(3);
+    }
+  }
+}
+
+// The buffers of the multi-CU mode for hp helpers per band, sized on first use, its control words zeroed on the stream before the
+// launch, and what the kernel is told of them. A failed allocation of the distance records is no error: the launch then runs without
+// distance helpers (hp.D = 0).
+int prepare_helpers(teb_amd_handle* h, Helpers& hp, McuDev& mcu) {
+  std::memset(&mcu, 0, sizeof mcu);
+  const size_t need_items = hp.D > 0 ? distance_records(h->B, h->M, h->stride) : 0;
+  if (h->mcu_items_have < need_items) {
+    h->mcu_items.free(); h->mcu_items_have = 0;
+    if (h->mcu_items.alloc(need_items) != hipSuccess) { (void)hipGetLastError(); hp.D = 0; }
+    else h->mcu_items_have = need_items;
+  }
+  if (hp.K + hp.D == 0) return TEB_AMD_OK;
+  if (!h->mcu_ctl.p) {
+    HIPCHK(h->mcu_ctl.alloc((size_t)h->max_tebs * kMcuCtlWords)); HIPCHK(h->mcu_pub.alloc((size_t)h->max_tebs * kMcuPubArrays * h->stride));
+    HIPCHK(h->mcu_spec.alloc((size_t)h->max_tebs * (kMcuMaxSpec + 1) * mcu_spec_slot(h->stride)));
+  }
+  HIPCHK(hipMemsetAsync(h->mcu_ctl.p, 0, (size_t)h->B * kMcuCtlWords * sizeof(unsigned), h->stream));
+  mcu.K = hp.K; mcu.D = hp.D; mcu.ctl = h->mcu_ctl.p; mcu.pub = h->mcu_pub.p; mcu.items = hp.D > 0 ? h->mcu_items.p : nullptr; mcu.item_cap = h->M; mcu.spec = h->mcu_spec.p;
+  mcu.timeout_ticks = helper_timeout_ticks(h->opt.multi_cu_timeout_us);
+  if (hp.D > 0) mcu.timeout_ticks = h->mcu_backoff.probe_timeout(mcu.timeout_ticks);
+  mcu.trace = h->mcu_trace;
+  mcu.debug_flags = h->mcu_debug_flags;
+  if (h->mcu_trace) std::memset(h->mcu_trace, 0, 1024 * sizeof(unsigned));
+  return TEB_AMD_OK;
+}
+// the strips as they are now, for a repeat of the launch
+int save_strips(teb_amd_handle* h) {
+  if (!h->opt_backup_ready) {
+    const size_t BS = (size_t)h->max_tebs * h->stride;
+    HIPCHK(h->ob_x.alloc(BS)); HIPCHK(h->ob_y.alloc(BS)); HIPCHK(h->ob_th.alloc(BS)); HIPCHK(h->ob_dt.alloc(BS)); HIPCHK(h->ob_n.alloc(h->max_tebs));
+    h->opt_backup_ready = true;
+  }
+  return copy_strips(h, h->saved(), h->live(), h->B);
+}
+// the longest resident band, read back from the device
+int longest_band(teb_amd_handle* h, int* nmax) {
+  std::vector<int> n(h->B);
+  HIPCHK(hipMemcpyAsync(n.data(), h->n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  *nmax = 0;
+  for (int v : n) *nmax = std::max(*nmax, v);
+  return TEB_AMD_OK;
+}
+
+// One optimise launch: what it runs is decided by the rules of teb_launch_host.hpp; here are the buffers, the launches and the copies.
 int launch(teb_amd_handle* h, const OptArgs& args) {
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs uploaded");
   // What the launch runs against, decided ONCE: the single scene of the handle, or the scene set (teb_amd_set_scenes) - then the layout,
@@ -557,129 +600,53 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
   const SceneLayout& own = fleet ? h->fleet.layout : h->layout;
   SceneDev sc = scene_of(h);
   BatchDev bt = batch_of(h);
-  // The layout of the normal matrix follows the pose capacity of the handle (blocks in LDS <= 238 poses, band in LDS <= 337, band in
-  // HBM beyond), the faster layouts only hold shorter bands. A handle created for long bands that currently holds short ones is
-  // launched in the fastest layout that leaves the bands 10 % room to grow (autoResize); should a band outgrow it all the same, the
-  // launch is repeated from the saved strips in the handle's own layout. Results do not depend on the layout (same arithmetic up to
-  // the order of the block reduction). TEB_AMD_FIXED_LAYOUT=1 switches this off.
-  int eff_solver = own.solver;
-  LdsPlan eff_plan = own.plan;
   // (a fleet launch has no helper workgroups: mcu is null then)
   auto run = [&](int solver, const LdsPlan& plan, const McuDev* mcu) {
     return fleet ? launch_fleet(h, h->B, bt, args, solver, plan) : launch_opt(h, h->B, sc, bt, args, solver, plan, mcu);
   };
-  bool optimistic = false;
-  if (own.solver != SOLVER_CR && !args.debug_linearize && !h->opt.fixed_layout && h->opt.layout == TEB_AMD_LAYOUT_AUTO && !h->band_ldlt) {
-    int nmax = h->nmax_known;
-    if (nmax < 0) {   // a device-side producer changed the bands since the host last saw their pose counts
-      std::vector<int> n(h->B);
-      HIPCHK(hipMemcpyAsync(n.data(), h->n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-      nmax = 0;
-      for (int v : n) nmax = std::max(nmax, v);
-    }
-    const int need = nmax + nmax / 10 + 4;   // 10 % room to grow; a band that needs more triggers the repeat below
-    const int ob = own.cache_entries();
-    const int s_cr = max_capacity_of(h, SOLVER_CR, std::min(h->stride, 238), ob);
-    const int s_band = own.solver == SOLVER_BANDG ? max_capacity_of(h, SOLVER_BAND, std::min(h->stride, 337), ob) : 0;
-    if (s_cr > 0 && need <= s_cr) { eff_solver = SOLVER_CR; eff_plan = make_lds_plan(s_cr, SOLVER_CR, ob, h->lds_limit); optimistic = true; }
-    else if (s_band > 0 && need <= s_band) { eff_solver = SOLVER_BAND; eff_plan = make_lds_plan(s_band, SOLVER_BAND, ob, h->lds_limit); optimistic = true; }
-  }
-  // multi-CU mode: helper workgroups per band (0 = none); its buffers, and the control words zeroed on the stream before the launch
-  int K = 0, D = 0;
-  if (!fleet) mcu_helpers_for(h, args, eff_solver, &K, &D);   // (a fleet launch has no helper workgroups)
-  if (D > 0 && h->mcu_backoff_left > 0) { D = 0; --h->mcu_backoff_left; }   // paused after a miss: one CU per band, no wait, no repeat
-  if (D > 0) {
-    // distance records [B][M][4][stride]: bounded (the association list of a pose is short, but its capacity is every obstacle), and a
-    // failed allocation is no error - the launch then runs on one CU per band
-    const size_t need_items = (size_t)h->B * h->M * 4 * h->stride;
-    if (need_items * sizeof(double) > kMcuItemsMaxBytes) D = 0;
-    else if (h->mcu_items_have < need_items) {
-      h->mcu_items.free(); h->mcu_items_have = 0;
-      if (h->mcu_items.alloc(need_items) != hipSuccess) { (void)hipGetLastError(); D = 0; }
-      else h->mcu_items_have = need_items;
-    }
-  }
-  const int H = K + D;
+  // 1. decide: the layout of this launch (layout_per_launch), its helper workgroups, whether its flags are looked at afterwards
+  const LayoutSwitches sw{args.debug_linearize != 0, h->opt.fixed_layout != 0, h->opt.layout != TEB_AMD_LAYOUT_AUTO, h->band_ldlt != 0};
+  int nmax = h->nmax_known;
+  if (nmax < 0 && may_launch_optimistic(own.solver, sw))   // a device-side producer changed the bands since the host last saw their pose counts
+    if (int rc = longest_band(h, &nmax)) return rc;
+  const LaunchLayout lay = layout_per_launch(own.solver, sw, nmax, h->stride, own.cache_entries(), h->lds_limit, plan_bytes_of(h->lds_limit));
+  const int eff_solver = lay.layout;
+  const LdsPlan eff_plan = lay.optimistic ? make_lds_plan(lay.S, eff_solver, own.cache_entries(), h->lds_limit) : own.plan;
+  Helpers hp = helpers_for_launch(helper_inputs(h, args, fleet, eff_solver), h->mcu_backoff);
+  // 2. make sure the buffers exist (without distance records there are no distance helpers), 3. save the strips
   McuDev mcu;
-  std::memset(&mcu, 0, sizeof mcu);
-  if (H > 0) {
-    if (!h->mcu_ctl.p) {
-      HIPCHK(h->mcu_ctl.alloc((size_t)h->max_tebs * kMcuCtlWords)); HIPCHK(h->mcu_pub.alloc((size_t)h->max_tebs * kMcuPubArrays * h->stride));
-      HIPCHK(h->mcu_spec.alloc((size_t)h->max_tebs * (kMcuMaxSpec + 1) * mcu_spec_slot(h->stride)));
-    }
-    HIPCHK(hipMemsetAsync(h->mcu_ctl.p, 0, (size_t)h->B * kMcuCtlWords * sizeof(unsigned), h->stream));
-    mcu.K = K; mcu.D = D; mcu.ctl = h->mcu_ctl.p; mcu.pub = h->mcu_pub.p; mcu.items = D > 0 ? h->mcu_items.p : nullptr; mcu.item_cap = h->M; mcu.spec = h->mcu_spec.p;
-    mcu.timeout_ticks = (long long)(h->opt.multi_cu_timeout_us > 0 ? h->opt.multi_cu_timeout_us : 2000) * 100LL;   // 100 MHz real-time counter
-    // a probe after a pause waits 250 us at most: helpers that have CUs answer a phase within ~ 10 us, and a device that is still busy
-    // should cost the tick as little as possible beyond its one-CU time
-    if (D > 0 && h->mcu_backoff_len > 0) mcu.timeout_ticks = std::min(mcu.timeout_ticks, 25000LL);
-    mcu.trace = h->mcu_trace;
-    mcu.debug_flags = h->mcu_debug_flags;
-    if (h->mcu_trace) std::memset(h->mcu_trace, 0, 1024 * sizeof(unsigned));
-  }
+  if (int rc = prepare_helpers(h, hp, mcu)) return rc;
+  const int K = hp.K, D = hp.D, H = K + D;
   h->mcu_last_helpers = D; h->mcu_last_solvers = K; h->mcu_last_repeated = 0;
-  const bool checked = optimistic || D > 0;   // (solver helpers alone cannot fail a band: a late one just means the band solves itself)   // the launch is followed by a look at the per-band flags (and possibly repeated)
-  if (checked) {   // strips as they are now, for the repeat
-    if (!h->opt_backup_ready) {
-      const size_t BS = (size_t)h->max_tebs * h->stride;
-      HIPCHK(h->ob_x.alloc(BS)); HIPCHK(h->ob_y.alloc(BS)); HIPCHK(h->ob_th.alloc(BS)); HIPCHK(h->ob_dt.alloc(BS)); HIPCHK(h->ob_n.alloc(h->max_tebs));
-      h->opt_backup_ready = true;
-    }
-    if (int crc = copy_strips(h, Strips{h->ob_x.p, h->ob_y.p, h->ob_th.p, h->ob_dt.p, h->ob_n.p}, Strips{h->x.p, h->y.p, h->th.p, h->dt.p, h->n.p}, h->B)) return crc;
-  }
+  const bool checked = launch_is_checked(lay.optimistic, D);
+  if (checked)
+    if (int rc = save_strips(h)) return rc;
+  // 4. run
   if (h->opt.compile_for_config >= 2 && !fleet)   // synchronous mode: the wait for the compiler is not kernel time
     (void)rtc_lookup(h, args, sc, eff_solver, H > 0, profile_matches(h, args, sc), true);
   HIPCHK(hipEventRecord(h->ev0, h->stream));   // (the kernel clears its bands' overflow flags itself)
   HIPCHK(run(eff_solver, eff_plan, H > 0 ? &mcu : nullptr));
-  if (H > 0 && h->mcu_trace && h->mcu_watchdog_ms > 0) {
-    // diagnostic: a multi-CU launch that does not finish in time is reported with the breadcrumbs of its workgroups, and the process ends
-    // (a kernel cannot be cancelled; the bounded spins of the kernel make this unreachable unless the protocol itself is broken)
-    const auto t0 = std::chrono::steady_clock::now();
-    while (hipStreamQuery(h->stream) == hipErrorNotReady) {
-      if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > h->mcu_watchdog_ms) {
-        fprintf(stderr, "[teb_amd multi-CU watchdog] launch of %d bands x (1 + %d) workgroups still running after %d ms; breadcrumbs (epoch << 8 | code):\n", h->B, H, h->mcu_watchdog_ms);
-        for (int w = 0; w < h->B * (1 + H) && w < 1024; ++w) fprintf(stderr, " wg%d:%x", w, h->mcu_trace[w]);
-        fprintf(stderr, "\n");
-        fflush(stderr);
-        _exit(3);
-      }
-    }
-  }
+  if (H > 0 && h->mcu_trace && h->mcu_watchdog_ms > 0) mcu_watchdog(h, H);
   if (checked) {
+    // 5. look at the flags, 6. ask the ladder, 7. run what it says - from the saved strips, without helpers; ev0 stays where it was: the
+    // reported time includes the discarded launches
     HIPCHK(hipGetLastError());
-    // this mode is synchronous: the overflow flags decide whether the launch has to be repeated (documented in teb_amd.h)
-    std::vector<int> ovf(h->B), nn(h->B);
-    HIPCHK(hipMemcpyAsync(ovf.data(), h->assoc_ovf.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(nn.data(), h->n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
     bool outgrown = false, helpers_late = false;
-    for (int v : ovf) { outgrown = outgrown || (v & 2); helpers_late = helpers_late || (v & 4); }
-    h->nmax_known = 0;
-    for (int v : nn) h->nmax_known = std::max(h->nmax_known, v);
-    if (D > 0) {
-      if (helpers_late) { h->mcu_backoff_len = std::min(256, std::max(4, 2 * h->mcu_backoff_len)); h->mcu_backoff_left = h->mcu_backoff_len; }
-      else { h->mcu_backoff_len = 0; h->mcu_backoff_left = 0; }
+    if (int rc = read_flags(h, &outgrown, &helpers_late, &h->nmax_known)) return rc;
+    if (D > 0) h->mcu_backoff.update(helpers_late);
+    LadderStep step = after_first_look(lay.optimistic, outgrown, helpers_late);
+    if (step.next == LadderStep::RETRY_OPTIMISTIC) {
+      if (int crc = copy_strips(h, h->live(), h->saved(), h->B)) return crc;
+      HIPCHK(run(eff_solver, eff_plan, nullptr));
+      if (int rc = read_flags(h, &outgrown, nullptr, nullptr)) return rc;
+      step = after_second_look(outgrown);
     }
-    if (outgrown || helpers_late) {
-      // from the saved strips: in the handle's own layout when a band outgrew the optimistic one, and on one CU per band when the
-      // helpers of the multi-CU mode did not show up in time (a busy device: nothing promises their residency)
-      if (int crc = copy_strips(h, Strips{h->x.p, h->y.p, h->th.p, h->dt.p, h->n.p}, Strips{h->ob_x.p, h->ob_y.p, h->ob_th.p, h->ob_dt.p, h->ob_n.p}, h->B)) return crc;
-      bool own_layout = outgrown || !optimistic;
-      if (!own_layout) {
-        // helpers late, no band outgrown so far: once more in the optimistic layout - whose capacity a band may outgrow in THIS run
-        // (the first one was cut short), so its flags are read as well
-        HIPCHK(run(eff_solver, eff_plan, nullptr));
-        HIPCHK(hipMemcpyAsync(ovf.data(), h->assoc_ovf.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        for (int v : ovf) own_layout = own_layout || (v & 2);
-        if (own_layout)
-          if (int crc = copy_strips(h, Strips{h->x.p, h->y.p, h->th.p, h->dt.p, h->n.p}, Strips{h->ob_x.p, h->ob_y.p, h->ob_th.p, h->ob_dt.p, h->ob_n.p}, h->B)) return crc;
-      }
-      if (own_layout) HIPCHK(run(own.solver, own.plan, nullptr));   // ev0 stays where it was: the reported time includes the discarded launches
-      h->mcu_last_repeated = helpers_late ? 1 : 0;
-      h->nmax_known = -1;
+    if (step.next == LadderStep::OWN_LAYOUT) {
+      if (int crc = copy_strips(h, h->live(), h->saved(), h->B)) return crc;
+      HIPCHK(run(own.solver, own.plan, nullptr));
     }
+    h->mcu_last_repeated = step.repeated;
+    if (step.nmax_stale) h->nmax_known = -1;
   } else if (h->cfg.teb_autosize && !args.debug_linearize) {
     h->nmax_known = -1;   // asynchronous launch: autoResize may change the pose counts
   }
@@ -764,37 +731,18 @@ int teb_amd_create_ex(const teb_amd_config_t* cfg, int32_t max_tebs, int32_t max
   if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail(TEB_AMD_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", this library is built for gfx950 only");
   HIPCHK(hipSetDevice(device));
-  // Normal matrix as 8x8 blocks in LDS (SOLVER_CR: cyclic reduction in place, fastest) when that fits TOGETHER with the LDS cache
-  // of a full obstacle table of max_obstacles point-like entries; otherwise as a band in LDS (SOLVER_BAND: 44 instead of 70
-  // doubles per pose) with the hybrid cyclic reduction (level 0 from a band-form copy in HBM) - within 2 % of the block layout
-  // per step, keeps the obstacle cache and holds bands up to 337 poses.
-  int solver = SOLVER_CR;
   // the kernel also owns a little static LDS (__syncthreads_or scratch): keep 1 KiB of head-room
   const size_t lds_limit = (size_t)prop.sharedMemPerBlock - kLdsHeadroomBytes;
-  if (lds_bytes_for(max_poses, SOLVER_CR, lds_limit) > lds_limit) solver = SOLVER_BAND;
-  else if ((size_t)make_lds_plan(max_poses, SOLVER_CR, max_obstacles > 0 ? max_obstacles : 0, lds_limit).total_bytes > lds_limit &&
-           (size_t)make_lds_plan(max_poses, SOLVER_BAND, max_obstacles > 0 ? max_obstacles : 0, lds_limit).total_bytes <= lds_limit)
-    solver = SOLVER_BAND;
-  if (opt.layout == TEB_AMD_LAYOUT_BAND_LDS) solver = SOLVER_BAND;
-  else if (opt.layout == TEB_AMD_LAYOUT_BAND_HBM) solver = SOLVER_BANDG;
-  else if (opt.layout == TEB_AMD_LAYOUT_BLOCKS_LDS) {
-    if (lds_bytes_for(max_poses, SOLVER_CR, lds_limit) > lds_limit) return fail(TEB_AMD_ERR_CAPACITY, "TEB_AMD_LAYOUT_BLOCKS_LDS: max_poses too large for the block layout");
-    solver = SOLVER_CR;
-  }
-  // bands too long for the LDS band (> 337 poses; the reference's max_samples default is 500): the band form of the normal matrix
-  // moves to HBM (SOLVER_BANDG: 44 doubles per pose, L2-resident), everything else stays as it is
-  if (solver == SOLVER_BAND && lds_bytes_for(max_poses, SOLVER_BAND, lds_limit) > lds_limit) solver = SOLVER_BANDG;
-  // more than two poses per lane: only the band-in-HBM instantiations are compiled for it (teb_device.hpp: kPoseIterBandHbm)
   static_assert(TEB_AMD_MAX_POSES <= kThreads * 4, "TEB_AMD_MAX_POSES of include/teb_amd.h exceeds four poses per lane");
-  if (max_poses > kThreads * 2) solver = SOLVER_BANDG;   // (the LDS layouts end at 337 poses: the checks above have already moved it there)
-  const size_t lds = lds_bytes_for(max_poses, solver, lds_limit);
-  const int thread_limit = kThreads * (solver == SOLVER_BANDG ? kPoseIterBandHbm : 2);
-  if (max_poses > thread_limit || lds > lds_limit) {
+  const CreateLayout made = layout_at_create(max_poses, max_obstacles, lds_limit, opt.layout, kThreads, kPoseIterBandHbm, plan_bytes_of(lds_limit));
+  if (made.refused == CreateLayout::BLOCKS_TOO_LARGE) return fail(TEB_AMD_ERR_CAPACITY, "TEB_AMD_LAYOUT_BLOCKS_LDS: max_poses too large for the block layout");
+  if (made.refused == CreateLayout::CAPACITY) {
     char buf[256];
     std::snprintf(buf, sizeof buf, "max_poses=%d needs %zu B of LDS per workgroup (device limit %zu B, thread limit %d poses)",
-                  max_poses, lds, lds_limit, thread_limit);
+                  max_poses, made.lds, lds_limit, made.thread_limit);
     return fail(TEB_AMD_ERR_CAPACITY, buf);
   }
+  const int solver = made.layout;
   const size_t assoc_bytes = sizeof(int) * (size_t)max_tebs * max_poses * (size_t)(max_obstacles > 0 ? max_obstacles : 1);
   if (assoc_bytes > ((size_t)64 << 30)) return fail(TEB_AMD_ERR_CAPACITY, "association table would exceed 64 GiB");
 
@@ -845,12 +793,11 @@ int teb_amd_create_ex(const teb_amd_config_t* cfg, int32_t max_tebs, int32_t max
   A(h->hsig.alloc((size_t)max_tebs * (Mo > 2 ? Mo : 2))); A(h->hs_pre.alloc(Mo)); A(h->hs_pim.alloc(Mo)); A(h->hs_pex.alloc(Mo));
   if (ok && hipEventCreate(&h->ev0) != hipSuccess) ok = false;
   if (ok && hipEventCreate(&h->ev1) != hipSuccess) ok = false;
-  for (int sv : {SOLVER_BAND, SOLVER_CR, SOLVER_BANDG})   // every layout may be launched (teb_amd_set_obstacles / per-launch choice)
-    for (int jm : {TEB_AMD_JACOBIAN_ANALYTIC, TEB_AMD_JACOBIAN_G2O_NUMERIC})
-      for (int sk : {SCENE_POINTS, SCENE_GENERIC, SCENE_POINTS_SMALL, SCENE_GENERIC_SMALL, SCENE_POINTS_DEFAULTS, SCENE_POINTS_SMALL_DEFAULTS, SCENE_GENERIC_DEFAULTS, SCENE_GENERIC_SMALL_DEFAULTS}) {
-        const void* k = opt_kernel(sv, jm, sk);
-        if (ok && k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit) != hipSuccess) ok = false;
-      }
+  // every instantiation of the build may be launched (teb_amd_set_obstacles / per-launch choice) with any plan up to the limit
+#define TEB_OPT_FULL_LDS(S, J, P) \
+  if (const void* k = TEB_OPT_KERNEL_FN(S, J, P)()) if (ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit) != hipSuccess) ok = false;
+  TEB_OPT_FOR_ALL(TEB_OPT_FULL_LDS)
+#undef TEB_OPT_FULL_LDS
   if (ok && hipMemset(h->cost.p, 0, sizeof(double) * max_tebs) != hipSuccess) ok = false;
   if (ok && hipMemset(h->chi2.p, 0, sizeof(double) * max_tebs) != hipSuccess) ok = false;
   if (ok && hipMemset(h->iters.p, 0, sizeof(int) * max_tebs) != hipSuccess) ok = false;   // hasDiverged: "no statistics yet"
@@ -886,28 +833,19 @@ void teb_amd_destroy(teb_amd_handle_t* h) {
 }
 
 namespace {
-// The distance path and the layout that goes with it, for an obstacle cache of lay.max_cache entries: point-like fast path iff all
-// obstacles are Point/Circular, the footprint is Point/Circular, and the cache fits the LDS.
+// The distance path and the layout of the tables of a scene store, for an obstacle cache of lay.max_cache entries (layout_per_table), and
+// what the answer needs: the HBM band buffer of a handle that was created without one, the LDS plan.
 int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, SceneLayout& lay) {
-  const int M = lay.max_cache;
-  bool pointlike = pointlike_rows && (h->cfg.footprint_type == TEB_AMD_FOOTPRINT_POINT || h->cfg.footprint_type == TEB_AMD_FOOTPRINT_CIRCULAR);
-  if (h->opt.generic_distance_path) pointlike = false;
-  // a point-like scene whose obstacle cache does not fit beside the LDS band: the band moves to HBM and the cache stays (measured,
-  // 64 bands x 337 poses x 500 obstacles: 9.0 instead of 11.8 ms per step)
-  lay.solver = h->solver_created;
-  if (pointlike && M > 0 && lay.solver == SOLVER_BAND && h->opt.layout == TEB_AMD_LAYOUT_AUTO &&
-      (size_t)make_lds_plan(h->stride, SOLVER_BAND, M, h->lds_limit).total_bytes > h->lds_limit &&
-      (size_t)make_lds_plan(h->stride, SOLVER_BANDG, M, h->lds_limit).total_bytes <= h->lds_limit) {
-    if (h->hband_stride == 0) {
-      h->hband_stride = ((size_t)hbo(4 * h->stride) + 2 + 1) & ~(size_t)1;
-      h->Hband.free();
-      HIPCHK(h->Hband.alloc((size_t)h->max_tebs * h->hband_stride));
-    }
-    lay.solver = SOLVER_BANDG;
+  const TableLayout t = layout_per_table(pointlike_rows, h->cfg.footprint_type, h->opt.generic_distance_path != 0, h->solver_created, h->opt.layout,
+                                         lay.max_cache, h->stride, h->lds_limit, plan_bytes_of(h->lds_limit));
+  if (t.hbm_band && h->hband_stride == 0) {
+    h->hband_stride = ((size_t)hbo(4 * h->stride) + 2 + 1) & ~(size_t)1;
+    h->Hband.free();
+    HIPCHK(h->Hband.alloc((size_t)h->max_tebs * h->hband_stride));
   }
-  LdsPlan with_cache = make_lds_plan(h->stride, lay.solver, M, h->lds_limit);
-  if (pointlike && M > 0 && (size_t)with_cache.total_bytes <= h->lds_limit) { lay.fast_points = 1; lay.plan = with_cache; }
-  else { lay.fast_points = 0; lay.plan = make_lds_plan(h->stride, lay.solver, 0, h->lds_limit); }
+  lay.solver = t.layout;
+  lay.fast_points = t.fast_points;
+  lay.plan = make_lds_plan(h->stride, t.layout, t.cache_entries, h->lds_limit);
   return TEB_AMD_OK;
 }
 // (Re)derives everything that depends on BOTH obstacle tables and the configuration, for the ns tables `tabs` whose rows `store` holds
@@ -1053,11 +991,12 @@ int fleet_allocate(teb_amd_handle* h) {
   A(F.scenes.alloc(T)); A(F.scene_of.alloc(T)); A(F.sel_last.alloc(T)); A(F.sel_init.alloc(T)); A(F.sel_idx.alloc(T)); A(F.sel_cost.alloc(T));
   const size_t rows = (size_t)std::max(h->max_obst, 0) + kFleetPad;   // one product per row of the set's store
   A(F.hs_pre.alloc(rows)); A(F.hs_pim.alloc(rows)); A(F.hs_pex.alloc(rows)); A(F.hs_off.alloc(T + 1));
-  for (int sv : {SOLVER_BAND, SOLVER_CR, SOLVER_BANDG})
-    for (int sk : {SCENE_POINTS, SCENE_GENERIC}) {
-      const void* k = fleet_kernel(sv, sk);
-      if (ok && k && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit) != hipSuccess) ok = false;
-    }
+#ifdef TEB_AMD_HAS_FLEET_UNITS
+#define TEB_FLEET_FULL_LDS(S, P) \
+  if (const void* k = TEB_FLEET_KERNEL_FN(S, P)()) if (ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit) != hipSuccess) ok = false;
+  TEB_FLEET_FOR_ALL(TEB_FLEET_FULL_LDS)
+#undef TEB_FLEET_FULL_LDS
+#endif
   if (F.band_scene.empty()) F.band_scene.assign(T, 0);
   if (ok && hipMemcpy(F.scene_of.p, F.band_scene.data(), T * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) ok = false;
   if (!ok) {
@@ -3357,7 +3296,7 @@ int teb_amd_device_state(teb_amd_handle_t* h, void** x, void** y, void** theta, 
 int teb_amd_snapshot_state(teb_amd_handle_t* h) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if ((rc = copy_strips(h, Strips{h->snap_x.p, h->snap_y.p, h->snap_th.p, h->snap_dt.p, h->snap_n.p}, Strips{h->x.p, h->y.p, h->th.p, h->dt.p, h->n.p}, h->max_tebs))) return rc;
+  if ((rc = copy_strips(h, h->snapshot(), h->live(), h->max_tebs))) return rc;
   h->snap_nmax = h->nmax_known;
   h->snap_B = h->B;
   return TEB_AMD_OK;
@@ -3366,7 +3305,7 @@ int teb_amd_snapshot_state(teb_amd_handle_t* h) {
 int teb_amd_restore_state(teb_amd_handle_t* h) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if ((rc = copy_strips(h, Strips{h->x.p, h->y.p, h->th.p, h->dt.p, h->n.p}, Strips{h->snap_x.p, h->snap_y.p, h->snap_th.p, h->snap_dt.p, h->snap_n.p}, h->max_tebs))) return rc;
+  if ((rc = copy_strips(h, h->live(), h->snapshot(), h->max_tebs))) return rc;
   // snap_nmax bounded the first snap_B bands only; the copy brings back the counts of ALL max_tebs slots, so with another batch size the
   // bound says nothing about the bands beyond the old B
   h->consumers_valid = false; h->nmax_known = (h->B == h->snap_B) ? h->snap_nmax : -1;
@@ -3386,8 +3325,8 @@ int teb_amd_last_launch_info(teb_amd_handle_t* h, int32_t* distance_helpers_per_
 int teb_amd_multi_cu_backoff(teb_amd_handle_t* h, int32_t* launches_paused, int32_t* pause_length) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if (launches_paused) *launches_paused = h->mcu_backoff_left;
-  if (pause_length) *pause_length = h->mcu_backoff_len;
+  if (launches_paused) *launches_paused = h->mcu_backoff.left;
+  if (pause_length) *pause_length = h->mcu_backoff.len;
   return TEB_AMD_OK;
 }
 
