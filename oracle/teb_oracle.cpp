@@ -2212,8 +2212,9 @@ int teb_oracle_is_trajectory_feasible(const teb_amd_teb_batch_t* batch, int32_t 
       const double ddx = t.x[i + 1] - t.x[i], ddy = t.y[i + 1] - t.y[i];
       const double dnorm = std::sqrt(ddx * ddx + ddy * ddy);   // Eigen::Vector2d::norm()
       if (fabs(delta_rot) > min_resolution_collision_check_angular || dnorm > inscribed_radius) {
-        const int n_additional_samples = (int)std::max(std::ceil(fabs(delta_rot) / min_resolution_collision_check_angular),
-                                                       std::ceil(dnorm / inscribed_radius)) - 1;
+        // as the reference writes it: the double minus one, then the conversion (a NaN heading gives std::max its first argument, NaN)
+        const int n_additional_samples = std::max(std::ceil(fabs(delta_rot) / min_resolution_collision_check_angular),
+                                                  std::ceil(dnorm / inscribed_radius)) - 1;
         double px = t.x[i], py = t.y[i], pth = t.th[i];
         for (int step = 0; step < n_additional_samples; ++step) {
           px = px + ddx / (n_additional_samples + 1.0);

@@ -19,9 +19,10 @@
 
 namespace tebamd {
 
-// costmap_2d::Costmap2D::worldToMap
+// costmap_2d::Costmap2D::worldToMap. A NaN coordinate is off the map: the reference's (int) of a NaN quotient is undefined, x86 makes it
+// INT_MIN, which the unsigned comparison rejects, while the conversion here would give cell 0. !(w >= o) is w < o for every other value.
 __device__ __forceinline__ bool world_to_map(const GridDev& g, double wx, double wy, int& mx, int& my) {
-  if (wx < g.ox || wy < g.oy) return false;
+  if (!(wx >= g.ox) || !(wy >= g.oy)) return false;
   mx = (int)((wx - g.ox) / g.res);
   my = (int)((wy - g.oy) / g.res);
   return (unsigned)mx < (unsigned)g.sx && (unsigned)my < (unsigned)g.sy;
@@ -123,8 +124,8 @@ __device__ __forceinline__ void feasibility_band(FeasShared& sh, const int* __re
       const double dnorm = sqrt(ddx * ddx + ddy * ddy);
       if (fabs(delta_rot) > min_res_angular || dnorm > inscribed_radius) {
         const double a = ceil(fabs(delta_rot) / min_res_angular), d = ceil(dnorm / inscribed_radius);
-        const double m = fmax(a, d);
-        extra = (m >= 2147483647.0 || !(m == m)) ? 0x3fffffff : (int)m - 1;
+        const double m = a < d ? d : a;   // std::max: its first argument unless the second is larger - NaN for a NaN heading
+        extra = !(m == m) ? 0 : m >= 2147483647.0 ? 0x3fffffff : (int)m - 1;   // x86's cast of NaN - 1 is INT_MIN: no sample
       }
     }
     s_base[i + 1] = extra;   // temporarily: samples after pose i
