@@ -195,10 +195,8 @@ struct teb_amd_handle {
   // equivalence classes (f3)
   DevBuf<double> hsig, hs_pre, hs_pim;
   DevBuf<int> hs_pex;
-  std::vector<double> hsig_host;
-  int hsig_mode = 0, hsig_B = 0, hsig_M = 0;
+  SignatureSet sigs;            // of the single scene's bands (teb_hcp_host.hpp); hsig is the scratch of every signature launch
   bool hs_prod_valid = false;   // hs_pre / hs_pim / hs_pex hold the products of the current obstacle table
-  double hsig_prescaler = 0;
   int consumers_la = 0, consumers_prevent = 0;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -270,14 +268,11 @@ struct teb_amd_handle {
     DevBuf<double> sel_cost;
     DevBuf<SceneDev> scenes;
     // equivalence classes per scene (teb_amd_compute_h_signatures_per_scene): state of the scene set, beside the single scene's
-    // (hsig_host, hs_pre .. above), which the per-scene calls never touch
+    // (sigs, hs_pre .. above), which the per-scene calls never touch
     DevBuf<double> hs_pre, hs_pim;   // 2-D: prod_l of every row of the set's store, each over the rows of its own scene
     DevBuf<int> hs_pex, hs_off;      // hs_off [max_tebs + 1]: first value of every band in the signature buffer
     bool hs_prod_valid = false;
-    int hsig_mode = 0, hsig_B = 0;   // 0 = no valid signatures; 2 / 3 as hsig_mode of the handle
-    std::vector<int> hsig_off;       // [hsig_B + 1]
-    std::vector<double> hsig_host;   // band after band
-    double hsig_prescaler = 0;       // of those signatures
+    SignatureSet sigs;               // of the bands of the set, each as wide as its scene's table
     std::vector<PlannerMemory> memory;   // [n_scenes] what the planner of every scene - a robot - remembers; none of it is the single scene's
     // scratch of the candidate exploration per scene, separate from the single scene's and allocated at the first call: candidate
     // strips, path points, offsets, candidate -> scene map, signatures; the graphs of a call (vertices, adjacency, records)
@@ -297,7 +292,10 @@ struct teb_amd_handle {
   int explore_quota = 0;   // teb_amd_debug_set_explore_quota: paths per scene and round of the per-scene exploration, 0 = kExploreQuota
   // the bands, the obstacles or the configuration change: the signatures of an earlier compute call are stale, the single scene's and
   // the scene set's alike
-  void signatures_stale() { hsig_mode = 0; fleet.hsig_mode = 0; }
+  void signatures_stale() { sigs.clear(); fleet.sigs.clear(); }
+  // the bands changed on the device: the consumers' outputs are void, the host's bound on the pose counts is nmax (-1: unknown) and,
+  // unless the caller moves the signatures with the bands, these are stale
+  void bands_changed(int nmax = -1, bool signatures_too = true) { consumers_valid = false; nmax_known = nmax; if (signatures_too) signatures_stale(); }
 };
 
 namespace {
@@ -895,7 +893,7 @@ int commit_obstacles(teb_amd_handle* h) {
 int commit_fleet(teb_amd_handle* h) {
   auto& F = h->fleet;
   std::vector<SceneDev> views;
-  F.hsig_mode = 0; F.hs_prod_valid = false;   // signatures depend on the tables of the set and on include_dynamic_obstacles
+  F.sigs.clear(); F.hs_prod_valid = false;   // signatures depend on the tables of the set and on include_dynamic_obstacles
   return commit_tables(h, F.tabs.data(), F.via_count.data(), F.tabs.size(), F.store, F.layout, views, &F.scenes, nullptr);
 }
 // both, as far as they hold anything (teb_amd_set_config)
@@ -909,6 +907,39 @@ int commit_all(teb_amd_handle* h) {
 int refuse_in_fleet_mode(const teb_amd_handle* h, const char* call) {
   if (h->fleet.n_scenes > 0)
     return fail(TEB_AMD_ERR_INVALID_ARG, std::string(call) + ": not available while scenes are set (fleet mode); call teb_amd_clear_scenes first");
+  return TEB_AMD_OK;
+}
+// ... and the per-scene calls need one
+int require_fleet_mode(const teb_amd_handle* h, const char* call) {
+  if (h->fleet.n_scenes <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(call) + ": no scenes set (teb_amd_set_scenes)");
+  return TEB_AMD_OK;
+}
+// every band < B maps to a scene of the set (the check of teb_amd_optimize_batch)
+int check_band_scenes(const teb_amd_handle* h, int B) {
+  const auto& F = h->fleet;
+  for (int b = 0; b < B; ++b)
+    if (F.band_scene[b] >= F.n_scenes) {
+      char buf[160];
+      std::snprintf(buf, sizeof buf, "band %d maps to scene %d, but %d scenes are set (teb_amd_set_band_scenes)", b, F.band_scene[b], F.n_scenes);
+      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+    }
+  return TEB_AMD_OK;
+}
+// The planners of a scene set and their first B bands (BandGroups of teb_hcp_host.hpp), one group per scene. The single scene's one
+// planner is BandGroups(1, B, nullptr).
+int scene_groups(const teb_amd_handle* h, int B, BandGroups& G) {
+  if (int rc = check_band_scenes(h, B)) return rc;
+  G = BandGroups(h->fleet.n_scenes, B, h->fleet.band_scene.data());
+  return TEB_AMD_OK;
+}
+// best[s] is a band of scene s or negative (best NULL: none)
+int check_best_per_scene(const BandGroups& G, const int32_t* best, const char* call) {
+  for (int s = 0; best && s < G.size(); ++s)
+    if (best[s] >= 0 && !G.has(s, best[s])) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "%s: best[%d] = %d is not a band of scene %d", call, s, best[s], s);
+      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+    }
   return TEB_AMD_OK;
 }
 }  // namespace
@@ -1061,7 +1092,7 @@ int teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_
     if (scene_of[b] < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_band_scenes: negative scene index");
   auto& F = h->fleet;
   F.band_scene.assign((size_t)h->max_tebs, 0);   // bands >= count: scene 0
-  F.hsig_mode = 0;   // per-scene signatures were computed against the previous map
+  F.sigs.clear();   // per-scene signatures were computed against the previous map
   std::copy(scene_of, scene_of + count, F.band_scene.begin());
   if (F.allocated) {
     HIPCHK(hipMemcpyAsync(F.scene_of.p, F.band_scene.data(), F.band_scene.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1085,7 +1116,7 @@ int teb_amd_clear_scenes(teb_amd_handle_t* h) {
   if (rc) return rc;
   h->fleet.n_scenes = 0;   // the single-scene table, its lists and its layout are as they were
   h->fleet.tabs.clear(); h->fleet.via_count.clear();
-  h->fleet.hsig_mode = 0; h->fleet.hs_prod_valid = false;
+  h->fleet.sigs.clear(); h->fleet.hs_prod_valid = false;
   h->fleet.new_planners(0);
   return TEB_AMD_OK;
 }
@@ -1166,8 +1197,7 @@ int teb_amd_upload_tebs(teb_amd_handle_t* h, const teb_amd_teb_batch_t* bt) {
            h->via_en.p, h->vs.p, h->vg.p, h->x.p, h->y.p, h->th.p, h->dt.p, h->optimized.p);
     HIPCHK(hipStreamSynchronize(h->stream));   // (the pinned buffer is reused by the next call)
     h->B = B;
-    h->consumers_valid = false; h->nmax_known = nmax;
-    h->signatures_stale();
+    h->bands_changed(nmax);
     return TEB_AMD_OK;
   }
   const size_t w = (size_t)(bt->stride < h->stride ? bt->stride : h->stride) * sizeof(double);
@@ -1198,8 +1228,7 @@ int teb_amd_upload_tebs(teb_amd_handle_t* h, const teb_amd_teb_batch_t* bt) {
   HIPCHK(hipMemsetAsync(h->optimized.p, 0, B * sizeof(int), h->stream));   // bands from the host: optimized_ unknown -> false
   HIPCHK(hipStreamSynchronize(h->stream));
   h->B = B;
-  h->consumers_valid = false; h->nmax_known = nmax;
-  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->bands_changed(nmax);
   return TEB_AMD_OK;
 }
 
@@ -1598,8 +1627,7 @@ int finish_init(teb_amd_handle* h) {
   int err = 0;
   HIPCHK(hipMemcpyAsync(&err, h->err_flag.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->consumers_valid = false; h->nmax_known = -1;
-  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->bands_changed();
   if (err) return fail(TEB_AMD_ERR_CAPACITY, "initTrajectoryToGoal: the band needs more poses than max_poses");
   return TEB_AMD_OK;
 }
@@ -1680,8 +1708,7 @@ int teb_amd_update_and_prune(teb_amd_handle_t* h, int32_t b, const double* new_s
   const double* g = new_goal ? new_goal : z;
   LAUNCH(prune_kernel, dim3(b < 0 ? h->B : 1), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), b < 0 ? 0 : b, new_start ? 1 : 0,
          s[0], s[1], s[2], new_goal ? 1 : 0, g[0], g[1], g[2], min_samples);
-  h->consumers_valid = false; h->nmax_known = -1;
-  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->bands_changed();
   return TEB_AMD_OK;
 }
 
@@ -1698,7 +1725,7 @@ int set_velocity(teb_amd_handle* h, DevBuf<int>& flag, DevBuf<double>& vel, int 
     HIPCHK(hipMemcpyAsync(vel.p + 3 * b0, vv.data(), vv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  h->consumers_valid = false; h->nmax_known = -1;
+  h->bands_changed(-1, false);
   return TEB_AMD_OK;
 }
 }  // namespace
@@ -1828,113 +1855,112 @@ int teb_amd_set_costmap(teb_amd_handle_t* h, const uint8_t* cells, int32_t size_
   return TEB_AMD_OK;
 }
 
+namespace {
+// What the two feasibility calls share. Their argument checks: `given` says that the call's pointers and footprint size are usable.
+int check_feasibility_arguments(bool given, const char* what, double inscribed_radius, double min_res_angular) {
+  if (!given) return fail(TEB_AMD_ERR_INVALID_ARG, what);
+  if (!(inscribed_radius > 0) || !(min_res_angular > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "inscribed_radius and the angular resolution must be > 0");
+  return TEB_AMD_OK;
+}
+// ... and `count` checks in one launch: the footprint upload, the output block [feasible | first_infeasible] count each + the overflow
+// word with its one download, and the refusal of more than 2^22 samples. launch(fp_x, fp_y, feasible, first_infeasible, overflow) runs
+// the call's kernel on the device arrays.
+extern "C++" template <class Launch>
+int run_feasibility(teb_amd_handle* h, int count, int nf, const double* fx, const double* fy, int32_t* feasible, int32_t* first_infeasible, Launch launch) {
+  if (h->stride > 1024) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check supports bands up to 1024 poses");
+  HIPCHK(ensure(h->cm_fp, 2 * (size_t)kMaxFeasFootprint));
+  HIPCHK(ensure(h->cm_out, 2 * (size_t)h->max_tebs + 1));
+  int* ovf = h->cm_out.p + 2 * (size_t)count;
+  HIPCHK(hipMemcpyAsync(h->cm_fp.p, fx, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->cm_fp.p + kMaxFeasFootprint, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
+  if (int rc = launch(h->cm_fp.p, h->cm_fp.p + kMaxFeasFootprint, h->cm_out.p, h->cm_out.p + count, ovf)) return rc;
+  std::vector<int> out(2 * (size_t)count + 1);
+  HIPCHK(hipMemcpyAsync(out.data(), h->cm_out.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // (the caller's footprint, and what launch() uploaded, are read until here)
+  if (out[2 * (size_t)count]) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check: more than 2^22 interpolated samples requested (inscribed radius / angular resolution too small)");
+  for (int k = 0; k < count; ++k) { feasible[k] = out[k]; if (first_infeasible) first_infeasible[k] = out[count + k]; }
+  return TEB_AMD_OK;
+}
+}  // namespace
+
 int teb_amd_is_trajectory_feasible(teb_amd_handle_t* h, int32_t b, int32_t nf, const double* fx, const double* fy, double inscribed_radius,
                                    double min_res_angular, int32_t look_ahead_idx, double lookahead_distance, int32_t* feasible,
                                    int32_t* first_infeasible) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (h->cm.sx <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_is_trajectory_feasible: no costmap (teb_amd_set_costmap)");
-  if (!feasible || nf < 1 || nf > kMaxFeasFootprint || !fx || !fy) return fail(TEB_AMD_ERR_INVALID_ARG, "bad footprint / output");
-  if (!(inscribed_radius > 0) || !(min_res_angular > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "inscribed_radius and the angular resolution must be > 0");
+  if ((rc = check_feasibility_arguments(feasible && nf >= 1 && nf <= kMaxFeasFootprint && fx && fy, "bad footprint / output", inscribed_radius, min_res_angular))) return rc;
   if (h->B <= 0 || b >= h->B || b < -1) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
-  if (h->stride > 1024) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check supports bands up to 1024 poses");
   const int first = b < 0 ? 0 : b, count = b < 0 ? h->B : 1;
-  HIPCHK(ensure(h->cm_fp, 2 * (size_t)kMaxFeasFootprint));
-  HIPCHK(ensure(h->cm_out, 2 * (size_t)h->max_tebs + 1));
-  HIPCHK(hipMemcpyAsync(h->cm_fp.p, fx, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->cm_fp.p + kMaxFeasFootprint, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  int* ovf = h->cm_out.p + 2 * (size_t)h->max_tebs;
-  HIPCHK(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
-  const GridDev& g = h->cm;
-  LAUNCH(feasibility_kernel, dim3(count), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, first, g, nf, h->cm_fp.p,
-         h->cm_fp.p + kMaxFeasFootprint, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, h->cm_out.p, h->cm_out.p + h->max_tebs,
-         ovf);
-  std::vector<int> fe(count), fi(count);
-  int o = 0;
-  HIPCHK(hipMemcpyAsync(fe.data(), h->cm_out.p, count * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(fi.data(), h->cm_out.p + h->max_tebs, count * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&o, ovf, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (o) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check: more than 2^22 interpolated samples requested (inscribed radius / angular resolution too small)");
-  for (int k = 0; k < count; ++k) { feasible[k] = fe[k]; if (first_infeasible) first_infeasible[k] = fi[k]; }
-  return TEB_AMD_OK;
+  return run_feasibility(h, count, nf, fx, fy, feasible, first_infeasible, [&](double* px, double* py, int* fe, int* fi, int* ovf) {
+    LAUNCH(feasibility_kernel, dim3(count), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, first, h->cm, nf, px, py,
+           inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, fe, fi, ovf);
+    return (int)TEB_AMD_OK;
+  });
 }
 
 namespace {
-// H-signatures of the B bands of bt (the batch or the candidate scratch strips) into out [B * W], W = M (3-D) or 2 (2-D)
-int launch_hsig(teb_amd_handle* h, const BatchDev& bt, int B, double prescaler, double* out) {
-  SceneDev sc = scene_of(h);
-  const int M = h->M;
-  if (B <= 0) return TEB_AMD_OK;
+// The H-signatures of the `count` bands of bt (the batch, or the candidate strips of an exploration) into out. fl NULL: against the
+// single scene's table, band k at out + k * W, W = M (3-D) or 2 (2-D). Else band k against the table of scene fl->scene_of[k], at
+// fl->off[k] (3-D; the offsets uploaded by the caller) or at 2 k (2-D). n_values: values in all.
+int launch_signatures(teb_amd_handle* h, const FleetHsigDev* fl, const BatchDev& bt, int count, size_t n_values, double prescaler, double* out) {
+  auto& F = h->fleet;
+  if (count <= 0) return TEB_AMD_OK;
+  int widest = h->M;   // most rows of a table
+  if (fl) { widest = 0; for (const HostObst& t : F.tabs) widest = std::max(widest, (int)t.rows()); }
+  const size_t strip = (size_t)h->stride * sizeof(double);
   if (h->cfg.include_dynamic_obstacles) {
-    if (M > 0) {
-      // one lane per (band, obstacle) when that fills the chip; otherwise lanes over (obstacle, segment): same bits, lower latency
-      const char* force = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE ? "wide" : h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_SMALL ? "small" : nullptr;   // teb_amd_options_t::hsig3d_kernel pins one of the two kernels (tests, tools/hsig_bench.py)
-      const bool wide = force ? std::strcmp(force, "wide") == 0 : (long long)B * M >= 32768;
-      if (wide)
-        LAUNCH(hsig3d_kernel, dim3((M + kThreads - 1) / kThreads, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, sc, bt, out);
-      else
-        LAUNCH(hsig3d_small_kernel, dim3((M + kHsTile - 1) / kHsTile, B), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, sc, bt, out);
-    }
-  } else {
-    if (M > 0 && !h->hs_prod_valid) {   // the band-independent factor of A_l: once per obstacle table (O(M^2))
-      LAUNCH(hsig2d_prod_kernel, dim3((M + kThreads - 1) / kThreads), dim3(kThreads), 0, h->stream, sc, h->hs_pre.p, h->hs_pim.p, h->hs_pex.p);
-      h->hs_prod_valid = true;
-    }
-    LAUNCH(hsig2d_kernel, dim3(B), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, sc, bt, prescaler, h->hs_pre.p, h->hs_pim.p, h->hs_pex.p,
-           out);
+    if (n_values == 0) return TEB_AMD_OK;
+    const bool wide = hsig3d_wide(h->opt.hsig3d_kernel, (long long)n_values);
+    const dim3 grid((widest + (wide ? kThreads : kHsTile) - 1) / (wide ? kThreads : kHsTile), count);
+    if (!fl && wide) LAUNCH(hsig3d_kernel, grid, dim3(kThreads), 3 * strip, h->stream, scene_of(h), bt, out);
+    else if (!fl) LAUNCH(hsig3d_small_kernel, grid, dim3(kThreads), 3 * strip, h->stream, scene_of(h), bt, out);
+    else if (wide) LAUNCH(hsig3d_fleet_kernel, grid, dim3(kThreads), 3 * strip, h->stream, *fl, bt, out);
+    else LAUNCH(hsig3d_small_fleet_kernel, grid, dim3(kThreads), 3 * strip, h->stream, *fl, bt, out);
+    return TEB_AMD_OK;
   }
+  bool& products_valid = fl ? F.hs_prod_valid : h->hs_prod_valid;
+  if (widest > 0 && !products_valid) {   // the band-independent factor of A_l: once per obstacle table, every scene over its own rows (O(M^2))
+    const unsigned blocks = (widest + kThreads - 1) / kThreads;
+    if (!fl) LAUNCH(hsig2d_prod_kernel, dim3(blocks), dim3(kThreads), 0, h->stream, scene_of(h), h->hs_pre.p, h->hs_pim.p, h->hs_pex.p);
+    else LAUNCH(hsig2d_prod_fleet_kernel, dim3(blocks, F.n_scenes), dim3(kThreads), 0, h->stream, F.scenes.p, F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p);
+    products_valid = true;
+  }
+  if (!fl) LAUNCH(hsig2d_kernel, dim3(count), dim3(kThreads), 2 * strip, h->stream, scene_of(h), bt, prescaler, h->hs_pre.p, h->hs_pim.p, h->hs_pex.p, out);
+  else LAUNCH(hsig2d_fleet_kernel, dim3(count), dim3(kThreads), 2 * strip, h->stream, *fl, bt, prescaler, F.store.cx.p, F.hs_pre.p, F.hs_pim.p, F.hs_pex.p, out);
   return TEB_AMD_OK;
 }
 
-// Its counterpart for a scene set: the signatures of the `count` bands of bt (the batch or the set's candidate strips), band k against
-// the table of scene fl.scene_of[k], into out at fl.off[k] (3-D; `total` values in all, the offsets uploaded by the caller) or at 2 k
-// (2-D). widest: most rows of a table of the set.
-int launch_hsig_fleet(teb_amd_handle* h, const FleetHsigDev& fl, const BatchDev& bt, int count, size_t total, int widest, double prescaler,
-                      double* out) {
+// The signatures of the B resident bands into S at the offsets `off`: one launch into h->hsig [max_tebs * max(max_obstacles, 2)], one
+// download. by_scene: against the tables of the scene set (the offsets go to the device for the 3-D kernels), else the single scene's.
+int compute_signatures(teb_amd_handle* h, SignatureSet& S, bool by_scene, std::vector<int> off, double prescaler) {
   auto& F = h->fleet;
-  if (h->cfg.include_dynamic_obstacles) {
-    if (total > 0) {
-      // the rule of the single-scene launch on the total number of values; teb_amd_options_t::hsig3d_kernel pins one of the two
-      const bool wide = h->opt.hsig3d_kernel == TEB_AMD_HSIG3D_WIDE || (h->opt.hsig3d_kernel != TEB_AMD_HSIG3D_SMALL && (long long)total >= 32768);
-      if (wide)
-        LAUNCH(hsig3d_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, fl,
-               bt, out);
-      else
-        LAUNCH(hsig3d_small_fleet_kernel, dim3((widest + kHsTile - 1) / kHsTile, count), dim3(kThreads), 3 * (size_t)h->stride * sizeof(double), h->stream, fl,
-               bt, out);
-    }
-  } else {
-    if (widest > 0 && !F.hs_prod_valid) {   // the band-independent factor of A_l: once per scene set, every scene over its own rows
-      LAUNCH(hsig2d_prod_fleet_kernel, dim3((widest + kThreads - 1) / kThreads, F.n_scenes), dim3(kThreads), 0, h->stream, F.scenes.p, F.store.cx.p, F.hs_pre.p,
-             F.hs_pim.p, F.hs_pex.p);
-      F.hs_prod_valid = true;
-    }
-    LAUNCH(hsig2d_fleet_kernel, dim3(count), dim3(kThreads), 2 * (size_t)h->stride * sizeof(double), h->stream, fl, bt, prescaler, F.store.cx.p, F.hs_pre.p,
-           F.hs_pim.p, F.hs_pex.p, out);
-  }
+  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;   // homotopy_class_planner.hpp:50
+  double* host = S.reserve(std::move(off));
+  const size_t total = (size_t)S.off.back();
+  FleetHsigDev fl;
+  fl.scenes = F.scenes.p; fl.scene_of = F.scene_of.p; fl.off = F.hs_off.p;
+  if (by_scene && mode == 3 && total > 0) HIPCHK(hipMemcpyAsync(F.hs_off.p, S.off.data(), S.off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  if (int rc = launch_signatures(h, by_scene ? &fl : nullptr, batch_of(h), h->B, total, prescaler, h->hsig.p)) return rc;
+  if (total > 0) HIPCHK(hipMemcpyAsync(host, h->hsig.p, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  S.stamp(mode, prescaler);
   return TEB_AMD_OK;
 }
 }  // namespace
 
-// ---- f3 (arithmetic core): equivalence classes of the device-resident bands (kernels in teb_hsig.hpp) ----------------------------
+// ---- f3 (arithmetic core): equivalence classes of the device-resident bands (kernels in teb_hsig.hpp), for the single scene and per
+// scene of a fleet batch (the fleet forms of the kernels). Each step is one function over a SignatureSet and BandGroups. ------------------
 int teb_amd_compute_h_signatures(teb_amd_handle_t* h, double prescaler, double* values, int32_t* width) {
   int rc = check_handle(h);
   if (rc) return rc;
   if ((rc = refuse_in_fleet_mode(h, "teb_amd_compute_h_signatures"))) return rc;
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
-  BatchDev bt = batch_of(h);
-  const int M = h->M, B = h->B;
-  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;   // homotopy_class_planner.hpp:50
-  const int W = mode == 3 ? M : 2;
+  const int W = h->cfg.include_dynamic_obstacles ? h->M : 2;
   if (width) *width = W;
-  h->hsig_mode = mode; h->hsig_B = B; h->hsig_M = M; h->hsig_prescaler = prescaler;
-  h->hsig_host.assign((size_t)B * (W > 0 ? W : 1), 0.0);
-  if ((rc = launch_hsig(h, bt, B, prescaler, h->hsig.p))) return rc;
-  if ((size_t)B * W > 0)
-    HIPCHK(hipMemcpyAsync(h->hsig_host.data(), h->hsig.p, (size_t)B * W * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));
-  if (values && (size_t)B * W > 0) std::memcpy(values, h->hsig_host.data(), (size_t)B * W * sizeof(double));
+  if ((rc = compute_signatures(h, h->sigs, false, SignatureSet::fixed_width(h->B, W), prescaler))) return rc;
+  if (values) std::copy(h->sigs.values.begin(), h->sigs.values.begin() + h->sigs.off.back(), values);
   return TEB_AMD_OK;
 }
 
@@ -1943,48 +1969,10 @@ int teb_amd_filter_equivalence_classes(teb_amd_handle_t* h, double threshold, in
   int rc = check_handle(h);
   if (rc) return rc;
   if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_equivalence_classes"))) return rc;
-  if (h->hsig_mode == 0 || h->hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures first");
-  const int B = h->hsig_B, mode = h->hsig_mode, W = mode == 3 ? h->hsig_M : 2;
-  std::vector<int> order(B);
-  std::vector<const double*> row(B);
-  for (int b = 0; b < B; ++b) { order[b] = b; row[b] = h->hsig_host.data() + (size_t)b * W; }
-  filter_class_list(SignatureRule{mode, W, threshold}, max_number_plans_in_current_class, std::move(order), best, row, h->memory, keep, valid, reasonable);
+  if (h->sigs.mode == 0 || h->sigs.B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures first");
+  filter_class_lists(h->sigs, BandGroups(1, h->B, nullptr), threshold, max_number_plans_in_current_class, &best, &h->memory, keep, valid, reasonable);
   return TEB_AMD_OK;
 }
-
-// ---- equivalence classes per scene of a fleet batch (teb_amd.h, fleet batches; kernels: the fleet forms of teb_hsig.hpp) ----------
-namespace {
-int require_fleet_mode(const teb_amd_handle* h, const char* call) {
-  if (h->fleet.n_scenes <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(call) + ": no scenes set (teb_amd_set_scenes)");
-  return TEB_AMD_OK;
-}
-// every band < B maps to a scene of the set (the check of teb_amd_optimize_batch)
-int check_band_scenes(const teb_amd_handle* h, int B) {
-  for (int b = 0; b < B; ++b)
-    if (h->fleet.band_scene[b] >= h->fleet.n_scenes) {
-      char buf[160];
-      std::snprintf(buf, sizeof buf, "band %d maps to scene %d, but %d scenes are set (teb_amd_set_band_scenes)", b, h->fleet.band_scene[b], h->fleet.n_scenes);
-      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
-    }
-  return TEB_AMD_OK;
-}
-// the bands of every scene, in band order
-void bands_per_scene(const teb_amd_handle* h, int B, std::vector<std::vector<int>>& of) {
-  of.assign(h->fleet.n_scenes, {});
-  for (int b = 0; b < B; ++b) of[h->fleet.band_scene[b]].push_back(b);
-}
-// best[s] is a band of scene s or negative (best NULL: none)
-int check_best_per_scene(const teb_amd_handle* h, const int32_t* best, int B, const char* call) {
-  if (!best) return TEB_AMD_OK;
-  for (int s = 0; s < h->fleet.n_scenes; ++s)
-    if (best[s] >= 0 && (best[s] >= B || h->fleet.band_scene[best[s]] != s)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "%s: best[%d] = %d is not a band of scene %d", call, s, best[s], s);
-      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
-    }
-  return TEB_AMD_OK;
-}
-}  // namespace
 
 int teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler, double* values, int64_t capacity_values, int32_t* offset,
                                            int64_t* n_values) {
@@ -1996,29 +1984,15 @@ int teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler
   auto& F = h->fleet;
   const int B = h->B;
   if ((rc = check_band_scenes(h, B))) return rc;
-  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;   // homotopy_class_planner.hpp:50
-  int widest = 0;
-  for (const HostObst& t : F.tabs) widest = std::max(widest, (int)t.rows());
   std::vector<int> off(B + 1, 0);
-  for (int b = 0; b < B; ++b) off[b + 1] = off[b] + (mode == 3 ? (int)F.tabs[F.band_scene[b]].rows() : 2);
-  const size_t total = (size_t)off[B];
-  if (n_values) *n_values = (int64_t)total;
+  for (int b = 0; b < B; ++b) off[b + 1] = off[b] + (h->cfg.include_dynamic_obstacles ? (int)F.tabs[F.band_scene[b]].rows() : 2);
+  const int64_t total = off[B];
+  if (n_values) *n_values = total;
   if (offset) std::copy(off.begin(), off.end(), offset);
-  F.hsig_mode = 0;
-  BatchDev bt = batch_of(h);
-  FleetHsigDev fl;
-  fl.scenes = F.scenes.p; fl.scene_of = F.scene_of.p; fl.off = F.hs_off.p;
-  double* out = h->hsig.p;   // [max_tebs * max(max_obstacles, 2)]: scratch of the launch (the single scene's signatures live in hsig_host)
-  if (mode == 3 && total > 0) HIPCHK(hipMemcpyAsync(F.hs_off.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  if ((rc = launch_hsig_fleet(h, fl, bt, B, total, widest, prescaler, out))) return rc;
-  F.hsig_host.assign(std::max<size_t>(total, 1), 0.0);
-  if (total > 0) HIPCHK(hipMemcpyAsync(F.hsig_host.data(), out, total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));   // (off is read until here)
-  F.hsig_off = std::move(off);
-  F.hsig_mode = mode; F.hsig_B = B; F.hsig_prescaler = prescaler;
+  if ((rc = compute_signatures(h, F.sigs, true, std::move(off), prescaler))) return rc;
   if (!values) return TEB_AMD_OK;   // compute only: the signatures stay in the handle for the filter call
-  if (capacity_values < (int64_t)total) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_compute_h_signatures_per_scene: capacity_values is smaller than *n_values (the signatures are kept for the filter call)");
-  if (total > 0) std::memcpy(values, F.hsig_host.data(), total * sizeof(double));
+  if (capacity_values < total) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_compute_h_signatures_per_scene: capacity_values is smaller than *n_values (the signatures are kept for the filter call)");
+  std::copy(F.sigs.values.begin(), F.sigs.values.begin() + total, values);
   return TEB_AMD_OK;
 }
 
@@ -2028,16 +2002,10 @@ int teb_amd_filter_equivalence_classes_per_scene(teb_amd_handle_t* h, double thr
   if (rc) return rc;
   if ((rc = require_fleet_mode(h, "teb_amd_filter_equivalence_classes_per_scene"))) return rc;
   auto& F = h->fleet;
-  if (F.hsig_mode == 0 || F.hsig_B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures_per_scene first");
-  const int B = F.hsig_B, mode = F.hsig_mode;
-  if ((rc = check_best_per_scene(h, best, B, "teb_amd_filter_equivalence_classes_per_scene"))) return rc;
-  std::vector<const double*> row(B);
-  for (int b = 0; b < B; ++b) row[b] = F.hsig_host.data() + F.hsig_off[b];
-  std::vector<std::vector<int>> of;   // (every band < B is a band of one scene: check_band_scenes of the compute call)
-  bands_per_scene(h, B, of);
-  for (int s = 0; s < F.n_scenes; ++s)
-    filter_class_list(SignatureRule{mode, mode == 3 ? (int)F.tabs[s].rows() : 2, threshold}, max_number_plans_in_current_class, of[s],
-                      best ? best[s] : -1, row, F.memory[s], keep, valid, reasonable);
+  if (F.sigs.mode == 0 || F.sigs.B != h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "call teb_amd_compute_h_signatures_per_scene first");
+  BandGroups G;
+  if ((rc = scene_groups(h, h->B, G)) || (rc = check_best_per_scene(G, best, "teb_amd_filter_equivalence_classes_per_scene"))) return rc;
+  filter_class_lists(F.sigs, G, threshold, max_number_plans_in_current_class, best, F.memory.data(), keep, valid, reasonable);
   return TEB_AMD_OK;
 }
 
@@ -2317,33 +2285,20 @@ int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t*
   if ((rc = require_fleet_mode(h, "teb_amd_is_trajectory_feasible_per_scene"))) return rc;
   const int ns = h->fleet.n_scenes;
   if (h->cms.n != ns) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_is_trajectory_feasible_per_scene: needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
-  if (!bands || !feasible || nf < 1 || nf > kMaxFeasFootprint || !fx || !fy) return fail(TEB_AMD_ERR_INVALID_ARG, "bad bands / footprint / output");
-  if (!(inscribed_radius > 0) || !(min_res_angular > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "inscribed_radius and the angular resolution must be > 0");
+  if ((rc = check_feasibility_arguments(bands && feasible && nf >= 1 && nf <= kMaxFeasFootprint && fx && fy, "bad bands / footprint / output", inscribed_radius, min_res_angular))) return rc;
   for (int s = 0; s < ns; ++s)
     if (bands[s] >= 0 && (bands[s] >= h->B || h->fleet.band_scene[bands[s]] != s)) {
       char buf[200];
       std::snprintf(buf, sizeof buf, "teb_amd_is_trajectory_feasible_per_scene: bands[%d] = %d is not a band of scene %d", s, bands[s], s);
       return fail(TEB_AMD_ERR_INVALID_ARG, buf);
     }
-  if (h->stride > 1024) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check supports bands up to 1024 poses");
-  HIPCHK(ensure(h->cm_fp, 2 * (size_t)kMaxFeasFootprint));
-  HIPCHK(ensure(h->cm_out, 2 * (size_t)h->max_tebs + 1));
-  if (!h->cms_bands.p) HIPCHK(h->cms_bands.alloc((size_t)h->max_tebs));
-  // [feasible | first_infeasible] ns each, then the overflow flag: one download
-  int* ovf = h->cm_out.p + 2 * (size_t)ns;
-  HIPCHK(hipMemcpyAsync(h->cms_bands.p, bands, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->cm_fp.p, fx, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->cm_fp.p + kMaxFeasFootprint, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
-  LAUNCH(feasibility_fleet_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, h->cms_bands.p, h->cms.grids.p, nf,
-         h->cm_fp.p, h->cm_fp.p + kMaxFeasFootprint, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, h->cm_out.p,
-         h->cm_out.p + ns, ovf);
-  std::vector<int> out(2 * (size_t)ns + 1);
-  HIPCHK(hipMemcpyAsync(out.data(), h->cm_out.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipStreamSynchronize(h->stream));   // (the caller's bands and footprint are read until here)
-  if (out[2 * (size_t)ns]) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check: more than 2^22 interpolated samples requested (inscribed radius / angular resolution too small)");
-  for (int s = 0; s < ns; ++s) { feasible[s] = out[s]; if (first_infeasible) first_infeasible[s] = out[ns + s]; }
-  return TEB_AMD_OK;
+  return run_feasibility(h, ns, nf, fx, fy, feasible, first_infeasible, [&](double* px, double* py, int* fe, int* fi, int* ovf) {
+    if (!h->cms_bands.p) HIPCHK(h->cms_bands.alloc((size_t)h->max_tebs));
+    HIPCHK(hipMemcpyAsync(h->cms_bands.p, bands, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    LAUNCH(feasibility_fleet_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, h->cms_bands.p, h->cms.grids.p, nf,
+           px, py, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, fe, fi, ovf);
+    return (int)TEB_AMD_OK;
+  });
 }
 
 int teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_start, const double* new_goal, int32_t min_samples,
@@ -2367,8 +2322,7 @@ int teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_st
   HIPCHK(hipStreamSynchronize(h->stream));   // the upload reads msg; nothing waits for the kernel
   LAUNCH(prune_fleet_kernel, dim3(h->B), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), h->fleet.scene_of.p, h->prune_msg.p,
          (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples, h->has_vs.p, h->vs.p);
-  h->consumers_valid = false; h->nmax_known = -1;
-  h->signatures_stale();   // the bands change: the single scene's signatures and the per-scene signatures are stale
+  h->bands_changed();
   return TEB_AMD_OK;
 }
 
@@ -2724,7 +2678,7 @@ struct SingleRoute {
     return TEB_AMD_OK;
   }
   int signatures(std::vector<TickPlanner>&, const std::vector<int>& who, const std::vector<int>&) {
-    return launch_hsig(h, sc.cand, (int)who.size(), p->h_signature_prescaler, sc.sig);
+    return launch_signatures(h, nullptr, sc.cand, (int)who.size(), who.size() * (size_t)h->M, p->h_signature_prescaler, sc.sig);
   }
 };
 
@@ -2733,7 +2687,7 @@ struct FleetRoute {
   teb_amd_handle* h;
   const teb_amd_hcp_params_t* p;
   TickScratch sc;
-  int per_round, widest;   // paths per scene and round; most rows of a table of the set
+  int per_round;           // paths per scene and round
   std::vector<int> off;    // staging of plans() and lines(): read by the stream until the synchronisation after the signatures
   std::vector<double> px, py, pyaw;
   int plans(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // addAndInitNewTeb(*initial_plan_, ...) of every scene
@@ -2813,7 +2767,7 @@ struct FleetRoute {
     fl.scenes = F.scenes.p; fl.scene_of = F.ex_scene.p; fl.off = F.ex_soff.p;
     if (h->cfg.include_dynamic_obstacles && total > 0)
       HIPCHK(hipMemcpyAsync(F.ex_soff.p, soff.data(), soff.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    return launch_hsig_fleet(h, fl, sc.cand, (int)who.size(), total, widest, p->h_signature_prescaler, sc.sig);
+    return launch_signatures(h, &fl, sc.cand, (int)who.size(), total, p->h_signature_prescaler, sc.sig);
   }
 };
 
@@ -2960,7 +2914,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
   if (n_plan > 0 && (!plan_x || !plan_y || !plan_yaw)) return fail(TEB_AMD_ERR_INVALID_ARG, "null initial plan");
   if (initial_plan_teb) *initial_plan_teb = -1;
   if ((rc = ensure_candidate_buffers(h))) return rc;
-  const int M = h->M, mode = h->cfg.include_dynamic_obstacles ? 3 : 2, W = mode == 3 ? M : 2;
+  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2, W = mode == 3 ? h->M : 2;
   h->memory.forget_graph();
   if (n_vertices) *n_vertices = 0;
   if (n_paths) *n_paths = 0;
@@ -2974,14 +2928,14 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
   // equivalence_classes_ of the existing bands
   std::vector<const double*> rows;
   if (h->B > 0) {
-    const bool fresh = h->hsig_mode == mode && h->hsig_B == h->B && h->hsig_M == M && h->hsig_prescaler == p->h_signature_prescaler;
-    if (!fresh && (rc = teb_amd_compute_h_signatures(h, p->h_signature_prescaler, nullptr, nullptr))) return rc;   // else: renew just did
-    for (int b = 0; b < h->B; ++b) { rows.push_back(h->hsig_host.data() + (size_t)b * W); t.bands.push_back(b); }
+    if (!h->sigs.fresh(mode, h->B, p->h_signature_prescaler, (long long)h->B * W) &&   // else: renew just did
+        (rc = teb_amd_compute_h_signatures(h, p->h_signature_prescaler, nullptr, nullptr))) return rc;
+    rows = h->sigs.rows();
+    for (int b = 0; b < h->B; ++b) t.bands.push_back(b);
   }
   t.ct = seed_class_table(SignatureRule{mode, W, p->h_signature_threshold}, p->max_number_plans_in_current_class, rows,
                           best >= 0 && best < h->B ? rows[best] : nullptr, h->memory);
-  h->signatures_stale();   // the batch is about to change: signatures have to be recomputed before the next filter call
-  h->consumers_valid = false; h->nmax_known = -1;
+  h->bands_changed();   // the batch is about to change: signatures have to be recomputed before the next filter call
   SingleRoute R{h, p, {batch_of(h), h->cand_map.p, h->cand_off.p, h->cand_px.p, h->cand_py.p, h->cand_sig.p}, kCandChunk};
   BatchDev& c = R.sc.cand;   // the scratch strips seen as a batch of kCandChunk bands
   c.B = kCandChunk; c.n = h->cand_n.p; c.x = h->cand_x.p; c.y = h->cand_y.p; c.th = h->cand_th.p; c.dt = h->cand_dt.p;
@@ -3016,10 +2970,9 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
     if (np > h->stride + 1) return fail(TEB_AMD_ERR_CAPACITY, "plan / path longer than max_poses + 1");
     plan_off[s + 1] = plan_off[s] + np;
   }
-  if ((rc = check_band_scenes(h, B0))) return rc;
-  if ((rc = check_best_per_scene(h, best, B0, "teb_amd_explore_candidates_per_scene"))) return rc;
-  std::vector<std::vector<int>> of;   // the bands of every scene in band order
-  bands_per_scene(h, B0, of);
+  BandGroups G;   // the bands of every scene in band order
+  if ((rc = scene_groups(h, B0, G)) || (rc = check_best_per_scene(G, best, "teb_amd_explore_candidates_per_scene"))) return rc;
+  std::vector<std::vector<int>>& of = G.of;
   const int slots = p->max_number_classes;   // per scene (the reference handle of the contract has max_tebs >= max_number_classes)
   {
     long long need = 0;
@@ -3046,8 +2999,8 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
   if (n_total) *n_total = B0;
   // equivalence_classes_ of the existing bands, one table per scene
   if (B0 > 0) {
-    const bool fresh = F.hsig_mode == mode && F.hsig_B == B0 && F.hsig_prescaler == p->h_signature_prescaler;
-    if (!fresh && (rc = teb_amd_compute_h_signatures_per_scene(h, p->h_signature_prescaler, nullptr, 0, nullptr, nullptr))) return rc;
+    if (!F.sigs.fresh(mode, B0, p->h_signature_prescaler) &&
+        (rc = teb_amd_compute_h_signatures_per_scene(h, p->h_signature_prescaler, nullptr, 0, nullptr, nullptr))) return rc;
   }
   std::vector<TickPlanner> P(ns);
   for (int s = 0; s < ns; ++s) {
@@ -3062,14 +3015,13 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
     t.n_vertices = n_vertices ? n_vertices + s : nullptr; t.n_paths = n_paths ? n_paths + s : nullptr;
     t.initial_plan_teb = initial_plan_teb ? initial_plan_teb + s : nullptr;
     std::vector<const double*> rows;
-    for (int b : of[s]) rows.push_back(F.hsig_host.data() + F.hsig_off[b]);
+    for (int b : of[s]) rows.push_back(F.sigs.row(b));
     t.ct = seed_class_table(SignatureRule{mode, mode == 3 ? (int)F.tabs[s].rows() : 2, p->h_signature_threshold}, p->max_number_plans_in_current_class,
-                            rows, best && best[s] >= 0 ? F.hsig_host.data() + F.hsig_off[best[s]] : nullptr, F.memory[s]);
+                            rows, best && best[s] >= 0 ? F.sigs.row(best[s]) : nullptr, F.memory[s]);
     t.bands = std::move(of[s]);
   }
-  h->signatures_stale();   // the batch is about to change
-  h->consumers_valid = false; h->nmax_known = -1;
-  FleetRoute R{h, p, {batch_of(h), F.ex_map.p, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_sig.p}, q, widest, {}, {}, {}, {}};
+  h->bands_changed();   // the batch is about to change
+  FleetRoute R{h, p, {batch_of(h), F.ex_map.p, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_sig.p}, q, {}, {}, {}, {}};
   BatchDev& c = R.sc.cand;   // the scratch strips of the scene set seen as a batch of K bands
   c.B = (int)K; c.n = F.ex_n.p; c.x = F.ex_x.p; c.y = F.ex_y.p; c.th = F.ex_th.p; c.dt = F.ex_dt.p;
   rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths);
@@ -3124,16 +3076,9 @@ int compact_by_map(teb_amd_handle* h, const std::vector<int>& map) {
     LAUNCH(move_bands_kernel, dim3(K), dim3(kThreads), 0, h->stream, tmp, src, h->cand_map.p, 0, 1);
     HIPCHK(hipStreamSynchronize(h->stream));
   }
-  if (h->hsig_mode != 0 && h->hsig_B == B) {   // the kept bands' signatures stay valid: same rows, new order
-    const int W = h->hsig_mode == 3 ? h->hsig_M : 2;
-    std::vector<double> moved((size_t)K * (W > 0 ? W : 1), 0.0);
-    for (int k = 0; k < K; ++k) std::copy(h->hsig_host.begin() + (size_t)map[k] * W, h->hsig_host.begin() + (size_t)(map[k] + 1) * W, moved.begin() + (size_t)k * W);
-    h->hsig_host.swap(moved);
-    h->hsig_B = K;
-  } else {
-    h->signatures_stale();
-  }
-  h->fleet.hsig_mode = 0;   // the per-scene signatures are computed again after a compaction (band offsets and the map move)
+  // the single scene's signatures travel with their bands (same rows, new order); the scene set's are computed again
+  if (h->sigs.mode != 0 && h->sigs.B == B) h->sigs.gather(map); else h->sigs.clear();
+  h->fleet.sigs.clear();
   if (!h->fleet.band_scene.empty()) {   // the band -> scene map (teb_amd_set_band_scenes) travels with the bands; the freed slots: scene 0
     auto& F = h->fleet;
     std::vector<int> moved(F.band_scene.size(), 0);
@@ -3147,60 +3092,21 @@ int compact_by_map(teb_amd_handle* h, const std::vector<int>& map) {
     }
   }
   h->B = K;
-  h->consumers_valid = false; h->nmax_known = -1;
-  return TEB_AMD_OK;
-}
-}  // namespace
-
-int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best, int32_t* n_kept, int32_t* new_best) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if (!keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null keep");
-  const int B = h->B;
-  if (new_best) *new_best = -1;
-  if (n_kept) *n_kept = 0;
-  if (B <= 0) return TEB_AMD_OK;
-  std::vector<int> order(B), map;
-  for (int b = 0; b < B; ++b) order[b] = b;
-  const bool has_best = best >= 0 && best < B;
-  if (has_best) std::swap(order[0], order[best]);   // std::iter_swap(tebs_.begin(), it_best_teb)
-  for (int k = 0; k < B; ++k) if (keep[order[k]]) map.push_back(order[k]);
-  if ((rc = compact_by_map(h, map))) return rc;
-  if (has_best && keep[best] && new_best) *new_best = 0;
-  if (n_kept) *n_kept = (int)map.size();
+  h->bands_changed(-1, false);
   return TEB_AMD_OK;
 }
 
-int teb_amd_compact_bands_per_scene(teb_amd_handle_t* h, const int32_t* keep, const int32_t* best, int32_t* n_kept, int32_t* new_best) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if ((rc = require_fleet_mode(h, "teb_amd_compact_bands_per_scene"))) return rc;
-  if (!keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null keep");
-  const int B = h->B, ns = h->fleet.n_scenes;
-  if (new_best) std::fill(new_best, new_best + ns, -1);
-  if (n_kept) *n_kept = 0;
-  if (B <= 0) return TEB_AMD_OK;
-  if ((rc = check_band_scenes(h, B))) return rc;
-  if ((rc = check_best_per_scene(h, best, B, "teb_amd_compact_bands_per_scene"))) return rc;
-  // the gather map: std::iter_swap(tebs_.begin(), it_best_teb) inside every scene, then the kept bands in the resulting order
-  std::vector<int> order(B), first(ns, -1), map;
-  for (int b = 0; b < B; ++b) { order[b] = b; if (first[h->fleet.band_scene[b]] < 0) first[h->fleet.band_scene[b]] = b; }
-  if (best)
-    for (int s = 0; s < ns; ++s) if (best[s] >= 0) std::swap(order[first[s]], order[best[s]]);
-  std::vector<int> nb(ns, -1);
-  for (int k = 0; k < B; ++k)
-    if (keep[order[k]]) {
-      const int b = order[k], s = h->fleet.band_scene[b];
-      if (best && best[s] == b) nb[s] = (int)map.size();
-      map.push_back(b);
-    }
-  if ((rc = compact_by_map(h, map))) return rc;
+// The erase of the dropped bands of the planners G (compaction_map of teb_hcp_host.hpp): best and new_best [groups] or NULL
+int compact_groups(teb_amd_handle* h, const BandGroups& G, const int32_t* keep, const int32_t* best, int32_t* n_kept, int32_t* new_best) {
+  std::vector<int> map;
+  std::vector<int32_t> nb(G.size());
+  compaction_map(G, keep, best, map, nb.data());
+  if (int rc = compact_by_map(h, map)) return rc;
   if (new_best) std::copy(nb.begin(), nb.end(), new_best);
   if (n_kept) *n_kept = (int)map.size();
   return TEB_AMD_OK;
 }
 
-namespace {
 // detour_stats_kernel over all B bands: st [4 * B], opt [B]
 int detour_statistics(teb_amd_handle* h, const teb_amd_hcp_params_t* p, int B, std::vector<double>& st, std::vector<int>& opt) {
   if (int rc = ensure_candidate_buffers(h)) return rc;
@@ -3211,23 +3117,51 @@ int detour_statistics(teb_amd_handle* h, const teb_amd_hcp_params_t* p, int B, s
   HIPCHK(hipMemcpyAsync(opt.data(), h->optimized.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return synced(h);
 }
+
+// deletePlansDetouringBackwards of the planners G, best [groups]: one launch over all bands if any planner is past its early-out
+int filter_detours(teb_amd_handle* h, const teb_amd_hcp_params_t* p, const BandGroups& G, const int32_t* best, int32_t* keep) {
+  std::vector<int> runs;
+  for (int g = 0; g < G.size(); ++g)
+    if (detour_rule_runs(G.of[g], best[g], keep)) runs.push_back(g);
+  if (runs.empty()) return TEB_AMD_OK;
+  std::vector<double> st;
+  std::vector<int> opt;
+  if (int rc = detour_statistics(h, p, G.B, st, opt)) return rc;
+  for (int g : runs) apply_detour_rule(G.of[g], best[g], p, st.data(), opt.data(), keep);
+  return TEB_AMD_OK;
+}
 }  // namespace
+
+int teb_amd_compact_bands(teb_amd_handle_t* h, const int32_t* keep, int32_t best, int32_t* n_kept, int32_t* new_best) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if (!keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null keep");
+  if (new_best) *new_best = -1;
+  if (n_kept) *n_kept = 0;
+  if (h->B <= 0) return TEB_AMD_OK;
+  return compact_groups(h, BandGroups(1, h->B, nullptr), keep, &best, n_kept, new_best);   // (a best that is no band: none, not refused)
+}
+
+int teb_amd_compact_bands_per_scene(teb_amd_handle_t* h, const int32_t* keep, const int32_t* best, int32_t* n_kept, int32_t* new_best) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_compact_bands_per_scene"))) return rc;
+  if (!keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null keep");
+  if (new_best) std::fill(new_best, new_best + h->fleet.n_scenes, -1);
+  if (n_kept) *n_kept = 0;
+  if (h->B <= 0) return TEB_AMD_OK;
+  BandGroups G;
+  if ((rc = scene_groups(h, h->B, G)) || (rc = check_best_per_scene(G, best, "teb_amd_compact_bands_per_scene"))) return rc;
+  return compact_groups(h, G, keep, best, n_kept, new_best);
+}
 
 int teb_amd_filter_detours(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, int32_t best, int32_t* keep) {
   int rc = check_handle(h);
   if (rc) return rc;
   if ((rc = refuse_in_fleet_mode(h, "teb_amd_filter_detours"))) return rc;
   if (!p || !keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
-  const int B = h->B;
-  if (B <= 0) return TEB_AMD_OK;
-  std::vector<int> order(B);
-  for (int b = 0; b < B; ++b) order[b] = b;
-  if (!detour_rule_runs(order, best, keep)) return TEB_AMD_OK;
-  std::vector<double> st;
-  std::vector<int> opt;
-  if ((rc = detour_statistics(h, p, B, st, opt))) return rc;
-  apply_detour_rule(order, best, p, st.data(), opt.data(), keep);
-  return TEB_AMD_OK;
+  if (h->B <= 0) return TEB_AMD_OK;
+  return filter_detours(h, p, BandGroups(1, h->B, nullptr), &best, keep);
 }
 
 int teb_amd_filter_detours_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const int32_t* best, int32_t* keep) {
@@ -3235,21 +3169,10 @@ int teb_amd_filter_detours_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_para
   if (rc) return rc;
   if ((rc = require_fleet_mode(h, "teb_amd_filter_detours_per_scene"))) return rc;
   if (!p || !keep) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
-  const int B = h->B;
-  if (B <= 0) return TEB_AMD_OK;
-  if ((rc = check_band_scenes(h, B))) return rc;
-  if ((rc = check_best_per_scene(h, best, B, "teb_amd_filter_detours_per_scene"))) return rc;
-  std::vector<std::vector<int>> of;
-  bands_per_scene(h, B, of);
-  std::vector<int> runs;   // the scenes past their own early-out
-  for (int s = 0; s < h->fleet.n_scenes; ++s)
-    if (best && detour_rule_runs(of[s], best[s], keep)) runs.push_back(s);
-  if (runs.empty()) return TEB_AMD_OK;
-  std::vector<double> st;
-  std::vector<int> opt;
-  if ((rc = detour_statistics(h, p, B, st, opt))) return rc;   // one launch over all bands
-  for (int s : runs) apply_detour_rule(of[s], best[s], p, st.data(), opt.data(), keep);
-  return TEB_AMD_OK;
+  if (h->B <= 0) return TEB_AMD_OK;
+  BandGroups G;
+  if ((rc = scene_groups(h, h->B, G)) || (rc = check_best_per_scene(G, best, "teb_amd_filter_detours_per_scene"))) return rc;
+  return best ? filter_detours(h, p, G, best, keep) : (int)TEB_AMD_OK;   // without best bands no planner's rule runs
 }
 
 int teb_amd_set_optimized_flags(teb_amd_handle_t* h, const int32_t* flags) {
@@ -3287,9 +3210,8 @@ int teb_amd_device_state(teb_amd_handle_t* h, void** x, void** y, void** theta, 
   if (rc) return rc;
   if (x) *x = h->x.p; if (y) *y = h->y.p; if (theta) *theta = h->th.p; if (dt) *dt = h->dt.p; if (n) *n = h->n.p;
   if (stride) *stride = h->stride;
-  h->nmax_known = -1;        // the caller may write pose counts through `n`: the host's upper bound is void from here on (the kernel guards
-  h->consumers_valid = false;   // itself against counts beyond its LDS strips as well)
-  h->signatures_stale();
+  h->bands_changed();   // the caller may write pose counts through `n`: the host's upper bound is void from here on (the kernel guards
+                        // itself against counts beyond its LDS strips as well)
   return TEB_AMD_OK;
 }
 
@@ -3308,8 +3230,7 @@ int teb_amd_restore_state(teb_amd_handle_t* h) {
   if ((rc = copy_strips(h, h->live(), h->snapshot(), h->max_tebs))) return rc;
   // snap_nmax bounded the first snap_B bands only; the copy brings back the counts of ALL max_tebs slots, so with another batch size the
   // bound says nothing about the bands beyond the old B
-  h->consumers_valid = false; h->nmax_known = (h->B == h->snap_B) ? h->snap_nmax : -1;
-  h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
+  h->bands_changed(h->B == h->snap_B ? h->snap_nmax : -1);
   return TEB_AMD_OK;
 }
 

@@ -306,4 +306,83 @@ inline void apply_detour_rule(const std::vector<int>& order, int best, const teb
   }
 }
 
+// The signatures of the B bands of a handle as the compute calls leave them: band b holds values [off[b], off[b + 1]). A table of
+// fixed width W (the single scene) is the offset form with off[b] = b * W; the bands of a scene set have the widths of their scenes.
+struct SignatureSet {
+  int mode = 0, B = 0;   // mode 0 = no valid signatures, 2 / 3 = HSignature / HSignature3d
+  double prescaler = 0;  // h_signature_prescaler of those signatures
+  std::vector<int> off;  // [B + 1]
+  std::vector<double> values;
+  static std::vector<int> fixed_width(int B, int W) { std::vector<int> o(B + 1); for (int b = 0; b <= B; ++b) o[b] = b * W; return o; }
+  const double* row(int b) const { return values.data() + off[b]; }
+  int width(int b) const { return off[b + 1] - off[b]; }
+  std::vector<const double*> rows() const { std::vector<const double*> r(B); for (int b = 0; b < B; ++b) r[b] = row(b); return r; }
+  void clear() { mode = 0; B = 0; off.clear(); values.clear(); }
+  // The two halves of a compute call: room for the values at the given offsets (never empty, so that row() of a set without values
+  // is a pointer), not valid before stamp() says of what the downloaded values are
+  double* reserve(std::vector<int> offsets) { clear(); off = std::move(offsets); values.assign(std::max(off.back(), 1), 0.0); return values.data(); }
+  void stamp(int mode_, double prescaler_) { mode = mode_; B = (int)off.size() - 1; prescaler = prescaler_; }
+  // Are these the signatures of B_ bands in mode mode_ at that prescaler? n_values >= 0: and that many values in all (the single scene:
+  // B * W, which in mode 3 is the row count of the table they were computed against)
+  bool fresh(int mode_, int B_, double prescaler_, long long n_values = -1) const {
+    return mode != 0 && mode == mode_ && B == B_ && prescaler == prescaler_ && (n_values < 0 || off.back() == n_values);
+  }
+  void gather(const std::vector<int>& map) {   // band k becomes the former band map[k]
+    std::vector<int> o(1, 0);
+    std::vector<double> v;
+    for (int b : map) { v.insert(v.end(), row(b), row(b) + width(b)); o.push_back((int)v.size()); }
+    if (v.empty()) v.assign(1, 0.0);
+    off.swap(o); values.swap(v); B = (int)map.size();
+  }
+};
+
+// The hsig3d launch rule: one lane per (band, obstacle) when the values fill the chip, otherwise lanes over (obstacle, segment) - same
+// bits, lower latency. option: teb_amd_options_t::hsig3d_kernel, which pins one of the two kernels (tests, tools/hsig_bench.py).
+inline bool hsig3d_wide(int option, long long n_values) {
+  return option == TEB_AMD_HSIG3D_WIDE || (option != TEB_AMD_HSIG3D_SMALL && n_values >= 32768);
+}
+
+// The planners of a handle and their bands: the bands 0 .. B - 1 in groups, one per planner. group_of NULL: one group of all bands (the
+// single scene); else band b belongs to group group_of[b] < n_groups (a scene set: band -> scene).
+struct BandGroups {
+  int B = 0;
+  std::vector<std::vector<int>> of;   // the bands of every group, in band order
+  BandGroups() = default;
+  BandGroups(int n_groups, int B_, const int* group_of) : B(B_), of(n_groups) {
+    for (int b = 0; b < B; ++b) of[group_of ? group_of[b] : 0].push_back(b);
+  }
+  int size() const { return (int)of.size(); }
+  int first(int g) const { return of[g].empty() ? -1 : of[g].front(); }
+  bool has(int g, int b) const { return std::binary_search(of[g].begin(), of[g].end(), b); }
+};
+
+// The class list of renewAndAnalyzeOldTebs for every planner (filter_class_list): memory [groups], best [groups] or NULL for none
+inline void filter_class_lists(const SignatureSet& S, const BandGroups& G, double threshold, int max_number_plans_in_current_class, const int32_t* best,
+                               PlannerMemory* memory, int32_t* kp, int32_t* vld, int32_t* rsn) {
+  const std::vector<const double*> row = S.rows();
+  for (int g = 0; g < G.size(); ++g)   // (a planner without bands: its width is not looked at)
+    filter_class_list(SignatureRule{S.mode, G.of[g].empty() ? 0 : S.width(G.first(g)), threshold}, max_number_plans_in_current_class, G.of[g],
+                      best ? best[g] : -1, row, memory[g], kp, vld, rsn);
+}
+
+// The erase of the dropped bands with the order renewAndAnalyzeOldTebs leaves: std::iter_swap(tebs_.begin(), it_best_teb) inside every
+// planner's bands (best [groups] or NULL; a best[g] that is no band of group g is none), then the kept bands in the resulting order.
+// map: the former index of every new band. new_best [groups] or NULL: the new index of every kept best band, else -1.
+inline void compaction_map(const BandGroups& G, const int32_t* keep, const int32_t* best, std::vector<int>& map, int32_t* new_best) {
+  std::vector<int> order(G.B), group(G.B, 0);
+  for (int g = 0; g < G.size(); ++g) for (int b : G.of[g]) group[b] = g;
+  for (int b = 0; b < G.B; ++b) order[b] = b;
+  auto is_best = [&](int b) { return best && best[group[b]] == b; };
+  for (int g = 0; g < G.size(); ++g) {
+    if (new_best) new_best[g] = -1;
+    if (best && G.has(g, best[g])) std::swap(order[G.first(g)], order[best[g]]);
+  }
+  map.clear();
+  for (int b : order) {
+    if (!keep[b]) continue;
+    if (new_best && is_best(b)) new_best[group[b]] = (int)map.size();
+    map.push_back(b);
+  }
+}
+
 }  // namespace tebamd

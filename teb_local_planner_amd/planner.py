@@ -1275,6 +1275,18 @@ class FleetHomotopyClassPlanner:
         """band indices of robot r, in band order"""
         return [int(b) for b in np.nonzero(self.solver.band_scenes() == r)[0]] if self.solver.count else []
 
+    def _drop_bands(self, keep, best_only=False):
+        """The bands with keep == 0 leave the batch, the kept ones move to the front in order: best_teb_, initial_plan_teb_ and
+        _last_best_teb follow them (best_only: best_teb_ alone - updateAllTEBs, which leaves the other two as they are)."""
+        if keep.all():
+            return
+        at = (np.cumsum(keep) - 1).astype(np.int32)
+        move = lambda a: np.array([at[b] if b >= 0 else -1 for b in a], np.int32)
+        self.best_teb_ = move(self.best_teb_)
+        if not best_only:
+            self.initial_plan_teb_, self._last_best_teb = move(self.initial_plan_teb_), move(self._last_best_teb)
+        self.solver.compact_bands_per_scene(keep, None)
+
     # ---- updateAllTEBs (src/homotopy_class_planner.cpp:539-562) of every robot ---------------------------------------------------------
     def updateAllTEBs(self, starts, goals, start_vels=None):
         import math
@@ -1290,10 +1302,7 @@ class FleetHomotopyClassPlanner:
                 if d >= t.force_reinit_new_goal_dist or a >= t.force_reinit_new_goal_angular:
                     keep[scene_of == r] = 0                       # tebs_.clear() of that robot only
                     self.best_teb_[r] = -1
-            if not keep.all():
-                at = np.cumsum(keep) - 1                          # the other robots' bands keep their order
-                self.best_teb_ = np.array([at[b] if b >= 0 else -1 for b in self.best_teb_], np.int32)
-                s.compact_bands_per_scene(keep, None)
+            self._drop_bands(keep, best_only=True)                # the other robots' bands keep their order
         if s.count > 0:                                           # every band of every robot, one launch
             sv = hv = None
             if start_vels is not None and any(v is not None for v in start_vels):
@@ -1449,11 +1458,7 @@ class FleetHomotopyClassPlanner:
                 if self.initial_plan_teb_[r] == best:
                     self.initial_plan_teb_[r] = -1
                 self.best_teb_[r] = -1
-            if not keep.all():
-                at = (np.cumsum(keep) - 1).astype(np.int32)        # the kept bands move to the front in order
-                move = lambda a: np.array([at[b] if b >= 0 else -1 for b in a], np.int32)
-                self.best_teb_, self.initial_plan_teb_, self._last_best_teb = move(self.best_teb_), move(self.initial_plan_teb_), move(self._last_best_teb)
-                s.compact_bands_per_scene(keep, None)
+            self._drop_bands(keep)
         return [bool(v) for v in verdict]
 
     def hasDiverged(self):
@@ -1494,13 +1499,7 @@ class FleetHomotopyClassPlanner:
             self._goal[k] = None
         if s.count == 0 or not rs:
             return
-        keep = (~np.isin(s.band_scenes(), rs)).astype(np.int32)
-        if keep.all():
-            return
-        at = (np.cumsum(keep) - 1).astype(np.int32)
-        move = lambda a: np.array([at[b] if b >= 0 else -1 for b in a], np.int32)
-        self.best_teb_, self.initial_plan_teb_, self._last_best_teb = move(self.best_teb_), move(self.initial_plan_teb_), move(self._last_best_teb)
-        s.compact_bands_per_scene(keep, None)
+        self._drop_bands((~np.isin(s.band_scenes(), rs)).astype(np.int32))
 
     def setPlans(self, plans, robots=None):
         """setPlan of every robot: plans[r] = (x, y, yaw) arrays in the plan frame (None: no plan), resident on the device from here on.

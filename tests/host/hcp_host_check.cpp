@@ -280,7 +280,166 @@ static void check_detour_rule() {
   CHECK(keep[0] == 1 && keep[1] == 1 && keep[2] == 0 && keep[3] == 0 && keep[4] == 0);
 }
 
+typedef std::vector<double> Row;
+static Row row_of(const SignatureSet& s, int b) { return Row(s.row(b), s.row(b) + s.width(b)); }
+
+static void check_signature_set() {
+  {   // fixed width 2: off[b] = 2 b
+    SignatureSet s;
+    CHECK(s.mode == 0 && !s.fresh(2, 0, 0.0));
+    CHECK((SignatureSet::fixed_width(3, 2) == std::vector<int>{0, 2, 4, 6}));
+    double* v = s.reserve(SignatureSet::fixed_width(3, 2));
+    CHECK(s.mode == 0 && s.values.size() == 6);   // not valid before the stamp
+    for (int k = 0; k < 6; ++k) v[k] = 10 + k;
+    s.stamp(2, 0.5);
+    CHECK(s.mode == 2 && s.B == 3 && s.width(1) == 2 && (row_of(s, 1) == Row{12, 13}) && s.rows().size() == 3 && s.rows()[2] == s.row(2));
+    // fresh: every field that can differ
+    CHECK(s.fresh(2, 3, 0.5) && s.fresh(2, 3, 0.5, 6));
+    CHECK(!s.fresh(3, 3, 0.5) && !s.fresh(2, 4, 0.5) && !s.fresh(2, 3, 0.25) && !s.fresh(2, 3, 0.5, 9));
+    s.gather({2, 0, 1});   // a permutation
+    CHECK(s.B == 3 && (s.off == std::vector<int>{0, 2, 4, 6}) && (s.values == Row{14, 15, 10, 11, 12, 13}) && s.fresh(2, 3, 0.5, 6));
+    s.gather({1});         // a drop
+    CHECK(s.B == 1 && (s.off == std::vector<int>{0, 2}) && (row_of(s, 0) == Row{10, 11}) && s.fresh(2, 1, 0.5, 2) && !s.fresh(2, 3, 0.5));
+    s.gather({});          // an empty map
+    CHECK(s.B == 0 && (s.off == std::vector<int>{0}) && s.mode == 2 && s.fresh(2, 0, 0.5, 0));
+    s.clear();
+    CHECK(s.mode == 0 && s.B == 0 && s.off.empty() && !s.fresh(2, 0, 0.5));
+  }
+  {   // ragged: bands of scenes with 3, 0 and 1 obstacles (3-D)
+    SignatureSet s;
+    double* v = s.reserve({0, 3, 3, 4, 7});
+    for (int k = 0; k < 7; ++k) v[k] = k;
+    s.stamp(3, 1.0);
+    CHECK(s.B == 4 && s.width(0) == 3 && s.width(1) == 0 && s.width(2) == 1 && (row_of(s, 2) == Row{3}) && (row_of(s, 3) == Row{4, 5, 6}));
+    CHECK(s.fresh(3, 4, 1.0) && s.fresh(3, 4, 1.0, 7) && !s.fresh(2, 4, 1.0));
+    s.gather({3, 1, 0});   // a permutation with a drop
+    CHECK(s.B == 3 && (s.off == std::vector<int>{0, 3, 3, 6}) && (s.values == Row{4, 5, 6, 0, 1, 2}));
+    s.gather({1});         // only the band without values is left
+    CHECK(s.B == 1 && s.width(0) == 0 && s.row(0) != nullptr);
+  }
+  {   // width 0: 3-D signatures without obstacles - no values, rows that are pointers all the same
+    SignatureSet s;
+    s.reserve(SignatureSet::fixed_width(2, 0));
+    s.stamp(3, 1.0);
+    CHECK(s.B == 2 && s.width(0) == 0 && s.width(1) == 0 && s.row(1) != nullptr && s.fresh(3, 2, 1.0, 0));
+    s.gather({1, 0});
+    CHECK(s.B == 2 && (s.off == std::vector<int>{0, 0, 0}) && s.row(0) != nullptr);
+  }
+  // the hsig3d launch rule: the option pins a kernel, otherwise 32768 values fill the chip
+  CHECK(hsig3d_wide(TEB_AMD_HSIG3D_AUTO, 32768) && !hsig3d_wide(TEB_AMD_HSIG3D_AUTO, 32767));
+  CHECK(hsig3d_wide(TEB_AMD_HSIG3D_WIDE, 1) && !hsig3d_wide(TEB_AMD_HSIG3D_SMALL, 1 << 20));
+}
+
+static void check_band_groups() {
+  {   // the single scene: one group of all bands
+    const BandGroups g(1, 3, nullptr);
+    CHECK(g.size() == 1 && g.B == 3 && (g.of[0] == std::vector<int>{0, 1, 2}) && g.first(0) == 0);
+    CHECK(g.has(0, 0) && g.has(0, 2) && !g.has(0, 3) && !g.has(0, -1));
+  }
+  {   // three interleaved scenes, scene 1 without bands
+    const int scene_of[5] = {2, 0, 2, 0, 2};
+    const BandGroups g(3, 5, scene_of);
+    CHECK(g.size() == 3 && (g.of[0] == std::vector<int>{1, 3}) && g.of[1].empty() && (g.of[2] == std::vector<int>{0, 2, 4}));
+    CHECK(g.first(0) == 1 && g.first(1) == -1 && g.first(2) == 0);
+    CHECK(g.has(0, 3) && !g.has(0, 2) && !g.has(1, 0) && !g.has(1, -1) && g.has(2, 4) && !g.has(2, 5));
+  }
+  CHECK(BandGroups(1, 0, nullptr).first(0) == -1);
+}
+
+static void check_filter_class_lists() {   // two planners over one ragged set: each sees its own bands, rows and memory
+  SignatureSet s;
+  const double v[8] = {1, 0, 3, 0, 1.125, 0, 3.125, 0};   // A, B, A1, B1
+  std::copy(v, v + 8, s.reserve(SignatureSet::fixed_width(4, 2)));
+  s.stamp(2, 1.0);
+  const int scene_of[4] = {0, 1, 0, 1};
+  const BandGroups g(2, 4, scene_of);
+  PlannerMemory mem[2];
+  int32_t kp[4], vld[4], rsn[4];
+  const int32_t best[2] = {2, -1};
+  filter_class_lists(s, g, 0.25, 1, best, mem, kp, vld, rsn);   // scene 0: band 2 first, band 0 its duplicate; scene 1: band 1, then its duplicate
+  CHECK(kp[0] == 0 && kp[1] == 1 && kp[2] == 1 && kp[3] == 0 && vld[0] && vld[3] && rsn[1]);
+  CHECK(mem[0].best_class_mode == 2 && (mem[0].best_class == Row{1.125, 0}) && mem[1].best_class_mode == 0);
+  filter_class_lists(s, BandGroups(1, 4, nullptr), 0.25, 1, nullptr, mem, kp, vld, rsn);   // one planner: A, B kept; mem[0] still holds class A
+  CHECK(kp[0] == 1 && kp[1] == 1 && kp[2] == 0 && kp[3] == 0);
+}
+
+// teb_amd_compact_bands as it stood before compaction_map, the single scene's loop
+static void old_single_compaction(int B, const int32_t* keep, int best, std::vector<int>& map, int& new_best) {
+  std::vector<int> order(B);
+  for (int b = 0; b < B; ++b) order[b] = b;
+  const bool has_best = best >= 0 && best < B;
+  if (has_best) std::swap(order[0], order[best]);
+  map.clear();
+  for (int k = 0; k < B; ++k) if (keep[order[k]]) map.push_back(order[k]);
+  new_best = has_best && keep[best] ? 0 : -1;
+}
+
+static void check_compaction_map() {
+  typedef std::vector<int> V;
+  V map;
+  int32_t nb[3];
+  {   // one group of four bands
+    const BandGroups g(1, 4, nullptr);
+    const int32_t all[4] = {1, 1, 1, 1}, some[4] = {1, 0, 1, 1}, none[4] = {0, 0, 0, 0};
+    int32_t best = 0;
+    compaction_map(g, all, &best, map, nb);
+    CHECK((map == V{0, 1, 2, 3}) && nb[0] == 0);              // best = 0: nothing moves
+    best = 3;
+    compaction_map(g, all, &best, map, nb);
+    CHECK((map == V{3, 1, 2, 0}) && nb[0] == 0);              // best = the last band: swapped with the first
+    compaction_map(g, some, &best, map, nb);
+    CHECK((map == V{3, 2, 0}) && nb[0] == 0);                 // ... kept
+    best = 1;
+    compaction_map(g, some, &best, map, nb);
+    CHECK((map == V{0, 2, 3}) && nb[0] == -1);                // best not kept: the swap still happened (1 <-> 0), no new best
+    best = 4;
+    compaction_map(g, some, &best, map, nb);
+    CHECK((map == V{0, 2, 3}) && nb[0] == -1);                // out of range: none
+    best = -1;
+    compaction_map(g, all, &best, map, nullptr);
+    CHECK((map == V{0, 1, 2, 3}));
+    compaction_map(g, all, nullptr, map, nb);
+    CHECK((map == V{0, 1, 2, 3}) && nb[0] == -1);             // all kept, no best
+    best = 2;
+    compaction_map(g, none, &best, map, nb);
+    CHECK(map.empty() && nb[0] == -1);                        // none kept
+  }
+  {   // three interleaved groups: scene 0 = {1, 3}, scene 1 empty, scene 2 = {0, 2, 4, 5}; best bands 3 and 4, band 4 dropped
+    const int scene_of[6] = {2, 0, 2, 0, 2, 2};
+    const BandGroups g(3, 6, scene_of);
+    const int32_t keep[6] = {1, 1, 0, 1, 0, 1}, best[3] = {3, -1, 4};
+    compaction_map(g, keep, best, map, nb);   // order after the swaps 1 <-> 3 and 0 <-> 4: 4 3 2 1 0 5
+    CHECK((map == V{3, 1, 0, 5}) && nb[0] == 0 && nb[1] == -1 && nb[2] == -1);
+    const int32_t all[6] = {1, 1, 1, 1, 1, 1}, none[6] = {0, 0, 0, 0, 0, 0};
+    compaction_map(g, all, best, map, nb);
+    CHECK((map == V{4, 3, 2, 1, 0, 5}) && nb[0] == 1 && nb[1] == -1 && nb[2] == 0);
+    const int32_t foreign[3] = {0, 1, 3};     // bands of other groups: none
+    compaction_map(g, all, foreign, map, nb);
+    CHECK((map == V{0, 1, 2, 3, 4, 5}) && nb[0] == -1 && nb[1] == -1 && nb[2] == -1);
+    compaction_map(g, none, best, map, nb);
+    CHECK(map.empty() && nb[0] == -1 && nb[2] == -1);
+  }
+  {   // one group against the single scene's former loop, 200 seeded keep / best draws
+    std::mt19937 rnd(7);
+    for (int draw = 0; draw < 200; ++draw) {
+      const int B = 1 + (int)(rnd() % 8);
+      int32_t keep[8];
+      for (int b = 0; b < B; ++b) keep[b] = rnd() % 3 != 0;
+      const int32_t best = (int)(rnd() % (B + 4)) - 2;   // -2 .. B + 1: out of range on both sides too
+      V old_map;
+      int old_best;
+      old_single_compaction(B, keep, best, old_map, old_best);
+      compaction_map(BandGroups(1, B, nullptr), keep, &best, map, nb);
+      CHECK(map == old_map && nb[0] == old_best);
+    }
+  }
+}
+
 int main() {
+  check_signature_set();
+  check_band_groups();
+  check_filter_class_lists();
+  check_compaction_map();
   check_path_enumerator();
   check_take_paths();
   check_predicates();
