@@ -30,11 +30,16 @@
 #include "teb_costmap_polygons.hpp"
 #include "teb_plan_window.hpp"
 #include "teb_scene_store.hpp"
+#include "teb_band_store.hpp"
 #include "teb_hcp_host.hpp"
 #include "teb_costmap_host.hpp"
 #include "teb_launch_host.hpp"
 
 using namespace tebamd;
+
+// the two primitives of DevBuf (teb_scene_store.hpp)
+tebamd::DevError tebamd::device_allocate(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+void tebamd::device_free(void* p) { (void)hipFree(p); }
 
 // teb_launch_host.hpp names the layouts, the scene kinds and the limits of its rules itself: they are the kernel's
 static_assert(LAYOUT_BAND == SOLVER_BAND && LAYOUT_BLOCKS == SOLVER_CR && LAYOUT_BAND_HBM == SOLVER_BANDG, "teb_launch_host.hpp numbers the layouts");
@@ -128,12 +133,42 @@ struct SceneLayout {
   LdsPlan plan;
   int cache_entries() const { return fast_points ? max_cache : 0; }   // 0: generic distance path
 };
-struct Strips { double *x, *y, *th, *dt; int* n; };   // the four strips of a set of bands and their pose counts
 
+// What a handle owns beside device memory. Each frees what it holds, if anything; none is copied.
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() = default;
+  OwnedStream(const OwnedStream&) = delete;
+  ~OwnedStream() { if (s) (void)hipStreamDestroy(s); }
+};
+struct OwnedEvent {
+  hipEvent_t e = nullptr;
+  OwnedEvent() = default;
+  OwnedEvent(const OwnedEvent&) = delete;
+  ~OwnedEvent() { if (e) (void)hipEventDestroy(e); }
+};
+template <typename T>
+struct PinnedBlock {   // hipHostMalloc
+  T* p = nullptr;
+  PinnedBlock() = default;
+  PinnedBlock(const PinnedBlock&) = delete;
+  ~PinnedBlock() { if (p) (void)hipHostFree(p); }
+};
+
+// TEARDOWN ORDER ("Who owns device memory"): the destructor body selects the device and waits for the stream; then the
+// members go in reverse order of declaration - every DevBuf first, then the pinned blocks, the events and an owned stream, which
+// therefore stand BEFORE every buffer below. teb_amd_destroy is `delete`.
 struct teb_amd_handle {
+  ~teb_amd_handle() {
+    (void)hipSetDevice(device);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
   int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = false;
+  OwnedStream own_stream;         // the stream the handle made itself, if the caller passed none
+  hipStream_t stream = nullptr;   // the stream everything runs on: the caller's, or own_stream.s
+  OwnedEvent ev1, ev0;
+  PinnedBlock<double> pack_host;   // the pinned host side of pack_dev
+  PinnedBlock<unsigned> mcu_trace; // teb_amd_debug_mcu_watchdog: host-pinned breadcrumbs of the multi-CU launch, one word per workgroup
   teb_amd_config_t cfg;
   int max_tebs = 0, stride = 0, max_obst = 0, max_verts = 0, max_via = 0;
   int B = 0, M = 0, nvia = 0, n_static = 0, n_dyn = 0;
@@ -156,36 +191,33 @@ struct teb_amd_handle {
   HostObst hob;
   std::vector<int> host_static;
   DevSceneStore scene;
-  // batch
-  DevBuf<int> n, has_vs, has_vg, rotdir, via_en, status, optimized, iters, last_iters, trials, assoc_cnt, assoc, assoc_ovf, via_pose, legacy_idx;
-  DevBuf<double> x, y, th, dt, vs, vg, chi2, cost, lambda, Hbackup, Hband, ob_x, ob_y, ob_th, ob_dt;   // ob_*: strips before an optimistic launch
-  DevBuf<int> ob_n;
-  Strips live() const { return Strips{x.p, y.p, th.p, dt.p, n.p}; }               // the bands the kernels work on
-  Strips saved() const { return Strips{ob_x.p, ob_y.p, ob_th.p, ob_dt.p, ob_n.p}; }   // their copy from before a checked launch
+  // the batch (teb_band_store.hpp): the bands the kernels work on, the scratch compact_by_map gathers them through (allocated at the
+  // first compaction), their strips from before a checked launch (allocated at the first one) and at the last snapshot
+  DevBandStore bands, tmp;
+  BandStrips ob, snap;
+  Strips live() const { return bands.strips.view(); }
+  Strips saved() const { return ob.view(); }
+  Strips snapshot() const { return snap.view(); }
+  // the scratch of an optimise launch, BatchDev's beyond the bands
+  DevBuf<int> assoc_cnt, assoc, assoc_ovf, via_pose, legacy_idx;
+  DevBuf<double> Hbackup, Hband;
   DevBuf<long long> clk;   // BatchDev::clk
   // multi-CU mode (teb_multicu.hpp): control words, published poses, distance records; sized on first use
   DevBuf<unsigned> mcu_ctl;
   DevBuf<double> pack_dev;          // packed messages of small batches (kPackMaxDoubles)
-  double* pack_host = nullptr;      // its pinned host side
   DevBuf<double> mcu_pub, mcu_items, mcu_spec;
   size_t mcu_items_have = 0;
   int mcu_last_helpers = 0;   // distance helpers per band of the last launch (0: none), teb_amd_last_launch_info
   int mcu_last_solvers = 0;   // solver helpers per band of the last launch
   int mcu_last_repeated = 0;  // that launch timed out waiting for its helpers and was repeated on one CU per band
   HelperBackoff mcu_backoff;  // the pause of the distance helpers after a launch they came late to (teb_launch_host.hpp)
-  unsigned* mcu_trace = nullptr;   // teb_amd_debug_mcu_watchdog: host-pinned breadcrumbs of the multi-CU launch, one word per workgroup
   int mcu_watchdog_ms = 0;
   int mcu_debug_flags = 0;
   DevBuf<double> iter_log;   // teb_amd_set_iteration_log: [max_tebs][TEB_AMD_ITERATION_LOG_ROWS][4]
   bool iter_log_on = false;
   DevBuf<double> phase_log;  // teb_amd_set_phase_log: [max_tebs][kPhaseLogSlots]
   bool phase_log_on = false;
-  bool opt_backup_ready = false;
   size_t hband_stride = 0;
-  // snapshot
-  DevBuf<int> snap_n;
-  DevBuf<double> snap_x, snap_y, snap_th, snap_dt;
-  Strips snapshot() const { return Strips{snap_x.p, snap_y.p, snap_th.p, snap_dt.p, snap_n.p}; }
   // debug / select
   DevBuf<double> dbg_H, dbg_b, dbg_chi2, sel_cost;
   DevBuf<int> sel_idx, err_flag;
@@ -198,14 +230,12 @@ struct teb_amd_handle {
   SignatureSet sigs;            // of the single scene's bands (teb_hcp_host.hpp); hsig is the scratch of every signature launch
   bool hs_prod_valid = false;   // hs_pre / hs_pim / hs_pex hold the products of the current obstacle table
   int consumers_la = 0, consumers_prevent = 0;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   // candidate generation (f3): graph + candidate scratch strips, boost-compatible generator
-  DevBuf<double> g_vx, g_vy, cand_x, cand_y, cand_th, cand_dt, cand_sig, cand_px, cand_py, tmp_x, tmp_y, tmp_th, tmp_dt, tmp_vs, tmp_vg,
-      tmp_chi2, tmp_cost, tmp_lambda;
-  DevBuf<int> cand_n, cand_off, cand_map, tmp_n, tmp_i;
+  BandStrips cand;   // kCandChunk candidate bands; allocated with the scratch below (ensure_candidate_buffers)
+  DevBuf<double> g_vx, g_vy, cand_sig, cand_px, cand_py;
+  DevBuf<int> cand_off, cand_map;
   DevBuf<unsigned char> g_adj;
-  bool cand_ready = false, tmp_ready = false;
   PlannerMemory memory;   // what the single scene's planner remembers between ticks (teb_hcp_host.hpp); g_vx .. g_adj above are launch scratch
   // costmap (f4)
   DevBuf<unsigned char> cm_cells;
@@ -233,7 +263,6 @@ struct teb_amd_handle {
     DevBuf<int> pcnt, poff, blk, ptot;
     DevBuf<CmpSceneRec> prec;
     DevBuf<double> pvx, pvy;
-    void free() { free_all(cnt, tot, rec, px, py, pcnt, poff, blk, ptot, prec, pvx, pvy); }
   } cmx;
   // scratch of the per-scene calls at the far end of a fleet tick: the bands of teb_amd_is_trajectory_feasible_per_scene, the message
   // of teb_amd_update_and_prune_per_scene
@@ -256,13 +285,7 @@ struct teb_amd_handle {
   // fleet batches (teb_fleet.hpp, teb_amd_set_scenes): the scene set - a second DevSceneStore, allocated at the first
   // teb_amd_set_scenes and sized by the capacities of the handle, with the rows, vertices and via-points of the scenes one after the
   // other (scene_segments) - and what a fleet launch needs beside it
-  struct Fleet {
-    int n_scenes = 0;               // 0 = single-scene mode
-    bool allocated = false;
-    std::vector<HostObst> tabs;     // host copy of every scene's table: teb_amd_set_config re-derives the lists from them
-    std::vector<int> via_count;
-    std::vector<int> band_scene;    // [max_tebs] scene of every band (teb_amd_set_band_scenes); survives set / clear
-    SceneLayout layout;             // of a fleet launch (the single-scene choice h->layout is not touched)
+  struct FleetStorage {   // the device side of the scene set
     DevSceneStore store;
     DevBuf<int> scene_of, sel_last, sel_init, sel_idx;
     DevBuf<double> sel_cost;
@@ -271,23 +294,26 @@ struct teb_amd_handle {
     // (sigs, hs_pre .. above), which the per-scene calls never touch
     DevBuf<double> hs_pre, hs_pim;   // 2-D: prod_l of every row of the set's store, each over the rows of its own scene
     DevBuf<int> hs_pex, hs_off;      // hs_off [max_tebs + 1]: first value of every band in the signature buffer
+    // scratch of the candidate exploration per scene, separate from the single scene's and allocated at the first call: candidate
+    // strips, path points, offsets, candidate -> scene map, signatures; the graphs of a call (vertices, adjacency, records)
+    BandStrips ex;
+    DevBuf<double> ex_px, ex_py, ex_pyaw, ex_sig, ex_orient, ex_line, ex_gvx, ex_gvy;
+    DevBuf<int> ex_off, ex_scene, ex_soff, ex_map;
+    DevBuf<unsigned char> ex_gadj;
+    DevBuf<GraphFleetRec> ex_rec;
+  };
+  struct Fleet : FleetStorage {
+    int n_scenes = 0;               // 0 = single-scene mode
+    bool allocated = false;
+    std::vector<HostObst> tabs;     // host copy of every scene's table: teb_amd_set_config re-derives the lists from them
+    std::vector<int> via_count;
+    std::vector<int> band_scene;    // [max_tebs] scene of every band (teb_amd_set_band_scenes); survives set / clear
+    SceneLayout layout;             // of a fleet launch (the single-scene choice h->layout is not touched)
     bool hs_prod_valid = false;
     SignatureSet sigs;               // of the bands of the set, each as wide as its scene's table
     std::vector<PlannerMemory> memory;   // [n_scenes] what the planner of every scene - a robot - remembers; none of it is the single scene's
-    // scratch of the candidate exploration per scene, separate from the single scene's and allocated at the first call: candidate
-    // strips, path points, offsets, candidate -> scene map, signatures; the graphs of a call (vertices, adjacency, records)
-    DevBuf<double> ex_x, ex_y, ex_th, ex_dt, ex_px, ex_py, ex_pyaw, ex_sig, ex_orient, ex_line, ex_gvx, ex_gvy;
-    DevBuf<int> ex_n, ex_off, ex_scene, ex_soff, ex_map;
-    DevBuf<unsigned char> ex_gadj;
-    DevBuf<GraphFleetRec> ex_rec;
     void new_planners(size_t ns) { memory.assign(ns, PlannerMemory()); }   // ns planners that remember nothing
-    void release() {   // the device side
-      store.free();
-      free_all(scene_of, sel_last, sel_init, sel_idx, sel_cost, scenes, hs_pre, hs_pim, hs_pex, hs_off);
-      free_all(ex_x, ex_y, ex_th, ex_dt, ex_px, ex_py, ex_pyaw, ex_sig, ex_orient, ex_line, ex_gvx, ex_gvy, ex_n, ex_off, ex_scene, ex_soff, ex_map,
-               ex_gadj, ex_rec);
-      allocated = false;
-    }
+    void release() { static_cast<FleetStorage&>(*this) = FleetStorage(); allocated = false; }   // the device side
   } fleet;
   int explore_quota = 0;   // teb_amd_debug_set_explore_quota: paths per scene and round of the per-scene exploration, 0 = kExploreQuota
   // the bands, the obstacles or the configuration change: the signatures of an earlier compute call are stale, the single scene's and
@@ -318,11 +344,7 @@ SceneDev scene_of(teb_amd_handle* h) {
 BatchDev batch_of(teb_amd_handle* h) {
   BatchDev b;
   b.B = h->B; b.stride = h->stride;
-  b.n = h->n.p; b.x = h->x.p; b.y = h->y.p; b.th = h->th.p; b.dt = h->dt.p;
-  b.has_vs = h->has_vs.p; b.vs = h->vs.p; b.has_vg = h->has_vg.p; b.vg = h->vg.p;
-  b.rotdir = h->rotdir.p; b.via_en = h->via_en.p;
-  b.status = h->status.p; b.optimized = h->optimized.p; b.iters = h->iters.p; b.last_iters = h->last_iters.p; b.trials = h->trials.p;
-  b.chi2 = h->chi2.p; b.cost = h->cost.p; b.lambda = h->lambda.p;
+  h->bands.view(b);
   b.assoc_cnt = h->assoc_cnt.p; b.assoc = h->assoc.p; b.assoc_cap = h->max_obst > 0 ? h->max_obst : 1;
   b.assoc_overflow = h->assoc_ovf.p; b.legacy_idx = h->legacy_idx.p;
   b.via_pose = h->via_pose.p; b.via_cap = h->max_via > 0 ? h->max_via : 1;
@@ -520,7 +542,7 @@ static int copy_strips(teb_amd_handle_t* h, const Strips& dst, const Strips& src
 int read_flags(teb_amd_handle* h, bool* outgrown, bool* helpers_late, int* nmax) {
   std::vector<int> ovf(h->B), nn(nmax ? h->B : 0);
   HIPCHK(hipMemcpyAsync(ovf.data(), h->assoc_ovf.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (nmax) HIPCHK(hipMemcpyAsync(nn.data(), h->n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (nmax) HIPCHK(hipMemcpyAsync(nn.data(), h->bands.strips.n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   int flags = 0;
   for (int v : ovf) flags |= v;
@@ -537,7 +559,7 @@ void mcu_watchdog(teb_amd_handle* h, int H) {
   while (hipStreamQuery(h->stream) == hipErrorNotReady) {
     if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > h->mcu_watchdog_ms) {
       fprintf(stderr, "[teb_amd multi-CU watchdog] launch of %d bands x (1 + %d) workgroups still running after %d ms; breadcrumbs (epoch << 8 | code):\n", h->B, H, h->mcu_watchdog_ms);
-      for (int w = 0; w < h->B * (1 + H) && w < 1024; ++w) fprintf(stderr, " wg%d:%x", w, h->mcu_trace[w]);
+      for (int w = 0; w < h->B * (1 + H) && w < 1024; ++w) fprintf(stderr, " wg%d:%x", w, h->mcu_trace.p[w]);
       fprintf(stderr, "\n");
       fflush(stderr);
       _exit(3);
@@ -565,24 +587,20 @@ int prepare_helpers(teb_amd_handle* h, Helpers& hp, McuDev& mcu) {
   mcu.K = hp.K; mcu.D = hp.D; mcu.ctl = h->mcu_ctl.p; mcu.pub = h->mcu_pub.p; mcu.items = hp.D > 0 ? h->mcu_items.p : nullptr; mcu.item_cap = h->M; mcu.spec = h->mcu_spec.p;
   mcu.timeout_ticks = helper_timeout_ticks(h->opt.multi_cu_timeout_us);
   if (hp.D > 0) mcu.timeout_ticks = h->mcu_backoff.probe_timeout(mcu.timeout_ticks);
-  mcu.trace = h->mcu_trace;
+  mcu.trace = h->mcu_trace.p;
   mcu.debug_flags = h->mcu_debug_flags;
-  if (h->mcu_trace) std::memset(h->mcu_trace, 0, 1024 * sizeof(unsigned));
+  if (h->mcu_trace.p) std::memset(h->mcu_trace.p, 0, 1024 * sizeof(unsigned));
   return TEB_AMD_OK;
 }
 // the strips as they are now, for a repeat of the launch
 int save_strips(teb_amd_handle* h) {
-  if (!h->opt_backup_ready) {
-    const size_t BS = (size_t)h->max_tebs * h->stride;
-    HIPCHK(h->ob_x.alloc(BS)); HIPCHK(h->ob_y.alloc(BS)); HIPCHK(h->ob_th.alloc(BS)); HIPCHK(h->ob_dt.alloc(BS)); HIPCHK(h->ob_n.alloc(h->max_tebs));
-    h->opt_backup_ready = true;
-  }
+  if (!h->ob.bands()) HIPCHK(h->ob.alloc(h->max_tebs, h->stride));
   return copy_strips(h, h->saved(), h->live(), h->B);
 }
 // the longest resident band, read back from the device
 int longest_band(teb_amd_handle* h, int* nmax) {
   std::vector<int> n(h->B);
-  HIPCHK(hipMemcpyAsync(n.data(), h->n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(n.data(), h->bands.strips.n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   *nmax = 0;
   for (int v : n) *nmax = std::max(*nmax, v);
@@ -622,9 +640,9 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
   // 4. run
   if (h->opt.compile_for_config >= 2 && !fleet)   // synchronous mode: the wait for the compiler is not kernel time
     (void)rtc_lookup(h, args, sc, eff_solver, H > 0, profile_matches(h, args, sc), true);
-  HIPCHK(hipEventRecord(h->ev0, h->stream));   // (the kernel clears its bands' overflow flags itself)
+  HIPCHK(hipEventRecord(h->ev0.e, h->stream));   // (the kernel clears its bands' overflow flags itself)
   HIPCHK(run(eff_solver, eff_plan, H > 0 ? &mcu : nullptr));
-  if (H > 0 && h->mcu_trace && h->mcu_watchdog_ms > 0) mcu_watchdog(h, H);
+  if (H > 0 && h->mcu_trace.p && h->mcu_watchdog_ms > 0) mcu_watchdog(h, H);
   if (checked) {
     // 5. look at the flags, 6. ask the ladder, 7. run what it says - from the saved strips, without helpers; ev0 stays where it was: the
     // reported time includes the discarded launches
@@ -651,7 +669,7 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
   h->consumers_valid = false;
   h->signatures_stale();   // the bands change: signatures of an earlier teb_amd_compute_h_signatures call are stale
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(h->ev1, h->stream));
+  HIPCHK(hipEventRecord(h->ev1.e, h->stream));
   h->timed = true;
   return TEB_AMD_OK;
 }
@@ -760,75 +778,44 @@ int teb_amd_create_ex(const teb_amd_config_t* cfg, int32_t max_tebs, int32_t max
   h->hmat_stride = (h->hmat_stride + 1) & ~(size_t)1;   // every band's slice 16-byte aligned (the multi-CU mode writes it with 16-byte stores)
   h->band_ldlt = opt.band_ldlt != 0;
   if (solver == SOLVER_BANDG) h->band_ldlt = 0;   // the sequential LDL^T works in place on an LDS band only
-  if (stream) { h->stream = reinterpret_cast<hipStream_t>(stream); h->own_stream = false; }
+  if (stream) h->stream = reinterpret_cast<hipStream_t>(stream);
   else {
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(TEB_AMD_ERR_HIP, "hipStreamCreate failed"); }
-    h->own_stream = true;
+    if (hipStreamCreateWithFlags(&h->own_stream.s, hipStreamNonBlocking) != hipSuccess) { delete h; return fail(TEB_AMD_ERR_HIP, "hipStreamCreate failed"); }
+    h->stream = h->own_stream.s;
   }
   const size_t BS = (size_t)max_tebs * max_poses;
   const size_t Mo = max_obstacles > 0 ? max_obstacles : 1;
-  bool ok = true;
-  auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
-  if (!h->scene.alloc(Mo, 1, max_obstacle_vertices, max_via_points, 0)) ok = false;
-  A(h->n.alloc(max_tebs)); A(h->has_vs.alloc(max_tebs)); A(h->has_vg.alloc(max_tebs)); A(h->rotdir.alloc(max_tebs));
-  A(h->via_en.alloc(max_tebs)); A(h->status.alloc(max_tebs)); A(h->optimized.alloc(max_tebs)); A(h->iters.alloc(max_tebs)); A(h->last_iters.alloc(max_tebs)); A(h->trials.alloc(max_tebs));
+  AllocRun A;
+  if (!h->scene.alloc(Mo, 1, max_obstacle_vertices, max_via_points, 0)) A(hipErrorOutOfMemory);
+  A(h->bands.alloc(max_tebs, max_poses)); A(h->snap.alloc(max_tebs, max_poses));
   A(h->assoc_cnt.alloc(BS)); A(h->assoc.alloc(BS * Mo)); A(h->assoc_ovf.alloc(max_tebs)); A(h->legacy_idx.alloc((size_t)max_tebs * Mo));
   A(h->via_pose.alloc((size_t)max_tebs * (max_via_points > 0 ? max_via_points : 1)));
-  A(h->x.alloc(BS)); A(h->y.alloc(BS)); A(h->th.alloc(BS)); A(h->dt.alloc(BS));
-  A(h->vs.alloc(3 * (size_t)max_tebs)); A(h->vg.alloc(3 * (size_t)max_tebs));
-  A(h->chi2.alloc(max_tebs)); A(h->cost.alloc(max_tebs)); A(h->lambda.alloc(max_tebs));
   A(h->Hbackup.alloc((size_t)max_tebs * h->hmat_stride));
   A(h->clk.alloc(4));
   h->hband_stride = solver == SOLVER_BANDG ? (((size_t)hbo(4 * max_poses) + 2 + 1) & ~(size_t)1) : 0;   // even: the bands' slices are zeroed in 16-byte stores
   A(h->Hband.alloc((size_t)max_tebs * h->hband_stride));
-  A(h->snap_n.alloc(max_tebs)); A(h->snap_x.alloc(BS)); A(h->snap_y.alloc(BS)); A(h->snap_th.alloc(BS)); A(h->snap_dt.alloc(BS));
   A(h->dbg_H.alloc((size_t)4 * max_poses * kBand)); A(h->dbg_b.alloc((size_t)4 * max_poses)); A(h->dbg_chi2.alloc(4));
   A(h->sel_cost.alloc(2)); A(h->sel_idx.alloc(1)); A(h->err_flag.alloc(1));
   A(h->pack_dev.alloc(kPackMaxDoubles));
-  if (ok && hipHostMalloc(reinterpret_cast<void**>(&h->pack_host), kPackMaxDoubles * sizeof(double), hipHostMallocDefault) != hipSuccess) h->pack_host = nullptr;   // (optional: without it the strided copies are used)
+  if (A.ok() && hipHostMalloc(reinterpret_cast<void**>(&h->pack_host.p), kPackMaxDoubles * sizeof(double), hipHostMallocDefault) != hipSuccess) h->pack_host.p = nullptr;   // (optional: without it the strided copies are used)
   A(h->stage_x.alloc((size_t)max_poses + 2)); A(h->stage_y.alloc((size_t)max_poses + 2)); A(h->stage_yaw.alloc((size_t)max_poses + 2));
   A(h->out_cmd.alloc(4 * (size_t)max_tebs)); A(h->out_prof.alloc((size_t)max_tebs * (max_poses + 1) * 3)); A(h->out_traj.alloc(BS * 7));
   A(h->hsig.alloc((size_t)max_tebs * (Mo > 2 ? Mo : 2))); A(h->hs_pre.alloc(Mo)); A(h->hs_pim.alloc(Mo)); A(h->hs_pex.alloc(Mo));
-  if (ok && hipEventCreate(&h->ev0) != hipSuccess) ok = false;
-  if (ok && hipEventCreate(&h->ev1) != hipSuccess) ok = false;
+  if (A.ok()) A(hipEventCreate(&h->ev0.e));
+  if (A.ok()) A(hipEventCreate(&h->ev1.e));
   // every instantiation of the build may be launched (teb_amd_set_obstacles / per-launch choice) with any plan up to the limit
 #define TEB_OPT_FULL_LDS(S, J, P) \
-  if (const void* k = TEB_OPT_KERNEL_FN(S, J, P)()) if (ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit) != hipSuccess) ok = false;
+  if (const void* k = TEB_OPT_KERNEL_FN(S, J, P)()) if (A.ok()) A(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_limit));
   TEB_OPT_FOR_ALL(TEB_OPT_FULL_LDS)
 #undef TEB_OPT_FULL_LDS
-  if (ok && hipMemset(h->cost.p, 0, sizeof(double) * max_tebs) != hipSuccess) ok = false;
-  if (ok && hipMemset(h->chi2.p, 0, sizeof(double) * max_tebs) != hipSuccess) ok = false;
-  if (ok && hipMemset(h->iters.p, 0, sizeof(int) * max_tebs) != hipSuccess) ok = false;   // hasDiverged: "no statistics yet"
-  if (ok && hipMemset(h->last_iters.p, 0, sizeof(int) * max_tebs) != hipSuccess) ok = false;
-  if (ok && hipMemset(h->status.p, 0, sizeof(int) * max_tebs) != hipSuccess) ok = false;
-  if (ok && hipMemset(h->optimized.p, 0, sizeof(int) * max_tebs) != hipSuccess) ok = false;
-  if (!ok) { teb_amd_destroy(h); return fail(TEB_AMD_ERR_HIP, "device allocation / kernel attribute setup failed"); }
+  if (A.ok()) A(h->bands.zero_at_create([](void* p, size_t bytes) { return hipMemset(p, 0, bytes); }));
+  if (!A.ok()) { delete h; return fail(TEB_AMD_ERR_HIP, "device allocation / kernel attribute setup failed"); }
   *out = h;
   return TEB_AMD_OK;
 }
 
-void teb_amd_destroy(teb_amd_handle_t* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  if (h->stream) (void)hipStreamSynchronize(h->stream);
-  h->scene.free();
-  h->fleet.release();
-  h->cmx.free();
-  free_all(h->n, h->has_vs, h->has_vg, h->rotdir, h->via_en, h->status, h->optimized, h->iters, h->last_iters, h->trials, h->assoc_cnt, h->assoc, h->assoc_ovf,
-           h->via_pose, h->legacy_idx, h->snap_n, h->sel_idx, h->err_flag, h->hs_pex, h->x, h->y, h->th, h->dt, h->vs, h->vg, h->chi2, h->cost, h->lambda,
-           h->Hbackup, h->Hband, h->ob_x, h->ob_y, h->ob_th, h->ob_dt, h->ob_n, h->snap_x, h->snap_y, h->snap_th, h->snap_dt, h->dbg_H, h->dbg_b, h->dbg_chi2,
-           h->sel_cost, h->stage_x, h->stage_y, h->stage_yaw, h->out_cmd, h->out_prof, h->out_traj, h->hsig, h->hs_pre, h->hs_pim, h->g_vx, h->g_vy, h->cand_x,
-           h->cand_y, h->cand_th, h->cand_dt, h->cand_sig, h->cand_px, h->cand_py, h->tmp_x, h->tmp_y, h->tmp_th, h->tmp_dt, h->tmp_vs, h->tmp_vg, h->tmp_chi2,
-           h->tmp_cost, h->tmp_lambda, h->cand_n, h->cand_off, h->cand_map, h->tmp_n, h->tmp_i, h->iter_log, h->phase_log, h->mcu_ctl, h->mcu_pub, h->mcu_items,
-           h->mcu_spec, h->pack_dev, h->g_adj, h->cm_cells, h->cm_fp, h->cm_out, h->cms.cells, h->cms.grids, h->cms_bands, h->prune_msg,
-           h->plans.poses, h->plans.in, h->plans.pack, h->plans.first, h->plans.count, h->plans.cursor, h->plans.rec, h->plans.ticket);
-  if (h->mcu_trace) (void)hipHostFree(h->mcu_trace);
-  if (h->pack_host) (void)hipHostFree(h->pack_host);
-  if (h->ev0) (void)hipEventDestroy(h->ev0);
-  if (h->ev1) (void)hipEventDestroy(h->ev1);
-  if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
-}
+// (the order of the teardown: ~teb_amd_handle)
+void teb_amd_destroy(teb_amd_handle_t* h) { delete h; }
 
 namespace {
 // The distance path and the layout of the tables of a scene store, for an obstacle cache of lay.max_cache entries (layout_per_table), and
@@ -838,7 +825,6 @@ int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, SceneLayout& lay
                                          lay.max_cache, h->stride, h->lds_limit, plan_bytes_of(h->lds_limit));
   if (t.hbm_band && h->hband_stride == 0) {
     h->hband_stride = ((size_t)hbo(4 * h->stride) + 2 + 1) & ~(size_t)1;
-    h->Hband.free();
     HIPCHK(h->Hband.alloc((size_t)h->max_tebs * h->hband_stride));
   }
   lay.solver = t.layout;
@@ -1017,20 +1003,20 @@ int fleet_allocate(teb_amd_handle* h) {
   if (F.allocated) return TEB_AMD_OK;
   const size_t T = (size_t)h->max_tebs;
   // (every scene has one first-vertex offset more than rows, and there are at most T scenes)
-  bool ok = F.store.alloc((size_t)std::max(h->max_obst, 0), T, (size_t)std::max(h->max_verts, 0), (size_t)std::max(h->max_via, 0), kFleetPad);
-  auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
+  AllocRun A;
+  if (!F.store.alloc((size_t)std::max(h->max_obst, 0), T, (size_t)std::max(h->max_verts, 0), (size_t)std::max(h->max_via, 0), kFleetPad)) A(hipErrorOutOfMemory);
   A(F.scenes.alloc(T)); A(F.scene_of.alloc(T)); A(F.sel_last.alloc(T)); A(F.sel_init.alloc(T)); A(F.sel_idx.alloc(T)); A(F.sel_cost.alloc(T));
   const size_t rows = (size_t)std::max(h->max_obst, 0) + kFleetPad;   // one product per row of the set's store
   A(F.hs_pre.alloc(rows)); A(F.hs_pim.alloc(rows)); A(F.hs_pex.alloc(rows)); A(F.hs_off.alloc(T + 1));
 #ifdef TEB_AMD_HAS_FLEET_UNITS
 #define TEB_FLEET_FULL_LDS(S, P) \
-  if (const void* k = TEB_FLEET_KERNEL_FN(S, P)()) if (ok && hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit) != hipSuccess) ok = false;
+  if (const void* k = TEB_FLEET_KERNEL_FN(S, P)()) if (A.ok()) A(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->lds_limit));
   TEB_FLEET_FOR_ALL(TEB_FLEET_FULL_LDS)
 #undef TEB_FLEET_FULL_LDS
 #endif
   if (F.band_scene.empty()) F.band_scene.assign(T, 0);
-  if (ok && hipMemcpy(F.scene_of.p, F.band_scene.data(), T * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) ok = false;
-  if (!ok) {
+  if (A.ok()) A(hipMemcpy(F.scene_of.p, F.band_scene.data(), T * sizeof(int), hipMemcpyHostToDevice));
+  if (!A.ok()) {
     (void)hipGetLastError();
     F.release();
     return fail(TEB_AMD_ERR_HIP, "teb_amd_set_scenes: device allocation of the fleet storage failed");
@@ -1144,7 +1130,7 @@ int teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best,
   }
   HIPCHK(hipMemcpyAsync(F.sel_last.p, lb.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(F.sel_init.p, ip.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  LAUNCH(select_best_per_scene_kernel, dim3(ns), dim3(kThreads), 0, h->stream, h->cost.p, F.scene_of.p, h->B, F.sel_last.p, F.sel_init.p,
+  LAUNCH(select_best_per_scene_kernel, dim3(ns), dim3(kThreads), 0, h->stream, h->bands.cost.p, F.scene_of.p, h->B, F.sel_last.p, F.sel_init.p,
          h->cfg.selection_cost_hysteresis, h->cfg.selection_prefer_initial_plan, F.sel_cost.p, F.sel_idx.p);
   std::vector<double> cst(ns);
   HIPCHK(hipMemcpyAsync(best, F.sel_idx.p, ns * sizeof(int), hipMemcpyDeviceToHost, h->stream));
@@ -1169,32 +1155,15 @@ int teb_amd_upload_tebs(teb_amd_handle_t* h, const teb_amd_teb_batch_t* bt) {
   }
   if (nmax > h->stride) return fail(TEB_AMD_ERR_CAPACITY, "a TEB has more poses than max_poses");
   const int wc_pack = bt->stride < h->stride ? bt->stride : h->stride;   // whole rows, like the strided copies: the padding stays the caller's
-  if (h->pack_host && 11 * (size_t)B + 4 * (size_t)B * wc_pack <= kPackMaxDoubles) {   // small batch: one packed message, one copy, one kernel
-    double* m = h->pack_host;
+  const UploadMsg msg{(size_t)B, (size_t)wc_pack};
+  if (h->pack_host.p && msg.size() <= kPackMaxDoubles) {   // small batch: one packed message, one copy, one kernel
     const int wc = wc_pack;
-    for (int b = 0; b < B; ++b) {
-      m[b] = bt->n[b];
-      m[B + b] = bt->has_vel_start ? (bt->has_vel_start[b] != 0) : 1;
-      m[2 * B + b] = bt->has_vel_goal ? (bt->has_vel_goal[b] != 0) : 1;
-      m[3 * B + b] = bt->prefer_rotdir ? bt->prefer_rotdir[b] : TEB_AMD_ROT_NONE;
-      m[4 * B + b] = bt->via_points_enabled ? (bt->via_points_enabled[b] != 0) : 1;
-      for (int q = 0; q < 3; ++q) {
-        m[5 * B + 3 * b + q] = bt->vel_start ? bt->vel_start[3 * b + q] : 0.0;
-        m[8 * B + 3 * b + q] = bt->vel_goal ? bt->vel_goal[3 * b + q] : 0.0;
-      }
-    }
-    double* body = m + 11 * (size_t)B;
-    const size_t plane = (size_t)B * wc;
-    for (int b = 0; b < B; ++b) {
-      const size_t so = (size_t)b * bt->stride, q = (size_t)b * wc;
-      std::memcpy(body + q, bt->x + so, wc * sizeof(double)); std::memcpy(body + plane + q, bt->y + so, wc * sizeof(double));
-      std::memcpy(body + 2 * plane + q, bt->theta + so, wc * sizeof(double)); std::memcpy(body + 3 * plane + q, bt->dt + so, wc * sizeof(double));
-    }
-    const size_t count = 11 * (size_t)B + 4 * plane;
-    HIPCHK(hipMemcpyAsync(h->pack_dev.p, m, count * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const size_t plane = msg.plane();
+    pack_upload(*bt, msg.w, h->pack_host.p);
+    HIPCHK(hipMemcpyAsync(h->pack_dev.p, h->pack_host.p, msg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     const int grid = (int)std::min<size_t>(256, (std::max<size_t>(plane, 3 * (size_t)B) + 255) / 256);
-    LAUNCH(unpack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->n.p, h->has_vs.p, h->has_vg.p, h->rotdir.p,
-           h->via_en.p, h->vs.p, h->vg.p, h->x.p, h->y.p, h->th.p, h->dt.p, h->optimized.p);
+    LAUNCH(unpack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->bands.strips.n.p, h->bands.has_vs.p, h->bands.has_vg.p, h->bands.rotdir.p,
+           h->bands.via_en.p, h->bands.vs.p, h->bands.vg.p, h->bands.strips.x.p, h->bands.strips.y.p, h->bands.strips.th.p, h->bands.strips.dt.p, h->bands.optimized.p);
     HIPCHK(hipStreamSynchronize(h->stream));   // (the pinned buffer is reused by the next call)
     h->B = B;
     h->bands_changed(nmax);
@@ -1202,30 +1171,19 @@ int teb_amd_upload_tebs(teb_amd_handle_t* h, const teb_amd_teb_batch_t* bt) {
   }
   const size_t w = (size_t)(bt->stride < h->stride ? bt->stride : h->stride) * sizeof(double);
   const size_t sp = (size_t)bt->stride * sizeof(double), dp = (size_t)h->stride * sizeof(double);
-  HIPCHK(hipMemcpy2DAsync(h->x.p, dp, bt->x, sp, w, B, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpy2DAsync(h->y.p, dp, bt->y, sp, w, B, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpy2DAsync(h->th.p, dp, bt->theta, sp, w, B, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpy2DAsync(h->dt.p, dp, bt->dt, sp, w, B, hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->n.p, bt->n, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  std::vector<int> hvs(B, 1), hvg(B, 1), rd(B, TEB_AMD_ROT_NONE), ve(B, 1);
-  std::vector<double> vs(3 * (size_t)B, 0.0), vg(3 * (size_t)B, 0.0);
-  for (int b = 0; b < B; ++b) {
-    if (bt->has_vel_start) hvs[b] = bt->has_vel_start[b] != 0;
-    if (bt->has_vel_goal) hvg[b] = bt->has_vel_goal[b] != 0;
-    if (bt->prefer_rotdir) rd[b] = bt->prefer_rotdir[b];
-    if (bt->via_points_enabled) ve[b] = bt->via_points_enabled[b] != 0;
-    for (int q = 0; q < 3; ++q) {
-      if (bt->vel_start) vs[3 * b + q] = bt->vel_start[3 * b + q];
-      if (bt->vel_goal) vg[3 * b + q] = bt->vel_goal[3 * b + q];
-    }
-  }
-  HIPCHK(hipMemcpyAsync(h->has_vs.p, hvs.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->has_vg.p, hvg.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->rotdir.p, rd.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->via_en.p, ve.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->vs.p, vs.data(), 3 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->vg.p, vg.data(), 3 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemsetAsync(h->optimized.p, 0, B * sizeof(int), h->stream));   // bands from the host: optimized_ unknown -> false
+  HIPCHK(hipMemcpy2DAsync(h->bands.strips.x.p, dp, bt->x, sp, w, B, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpy2DAsync(h->bands.strips.y.p, dp, bt->y, sp, w, B, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpy2DAsync(h->bands.strips.th.p, dp, bt->theta, sp, w, B, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpy2DAsync(h->bands.strips.dt.p, dp, bt->dt, sp, w, B, hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.strips.n.p, bt->n, B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  const BandAttrArrays at = attrs_of(*bt);
+  HIPCHK(hipMemcpyAsync(h->bands.has_vs.p, at.has_vs.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.has_vg.p, at.has_vg.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.rotdir.p, at.rotdir.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.via_en.p, at.via_en.data(), B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.vs.p, at.vs.data(), 3 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.vg.p, at.vg.data(), 3 * (size_t)B * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemsetAsync(h->bands.optimized.p, 0, B * sizeof(int), h->stream));   // bands from the host: optimized_ unknown -> false
   HIPCHK(hipStreamSynchronize(h->stream));
   h->B = B;
   h->bands_changed(nmax);
@@ -1241,34 +1199,29 @@ int teb_amd_download_tebs(teb_amd_handle_t* h, teb_amd_teb_batch_t* bt) {
   if (B == 0) return TEB_AMD_OK;   // an empty handle (before the first upload, after every band was dropped, a rank without candidates): nothing to copy
   {
     const int wc = bt->stride < h->stride ? bt->stride : h->stride;
-    const size_t plane = (size_t)B * wc, count = (size_t)B + 4 * plane;
-    if (h->pack_host && count <= kPackMaxDoubles) {   // small batch: one gather kernel, one copy
+    const DownloadMsg msg{(size_t)B, (size_t)wc};
+    const size_t plane = msg.plane(), count = msg.size();
+    if (h->pack_host.p && count <= kPackMaxDoubles) {   // small batch: one gather kernel, one copy
       const int grid = (int)std::min<size_t>(256, (plane + 255) / 256);
-      LAUNCH(pack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->n.p, h->x.p, h->y.p, h->th.p, h->dt.p);
-      HIPCHK(hipMemcpyAsync(h->pack_host, h->pack_dev.p, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+      LAUNCH(pack_bands_kernel, dim3(grid), dim3(256), 0, h->stream, h->pack_dev.p, B, wc, h->stride, h->bands.strips.n.p, h->bands.strips.x.p, h->bands.strips.y.p, h->bands.strips.th.p, h->bands.strips.dt.p);
+      HIPCHK(hipMemcpyAsync(h->pack_host.p, h->pack_dev.p, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
-      const double* m = h->pack_host;
-      for (int b = 0; b < B; ++b) if ((int)m[b] > bt->stride) return fail(TEB_AMD_ERR_CAPACITY, "host batch stride too small for the resized TEB");
-      const double* body = m + B;
-      for (int b = 0; b < B; ++b) {
-        const size_t so = (size_t)b * bt->stride, q = (size_t)b * wc;
-        std::memcpy(bt->x + so, body + q, wc * sizeof(double)); std::memcpy(bt->y + so, body + plane + q, wc * sizeof(double));
-        std::memcpy(bt->theta + so, body + 2 * plane + q, wc * sizeof(double)); std::memcpy(bt->dt + so, body + 3 * plane + q, wc * sizeof(double));
-        bt->n[b] = (int)m[b];
-      }
+      const double* m = h->pack_host.p;
+      for (int b = 0; b < B; ++b) if ((int)m[msg.n() + b] > bt->stride) return fail(TEB_AMD_ERR_CAPACITY, "host batch stride too small for the resized TEB");
+      unpack_download(m, msg.B, msg.w, *bt);
       return TEB_AMD_OK;
     }
   }
   std::vector<int> n(B);
-  HIPCHK(hipMemcpyAsync(n.data(), h->n.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(n.data(), h->bands.strips.n.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int b = 0; b < B; ++b) if (n[b] > bt->stride) return fail(TEB_AMD_ERR_CAPACITY, "host batch stride too small for the resized TEB");
   const size_t w = (size_t)(bt->stride < h->stride ? bt->stride : h->stride) * sizeof(double);
   const size_t hp = (size_t)bt->stride * sizeof(double), dp = (size_t)h->stride * sizeof(double);
-  HIPCHK(hipMemcpy2DAsync(bt->x, hp, h->x.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpy2DAsync(bt->y, hp, h->y.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpy2DAsync(bt->theta, hp, h->th.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpy2DAsync(bt->dt, hp, h->dt.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpy2DAsync(bt->x, hp, h->bands.strips.x.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpy2DAsync(bt->y, hp, h->bands.strips.y.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpy2DAsync(bt->theta, hp, h->bands.strips.th.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpy2DAsync(bt->dt, hp, h->bands.strips.dt.p, dp, w, B, hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int b = 0; b < B; ++b) bt->n[b] = n[b];
   return TEB_AMD_OK;
@@ -1353,7 +1306,7 @@ int teb_amd_get_iteration_log(teb_amd_handle_t* h, int32_t b, double* rows, int3
   if (!h->iter_log_on || !h->iter_log.p) return fail(TEB_AMD_ERR_INVALID_ARG, "the iteration log is off (teb_amd_set_iteration_log)");
   if (b < 0 || b >= h->B || !rows || !n_rows || capacity_rows < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_get_iteration_log: bad arguments");
   int iters = 0;
-  HIPCHK(hipMemcpyAsync(&iters, h->iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&iters, h->bands.iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   int nr = std::min(std::min(iters, (int)TEB_AMD_ITERATION_LOG_ROWS), (int)capacity_rows);
   if (nr < 0) nr = 0;
@@ -1377,12 +1330,12 @@ int teb_amd_get_results(teb_amd_handle_t* h, teb_amd_results_t* out) {
   if (!out) return fail(TEB_AMD_ERR_INVALID_ARG, "null results");
   const int B = h->B;
   if (B == 0) return TEB_AMD_OK;   // an empty handle has no results to copy (a grid of 0 workgroups would be a launch error)
-  if (h->pack_host && 6 * (size_t)B <= kPackMaxDoubles) {   // six result columns in one gather + one copy
-    LAUNCH(pack_results_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->pack_dev.p, B, h->status.p, h->iters.p, h->trials.p, h->chi2.p, h->cost.p,
-           h->lambda.p);
-    HIPCHK(hipMemcpyAsync(h->pack_host, h->pack_dev.p, 6 * (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (h->pack_host.p && 6 * (size_t)B <= kPackMaxDoubles) {   // six result columns in one gather + one copy
+    LAUNCH(pack_results_kernel, dim3((B + 255) / 256), dim3(256), 0, h->stream, h->pack_dev.p, B, h->bands.status.p, h->bands.iters.p, h->bands.trials.p, h->bands.chi2.p, h->bands.cost.p,
+           h->bands.lambda.p);
+    HIPCHK(hipMemcpyAsync(h->pack_host.p, h->pack_dev.p, 6 * (size_t)B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    const double* m = h->pack_host;
+    const double* m = h->pack_host.p;
     for (int b = 0; b < B; ++b) {
       if (out->status) out->status[b] = (int32_t)m[b];
       if (out->lm_iterations) out->lm_iterations[b] = (int32_t)m[B + b];
@@ -1393,12 +1346,12 @@ int teb_amd_get_results(teb_amd_handle_t* h, teb_amd_results_t* out) {
     }
     return TEB_AMD_OK;
   }
-  if (out->status) HIPCHK(hipMemcpyAsync(out->status, h->status.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (out->lm_iterations) HIPCHK(hipMemcpyAsync(out->lm_iterations, h->iters.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (out->lm_trials) HIPCHK(hipMemcpyAsync(out->lm_trials, h->trials.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (out->chi2) HIPCHK(hipMemcpyAsync(out->chi2, h->chi2.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out->cost) HIPCHK(hipMemcpyAsync(out->cost, h->cost.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  if (out->lambda) HIPCHK(hipMemcpyAsync(out->lambda, h->lambda.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out->status) HIPCHK(hipMemcpyAsync(out->status, h->bands.status.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (out->lm_iterations) HIPCHK(hipMemcpyAsync(out->lm_iterations, h->bands.iters.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (out->lm_trials) HIPCHK(hipMemcpyAsync(out->lm_trials, h->bands.trials.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (out->chi2) HIPCHK(hipMemcpyAsync(out->chi2, h->bands.chi2.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out->cost) HIPCHK(hipMemcpyAsync(out->cost, h->bands.cost.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  if (out->lambda) HIPCHK(hipMemcpyAsync(out->lambda, h->bands.lambda.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
   return synced(h);
 }
 
@@ -1410,7 +1363,7 @@ int teb_amd_select_best(teb_amd_handle_t* h, int32_t last_best, int32_t initial_
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs uploaded");
   if (last_best >= h->B) last_best = -1;
   if (initial_plan >= h->B) initial_plan = -1;
-  LAUNCH(select_best_kernel, dim3(1), dim3(kThreads), 0, h->stream, h->cost.p, h->B, last_best, initial_plan, h->cfg.selection_cost_hysteresis,
+  LAUNCH(select_best_kernel, dim3(1), dim3(kThreads), 0, h->stream, h->bands.cost.p, h->B, last_best, initial_plan, h->cfg.selection_cost_hysteresis,
          h->cfg.selection_prefer_initial_plan, h->sel_cost.p, h->sel_idx.p);
   double rec[2];   // one 16-byte copy
   HIPCHK(hipMemcpyAsync(rec, h->sel_cost.p, sizeof(rec), hipMemcpyDeviceToHost, h->stream));
@@ -1490,7 +1443,7 @@ int teb_amd_select_best_distributed(teb_amd_handle_t* h, teb_amd_comm_t* c, int3
       int lb = last_best_global - global_offset, ip = initial_plan_global - global_offset;
       if (last_best_global < 0 || lb < 0 || lb >= h->B) lb = -1;
       if (initial_plan_global < 0 || ip < 0 || ip >= h->B) ip = -1;
-      hipLaunchKernelGGL(select_best_kernel, dim3(1), dim3(kThreads), 0, stream, h->cost.p, h->B, lb, ip,
+      hipLaunchKernelGGL(select_best_kernel, dim3(1), dim3(kThreads), 0, stream, h->bands.cost.p, h->B, lb, ip,
                          h->cfg.selection_cost_hysteresis, h->cfg.selection_prefer_initial_plan, h->sel_cost.p, h->sel_idx.p);
     }
     hipLaunchKernelGGL(pack_record_kernel, dim3(1), dim3(64), 0, stream, h->sel_cost.p, h->sel_idx.p, global_offset, have, c->rec);
@@ -1554,8 +1507,8 @@ int teb_amd_broadcast_band(teb_amd_handle_t* h, teb_amd_comm_t* c, int32_t owner
   }
   // round 2: the strip itself
   if (c->rank == owner_rank)
-    hipLaunchKernelGGL(pack_band_kernel, dim3((capacity + 255) / 256), dim3(256), 0, stream, h->n.p, h->x.p, h->y.p, h->th.p, h->dt.p,
-                       local_index, h->stride, capacity, c->msg, h->chi2.p, h->iters.p, h->last_iters.p, h->cfg.divergence_detection_enable != 0,
+    hipLaunchKernelGGL(pack_band_kernel, dim3((capacity + 255) / 256), dim3(256), 0, stream, h->bands.strips.n.p, h->bands.strips.x.p, h->bands.strips.y.p, h->bands.strips.th.p, h->bands.strips.dt.p,
+                       local_index, h->stride, capacity, c->msg, h->bands.chi2.p, h->bands.iters.p, h->bands.last_iters.p, h->cfg.divergence_detection_enable != 0,
                        h->last_inner);
   const bool packed = hipGetLastError() == hipSuccess;   // (a failed pack still enters the broadcast; what arrives is then rejected below)
   NCCLCHK(rccl().Broadcast(c->msg, c->msg, count, kRcclFloat64, owner_rank, c->comm, stream));
@@ -1594,27 +1547,27 @@ int teb_amd_debug_world_argmin(const double* records, int32_t world, int32_t* be
 // ---- f1 / f2: producers and consumers of the device-resident strips (kernels in teb_strip.hpp) ---------------------------------
 namespace {
 
-// slots >= B join the batch with the defaults of TebOptimalPlanner::initialize() (src/optimal_planner.cpp:86-104)
+// slots >= B join the batch as BandAttrs::fresh()
 int extend_batch(teb_amd_handle* h, int b) {
   if (b < 0 || b >= h->max_tebs) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB slot out of range");
   for (int k = h->B; k <= b; ++k) {
-    const int one = 1, none = TEB_AMD_ROT_NONE, two = 2;
-    const double z3[3] = {0, 0, 0};
-    HIPCHK(hipMemcpyAsync(h->has_vs.p + k, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->has_vg.p + k, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->rotdir.p + k, &none, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->via_en.p + k, &one, sizeof(int), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->optimized.p + k, 0, sizeof(int), h->stream));   // a new TebOptimalPlanner: optimized_(false)
-    HIPCHK(hipMemcpyAsync(h->vs.p + 3 * k, z3, sizeof(z3), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(h->vg.p + 3 * k, z3, sizeof(z3), hipMemcpyHostToDevice, h->stream));
+    const BandAttrs a = BandAttrs::fresh();
+    const int two = 2;
+    HIPCHK(hipMemcpyAsync(h->bands.has_vs.p + k, &a.has_vs, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->bands.has_vg.p + k, &a.has_vg, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->bands.rotdir.p + k, &a.rotdir, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->bands.via_en.p + k, &a.via_en, sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->bands.optimized.p + k, 0, sizeof(int), h->stream));   // a new TebOptimalPlanner: optimized_(false)
+    HIPCHK(hipMemcpyAsync(h->bands.vs.p + 3 * k, a.vs, sizeof(a.vs), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->bands.vg.p + 3 * k, a.vg, sizeof(a.vg), hipMemcpyHostToDevice, h->stream));
     if (k < b) {   // a skipped slot becomes the trivial two-pose band at the origin so that the batch stays well-formed
       const double zz[2] = {0, 0}, dd[2] = {0.1, 0};
       const size_t o = (size_t)k * h->stride;
-      HIPCHK(hipMemcpyAsync(h->x.p + o, zz, sizeof(zz), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(h->y.p + o, zz, sizeof(zz), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(h->th.p + o, zz, sizeof(zz), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(h->dt.p + o, dd, sizeof(dd), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipMemcpyAsync(h->n.p + k, &two, sizeof(int), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(h->bands.strips.x.p + o, zz, sizeof(zz), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(h->bands.strips.y.p + o, zz, sizeof(zz), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(h->bands.strips.th.p + o, zz, sizeof(zz), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(h->bands.strips.dt.p + o, dd, sizeof(dd), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(h->bands.strips.n.p + k, &two, sizeof(int), hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));   // the small host temporaries above
   }
@@ -1652,7 +1605,7 @@ int run_consumers(teb_amd_handle* h, int look_ahead, int prevent) {
 
 int band_n(teb_amd_handle* h, int b, int* n) {
   if (b < 0 || b >= h->B) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
-  HIPCHK(hipMemcpyAsync(n, h->n.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(n, h->bands.strips.n.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return synced(h);
 }
 
@@ -1733,13 +1686,13 @@ int set_velocity(teb_amd_handle* h, DevBuf<int>& flag, DevBuf<double>& vel, int 
 int teb_amd_set_velocity_start(teb_amd_handle_t* h, int32_t b, int32_t fixed, const double* v) {
   int rc = check_handle(h);
   if (rc) return rc;
-  return set_velocity(h, h->has_vs, h->vs, b, fixed, v);
+  return set_velocity(h, h->bands.has_vs, h->bands.vs, b, fixed, v);
 }
 
 int teb_amd_set_velocity_goal(teb_amd_handle_t* h, int32_t b, int32_t fixed, const double* v) {
   int rc = check_handle(h);
   if (rc) return rc;
-  return set_velocity(h, h->has_vg, h->vg, b, fixed, v);
+  return set_velocity(h, h->bands.has_vg, h->bands.vg, b, fixed, v);
 }
 
 int teb_amd_get_pose_counts(teb_amd_handle_t* h, int32_t* n, int32_t* count) {
@@ -1747,7 +1700,7 @@ int teb_amd_get_pose_counts(teb_amd_handle_t* h, int32_t* n, int32_t* count) {
   if (rc) return rc;
   if (count) *count = h->B;
   if (n && h->B > 0) {
-    HIPCHK(hipMemcpyAsync(n, h->n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(n, h->bands.strips.n.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   return TEB_AMD_OK;
@@ -1810,9 +1763,9 @@ int teb_amd_has_diverged(teb_amd_handle_t* h, int32_t b, int32_t* diverged) {
   *diverged = 0;
   if (!h->cfg.divergence_detection_enable) return TEB_AMD_OK;
   double chi2 = 0; int iters = 0, last = 0;
-  HIPCHK(hipMemcpyAsync(&chi2, h->chi2.p + b, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&iters, h->iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(&last, h->last_iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&chi2, h->bands.chi2.p + b, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&iters, h->bands.iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(&last, h->bands.last_iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   *diverged = diverged_rule(h->cfg, h->last_inner, iters, last, chi2);
   return TEB_AMD_OK;
@@ -1829,9 +1782,9 @@ int teb_amd_get_batch_statistics(teb_amd_handle_t* h, int32_t* available, double
   const int B = h->B;
   if (B <= 0) return TEB_AMD_OK;
   std::vector<double> chi2(B); std::vector<int> iters(B), last(B);
-  HIPCHK(hipMemcpyAsync(chi2.data(), h->chi2.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(iters.data(), h->iters.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(last.data(), h->last_iters.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(chi2.data(), h->bands.chi2.p, B * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(iters.data(), h->bands.iters.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(last.data(), h->bands.last_iters.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int b = 0; b < B; ++b) {
     available[b] = h->cfg.divergence_detection_enable && iters[b] > 0 && h->last_inner > 0;
@@ -1894,7 +1847,7 @@ int teb_amd_is_trajectory_feasible(teb_amd_handle_t* h, int32_t b, int32_t nf, c
   if (h->B <= 0 || b >= h->B || b < -1) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
   const int first = b < 0 ? 0 : b, count = b < 0 ? h->B : 1;
   return run_feasibility(h, count, nf, fx, fy, feasible, first_infeasible, [&](double* px, double* py, int* fe, int* fi, int* ovf) {
-    LAUNCH(feasibility_kernel, dim3(count), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, first, h->cm, nf, px, py,
+    LAUNCH(feasibility_kernel, dim3(count), dim3(kFeasThreads), 0, h->stream, h->bands.strips.n.p, h->bands.strips.x.p, h->bands.strips.y.p, h->bands.strips.th.p, h->stride, first, h->cm, nf, px, py,
            inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, fe, fi, ovf);
     return (int)TEB_AMD_OK;
   });
@@ -2031,10 +1984,9 @@ int teb_amd_set_costmaps(teb_amd_handle_t* h, int32_t n, const uint8_t* cells, c
   }
   if (S.cells.n < bytes) {   // the new buffer before the old one goes: a failed allocation leaves the previous set
     DevBuf<unsigned char> nb;
-    if (nb.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); nb.free(); return fail(TEB_AMD_ERR_HIP, "teb_amd_set_costmaps: device allocation failed"); }
+    if (nb.alloc(bytes) != hipSuccess) { (void)hipGetLastError(); return fail(TEB_AMD_ERR_HIP, "teb_amd_set_costmaps: device allocation failed"); }
     HIPCHK(hipStreamSynchronize(h->stream));
-    S.cells.free();
-    S.cells = nb;
+    S.cells = std::move(nb);
   }
   if (!S.grids.p) HIPCHK(S.grids.alloc((size_t)h->max_tebs));
   for (int s = 0; s < n; ++s) g[s] = GridDev{S.cells.p + first[s], size_x[s], size_y[s], resolution[s], origin_x[s], origin_y[s]};
@@ -2295,7 +2247,7 @@ int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t*
   return run_feasibility(h, ns, nf, fx, fy, feasible, first_infeasible, [&](double* px, double* py, int* fe, int* fi, int* ovf) {
     if (!h->cms_bands.p) HIPCHK(h->cms_bands.alloc((size_t)h->max_tebs));
     HIPCHK(hipMemcpyAsync(h->cms_bands.p, bands, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
-    LAUNCH(feasibility_fleet_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->n.p, h->x.p, h->y.p, h->th.p, h->stride, h->cms_bands.p, h->cms.grids.p, nf,
+    LAUNCH(feasibility_fleet_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->bands.strips.n.p, h->bands.strips.x.p, h->bands.strips.y.p, h->bands.strips.th.p, h->stride, h->cms_bands.p, h->cms.grids.p, nf,
            px, py, inscribed_radius, min_res_angular, look_ahead_idx, lookahead_distance, 1 << 22, fe, fi, ovf);
     return (int)TEB_AMD_OK;
   });
@@ -2321,7 +2273,7 @@ int teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_st
   HIPCHK(hipMemcpyAsync(h->prune_msg.p, msg.data(), msg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // the upload reads msg; nothing waits for the kernel
   LAUNCH(prune_fleet_kernel, dim3(h->B), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), h->fleet.scene_of.p, h->prune_msg.p,
-         (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples, h->has_vs.p, h->vs.p);
+         (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples, h->bands.has_vs.p, h->bands.vs.p);
   h->bands_changed();
   return TEB_AMD_OK;
 }
@@ -2383,15 +2335,13 @@ int teb_amd_set_global_plans(teb_amd_handle_t* h, int32_t n, const int32_t* plan
     if (begin) cur[r] = begin[r];
   }
   if (total > 0 && (!x || !y || !yaw)) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + "null pose array");
-  // The per-robot buffers of the first call, all six or none: a failed allocation frees what it got, so a later call tries again
-  // (no previous set exists yet at that point).
+  // The per-robot buffers of the first call, all six or none: a failed allocation leaves its buffer empty, so a later call comes here
+  // again and allocates each over what it holds (no previous set exists yet at that point).
   if (!P.first.p || !P.count.p || !P.cursor.p || !P.rec.p || !P.in.p || !P.ticket.p) {
     const size_t T = (size_t)h->max_tebs;
-    free_all(P.first, P.count, P.cursor, P.rec, P.in, P.ticket);
     if (P.first.alloc(T) != hipSuccess || P.count.alloc(T) != hipSuccess || P.cursor.alloc(T) != hipSuccess || P.rec.alloc(T) != hipSuccess ||
         P.in.alloc(9 * T) != hipSuccess || P.ticket.alloc(1) != hipSuccess) {
       (void)hipGetLastError();
-      free_all(P.first, P.count, P.cursor, P.rec, P.in, P.ticket);
       return fail(TEB_AMD_ERR_HIP, std::string(fn) + "device allocation failed");
     }
   }
@@ -2401,11 +2351,10 @@ int teb_amd_set_global_plans(teb_amd_handle_t* h, int32_t n, const int32_t* plan
     DevBuf<double> np, nk;
     if (np.alloc(3 * total) != hipSuccess || nk.alloc(5 * (total + (size_t)h->max_tebs)) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess) {
-      (void)hipGetLastError(); np.free(); nk.free();
+      (void)hipGetLastError();
       return fail(TEB_AMD_ERR_HIP, std::string(fn) + "device allocation failed");
     }
-    P.poses.free(); P.pack.free();
-    P.poses = np; P.pack = nk;
+    P.poses = std::move(np); P.pack = std::move(nk);
   }
   P.n = 0;   // from here on the previous plans are overwritten: a HIP error leaves no set
   P.count_host.clear();
@@ -2538,16 +2487,14 @@ namespace {
 constexpr int kCandChunk = 64;   // candidate paths initialised and classified per device round trip
 
 int ensure_candidate_buffers(teb_amd_handle* h) {
-  if (h->cand_ready) return TEB_AMD_OK;
-  const size_t KS = (size_t)kCandChunk * h->stride, W = (size_t)(h->max_obst > 2 ? h->max_obst : 2);
-  bool ok = true;
-  auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
-  A(h->cand_x.alloc(KS)); A(h->cand_y.alloc(KS)); A(h->cand_th.alloc(KS)); A(h->cand_dt.alloc(KS)); A(h->cand_n.alloc(kCandChunk));
+  if (h->cand.bands()) return TEB_AMD_OK;
+  const size_t W = (size_t)(h->max_obst > 2 ? h->max_obst : 2);
+  AllocRun A;
   A(h->cand_sig.alloc(std::max<size_t>(kCandChunk * W, 4 * (size_t)h->max_tebs)));   // signatures of a chunk / detour statistics of the batch
   A(h->cand_px.alloc((size_t)kCandChunk * (h->stride + 1)));
   A(h->cand_py.alloc((size_t)kCandChunk * (h->stride + 1))); A(h->cand_off.alloc(kCandChunk + 1)); A(h->cand_map.alloc(h->max_tebs));
-  if (!ok) return fail(TEB_AMD_ERR_HIP, "candidate scratch allocation failed");
-  h->cand_ready = true;
+  if (A.ok()) A(h->cand.alloc(kCandChunk, h->stride));   // last: the strips say that the scratch exists
+  if (!A.ok()) return fail(TEB_AMD_ERR_HIP, "candidate scratch allocation failed");
   return TEB_AMD_OK;
 }
 
@@ -2556,22 +2503,18 @@ constexpr int kExploreQuota = 16;  // paths a scene contributes to a round of a 
 // the candidate scratch of the scene set, for K candidates and `values` signature values; grows, never shrinks
 int ensure_fleet_candidate_buffers(teb_amd_handle* h, size_t K, size_t values) {
   auto& F = h->fleet;
-  bool ok = true;
-  auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
-  if (F.ex_n.n < K) {
-    free_all(F.ex_x, F.ex_y, F.ex_th, F.ex_dt, F.ex_n, F.ex_px, F.ex_py, F.ex_pyaw, F.ex_off, F.ex_scene, F.ex_soff, F.ex_line);
-    const size_t KS = K * (size_t)h->stride, KP = K * ((size_t)h->stride + 1);
-    A(F.ex_x.alloc(KS)); A(F.ex_y.alloc(KS)); A(F.ex_th.alloc(KS)); A(F.ex_dt.alloc(KS)); A(F.ex_n.alloc(K));
+  AllocRun A;
+  if (F.ex.bands() < K) {
+    const size_t KP = K * ((size_t)h->stride + 1);
+    F.ex.free();   // (first: a failure below leaves no strips, so the next call comes here again)
     A(F.ex_px.alloc(KP)); A(F.ex_py.alloc(KP)); A(F.ex_pyaw.alloc(KP)); A(F.ex_off.alloc(K + 1)); A(F.ex_scene.alloc(K));
     A(F.ex_soff.alloc(K + 1)); A(F.ex_line.alloc(6 * K));
+    if (A.ok()) A(F.ex.alloc(K, h->stride));
   }
-  if (F.ex_sig.n < std::max<size_t>(values, 2)) { F.ex_sig.free(); A(F.ex_sig.alloc(std::max<size_t>(values, 2))); }
-  if (F.ex_map.n < (size_t)h->max_tebs) { F.ex_map.free(); A(F.ex_map.alloc(h->max_tebs)); }
-  if (F.ex_orient.n < 2 * (size_t)h->max_tebs) {
-    F.ex_orient.free(); F.ex_rec.free();
-    A(F.ex_orient.alloc(2 * (size_t)h->max_tebs)); A(F.ex_rec.alloc(h->max_tebs));
-  }
-  if (!ok) { (void)hipGetLastError(); return fail(TEB_AMD_ERR_HIP, "teb_amd_explore_candidates_per_scene: candidate scratch allocation failed"); }
+  A(ensure(F.ex_sig, std::max<size_t>(values, 2)));
+  A(ensure(F.ex_map, (size_t)h->max_tebs));
+  if (F.ex_orient.n < 2 * (size_t)h->max_tebs) { A(F.ex_rec.alloc(h->max_tebs)); A(F.ex_orient.alloc(2 * (size_t)h->max_tebs)); }
+  if (!A.ok()) { (void)hipGetLastError(); return fail(TEB_AMD_ERR_HIP, "teb_amd_explore_candidates_per_scene: candidate scratch allocation failed"); }
   return TEB_AMD_OK;
 }
 
@@ -2604,8 +2547,7 @@ struct TickPlanner {
 struct TickScratch { BatchDev cand; int *map, *off; double *px, *py, *sig; };
 
 // tebs_.push_back(candidate) for the accepted candidates acc of a launch: bands of the scratch strips `cand` -> the next slots of the
-// batch in one gather, with the defaults of a new TebOptimalPlanner as arrays - born without via-points, its constructor gets none -,
-// setVelocityStart / setVelocityGoalFree of their planner and, in a scene set, their entries of the band -> scene map
+// batch in one gather, with BandAttrs::candidate of their planner as arrays and, in a scene set, their entries of the band -> scene map
 int append_candidates(teb_amd_handle* h, const TickScratch& sc, const std::vector<int>& acc, const std::vector<int>& who,
                       std::vector<TickPlanner>& P, int free_goal_vel) {
   if (acc.empty()) return TEB_AMD_OK;
@@ -2613,21 +2555,20 @@ int append_candidates(teb_amd_handle* h, const TickScratch& sc, const std::vecto
   const bool scene_map = F.n_scenes > 0;   // a scene set: planner s = scene s (the single scene keeps no map)
   const int slot0 = h->B, cnt = (int)acc.size();
   if (slot0 + cnt > h->max_tebs) return fail(TEB_AMD_ERR_CAPACITY, "more bands than max_tebs");   // (excluded by the slot limits)
-  std::vector<int> ones(cnt, 1), rot(cnt, TEB_AMD_ROT_NONE), hvg(cnt, free_goal_vel ? 0 : 1), zero(cnt, 0);
-  std::vector<double> vv(3 * (size_t)cnt, 0.0), z3(3 * (size_t)cnt, 0.0);
+  BandAttrArrays at((size_t)cnt);
   for (int k = 0; k < cnt; ++k) {
     TickPlanner& t = P[who[acc[k]]];
-    if (t.start_vel) for (int j = 0; j < 3; ++j) vv[3 * k + j] = t.start_vel[j];
+    at.set((size_t)k, BandAttrs::candidate(t.start_vel, free_goal_vel));
     if (scene_map) F.band_scene[slot0 + k] = who[acc[k]];
     t.bands.push_back(slot0 + k);
   }
-  HIPCHK(hipMemcpyAsync(h->has_vs.p + slot0, ones.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->has_vg.p + slot0, hvg.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->rotdir.p + slot0, rot.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->via_en.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->optimized.p + slot0, zero.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->vs.p + 3 * (size_t)slot0, vv.data(), vv.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->vg.p + 3 * (size_t)slot0, z3.data(), z3.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.has_vs.p + slot0, at.has_vs.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.has_vg.p + slot0, at.has_vg.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.rotdir.p + slot0, at.rotdir.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.via_en.p + slot0, at.via_en.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.optimized.p + slot0, at.optimized.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.vs.p + 3 * (size_t)slot0, at.vs.data(), at.vs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.vg.p + 3 * (size_t)slot0, at.vg.data(), at.vg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   if (scene_map) HIPCHK(hipMemcpyAsync(F.scene_of.p + slot0, F.band_scene.data() + slot0, cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(sc.map, acc.data(), cnt * sizeof(int), hipMemcpyHostToDevice, h->stream));
   h->B = slot0 + cnt;
@@ -2881,12 +2822,12 @@ int finish_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, std::vector<Ti
   if (!any) return TEB_AMD_OK;
   std::vector<int> ve(h->B, 0);
   if (P.size() > 1) {   // the bands of a planner whose rule does not run keep their flags
-    HIPCHK(hipMemcpyAsync(ve.data(), h->via_en.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(ve.data(), h->bands.via_en.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
   }
   for (size_t i = 0; i < P.size(); ++i)
     for (size_t b = 0; b < rule[i].size(); ++b) ve[P[i].bands[b]] = rule[i][b];
-  HIPCHK(hipMemcpyAsync(h->via_en.p, ve.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.via_en.p, ve.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   return synced(h);
 }
 
@@ -2937,8 +2878,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
                           best >= 0 && best < h->B ? rows[best] : nullptr, h->memory);
   h->bands_changed();   // the batch is about to change: signatures have to be recomputed before the next filter call
   SingleRoute R{h, p, {batch_of(h), h->cand_map.p, h->cand_off.p, h->cand_px.p, h->cand_py.p, h->cand_sig.p}, kCandChunk};
-  BatchDev& c = R.sc.cand;   // the scratch strips seen as a batch of kCandChunk bands
-  c.B = kCandChunk; c.n = h->cand_n.p; c.x = h->cand_x.p; c.y = h->cand_y.p; c.th = h->cand_th.p; c.dt = h->cand_dt.p;
+  h->cand.into(R.sc.cand);   // the scratch strips seen as a batch of kCandChunk bands
   if ((rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths))) return rc;
   if (n_total) *n_total = h->B;
   return finish_tick(h, p, P);
@@ -3022,8 +2962,8 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
   }
   h->bands_changed();   // the batch is about to change
   FleetRoute R{h, p, {batch_of(h), F.ex_map.p, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_sig.p}, q, {}, {}, {}, {}};
-  BatchDev& c = R.sc.cand;   // the scratch strips of the scene set seen as a batch of K bands
-  c.B = (int)K; c.n = F.ex_n.p; c.x = F.ex_x.p; c.y = F.ex_y.p; c.th = F.ex_th.p; c.dt = F.ex_dt.p;
+  F.ex.into(R.sc.cand);   // the scratch strips of the scene set seen as a batch of K bands (they may hold more)
+  R.sc.cand.B = (int)K;
   rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths);
   if (n_total) *n_total = h->B;
   for (int s = 0; s < ns; ++s) if (n_bands) n_bands[s] = (int)P[s].bands.size();
@@ -3045,28 +2985,15 @@ namespace {
 // and their entries of the band -> scene map; B = K afterwards.
 int compact_by_map(teb_amd_handle* h, const std::vector<int>& map) {
   const int B = h->B;
-  if (!h->tmp_ready) {
-    const size_t BS = (size_t)h->max_tebs * h->stride;
-    bool ok = true;
-    auto A = [&](hipError_t e) { if (e != hipSuccess) ok = false; };
-    A(h->tmp_x.alloc(BS)); A(h->tmp_y.alloc(BS)); A(h->tmp_th.alloc(BS)); A(h->tmp_dt.alloc(BS)); A(h->tmp_n.alloc(h->max_tebs));
-    A(h->tmp_vs.alloc(3 * (size_t)h->max_tebs)); A(h->tmp_vg.alloc(3 * (size_t)h->max_tebs)); A(h->tmp_i.alloc(9 * (size_t)h->max_tebs));
-    A(h->tmp_chi2.alloc(h->max_tebs)); A(h->tmp_cost.alloc(h->max_tebs)); A(h->tmp_lambda.alloc(h->max_tebs));
-    if (!h->cand_ready && ensure_candidate_buffers(h) != TEB_AMD_OK) ok = false;
-    if (!ok) return fail(TEB_AMD_ERR_HIP, "compaction scratch allocation failed");
-    h->tmp_ready = true;
+  if (!h->tmp.allocated()) {
+    if (ensure_candidate_buffers(h) != TEB_AMD_OK || h->tmp.alloc(h->max_tebs, h->stride) != hipSuccess) return fail(TEB_AMD_ERR_HIP, "compaction scratch allocation failed");
   }
   const int K = (int)map.size();
   bool identity = true;
   for (int k = 0; k < K; ++k) if (map[k] != k) identity = false;
   if (!identity && K > 0) {
     BatchDev src = batch_of(h), tmp = src;
-    tmp.n = h->tmp_n.p; tmp.x = h->tmp_x.p; tmp.y = h->tmp_y.p; tmp.th = h->tmp_th.p; tmp.dt = h->tmp_dt.p;
-    tmp.has_vs = h->tmp_i.p; tmp.has_vg = h->tmp_i.p + h->max_tebs; tmp.rotdir = h->tmp_i.p + 2 * (size_t)h->max_tebs;
-    tmp.via_en = h->tmp_i.p + 3 * (size_t)h->max_tebs; tmp.status = h->tmp_i.p + 4 * (size_t)h->max_tebs;
-    tmp.iters = h->tmp_i.p + 5 * (size_t)h->max_tebs; tmp.trials = h->tmp_i.p + 6 * (size_t)h->max_tebs;
-    tmp.optimized = h->tmp_i.p + 7 * (size_t)h->max_tebs; tmp.last_iters = h->tmp_i.p + 8 * (size_t)h->max_tebs;
-    tmp.vs = h->tmp_vs.p; tmp.vg = h->tmp_vg.p; tmp.chi2 = h->tmp_chi2.p; tmp.cost = h->tmp_cost.p; tmp.lambda = h->tmp_lambda.p;
+    h->tmp.view(tmp);
     std::vector<int> ident(K);
     for (int k = 0; k < K; ++k) ident[k] = k;
     HIPCHK(hipMemcpyAsync(h->cand_map.p, map.data(), K * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -3114,7 +3041,7 @@ int detour_statistics(teb_amd_handle* h, const teb_amd_hcp_params_t* p, int B, s
   st.assign((size_t)4 * B, 0.0);
   opt.assign(B, 0);
   HIPCHK(hipMemcpyAsync(st.data(), h->cand_sig.p, st.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-  HIPCHK(hipMemcpyAsync(opt.data(), h->optimized.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(opt.data(), h->bands.optimized.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return synced(h);
 }
 
@@ -3182,7 +3109,7 @@ int teb_amd_set_optimized_flags(teb_amd_handle_t* h, const int32_t* flags) {
   if (h->B <= 0) return TEB_AMD_OK;
   std::vector<int> f(h->B);
   for (int b = 0; b < h->B; ++b) f[b] = flags[b] != 0;
-  HIPCHK(hipMemcpyAsync(h->optimized.p, f.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.optimized.p, f.data(), h->B * sizeof(int), hipMemcpyHostToDevice, h->stream));
   return synced(h);
 }
 
@@ -3191,7 +3118,7 @@ int teb_amd_get_optimized_flags(teb_amd_handle_t* h, int32_t* flags) {
   if (rc) return rc;
   if (!flags) return fail(TEB_AMD_ERR_INVALID_ARG, "null flags");
   if (h->B <= 0) return TEB_AMD_OK;
-  HIPCHK(hipMemcpyAsync(flags, h->optimized.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipMemcpyAsync(flags, h->bands.optimized.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return synced(h);
 }
 
@@ -3199,16 +3126,16 @@ int teb_amd_get_band_flags(teb_amd_handle_t* h, int32_t* via_points_enabled, int
   int rc = check_handle(h);
   if (rc) return rc;
   if (h->B <= 0) return TEB_AMD_OK;
-  if (via_points_enabled) HIPCHK(hipMemcpyAsync(via_points_enabled, h->via_en.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (has_vel_start) HIPCHK(hipMemcpyAsync(has_vel_start, h->has_vs.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-  if (has_vel_goal) HIPCHK(hipMemcpyAsync(has_vel_goal, h->has_vg.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (via_points_enabled) HIPCHK(hipMemcpyAsync(via_points_enabled, h->bands.via_en.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (has_vel_start) HIPCHK(hipMemcpyAsync(has_vel_start, h->bands.has_vs.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+  if (has_vel_goal) HIPCHK(hipMemcpyAsync(has_vel_goal, h->bands.has_vg.p, h->B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   return synced(h);
 }
 
 int teb_amd_device_state(teb_amd_handle_t* h, void** x, void** y, void** theta, void** dt, void** n, int32_t* stride) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if (x) *x = h->x.p; if (y) *y = h->y.p; if (theta) *theta = h->th.p; if (dt) *dt = h->dt.p; if (n) *n = h->n.p;
+  if (x) *x = h->bands.strips.x.p; if (y) *y = h->bands.strips.y.p; if (theta) *theta = h->bands.strips.th.p; if (dt) *dt = h->bands.strips.dt.p; if (n) *n = h->bands.strips.n.p;
   if (stride) *stride = h->stride;
   h->bands_changed();   // the caller may write pose counts through `n`: the host's upper bound is void from here on (the kernel guards
                         // itself against counts beyond its LDS strips as well)
@@ -3255,8 +3182,8 @@ int teb_amd_last_kernel_ms(teb_amd_handle_t* h, float* ms) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (!ms || !h->timed) return fail(TEB_AMD_ERR_INVALID_ARG, "no kernel has been launched yet");
-  HIPCHK(hipEventSynchronize(h->ev1));
-  HIPCHK(hipEventElapsedTime(ms, h->ev0, h->ev1));
+  HIPCHK(hipEventSynchronize(h->ev1.e));
+  HIPCHK(hipEventElapsedTime(ms, h->ev0.e, h->ev1.e));
   return TEB_AMD_OK;
 }
 
@@ -3297,23 +3224,23 @@ int teb_amd_debug_linearize(teb_amd_handle_t* h, int32_t b, double weight_multip
   bt.via_pose += (size_t)b * bt.via_cap; bt.Hbackup += (size_t)b * h->hmat_stride;
   // results of TEB b must not be clobbered by the debug run: save and restore them
   int sv_i[3]; double sv_d[3];
-  HIPCHK(hipMemcpy(&sv_i[0], h->status.p + b, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&sv_i[1], h->iters.p + b, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&sv_i[2], h->trials.p + b, sizeof(int), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&sv_d[0], h->chi2.p + b, sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&sv_d[1], h->cost.p + b, sizeof(double), hipMemcpyDeviceToHost));
-  HIPCHK(hipMemcpy(&sv_d[2], h->lambda.p + b, sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&sv_i[0], h->bands.status.p + b, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&sv_i[1], h->bands.iters.p + b, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&sv_i[2], h->bands.trials.p + b, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&sv_d[0], h->bands.chi2.p + b, sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&sv_d[1], h->bands.cost.p + b, sizeof(double), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&sv_d[2], h->bands.lambda.p + b, sizeof(double), hipMemcpyDeviceToHost));
   HIPCHK(launch_opt(h, 1, sc, bt, a, h->layout.solver, h->layout.plan));
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(h->stream));
-  HIPCHK(hipMemcpy(h->status.p + b, &sv_i[0], sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->iters.p + b, &sv_i[1], sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->trials.p + b, &sv_i[2], sizeof(int), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->chi2.p + b, &sv_d[0], sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->cost.p + b, &sv_d[1], sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->lambda.p + b, &sv_d[2], sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->bands.status.p + b, &sv_i[0], sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->bands.iters.p + b, &sv_i[1], sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->bands.trials.p + b, &sv_i[2], sizeof(int), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->bands.chi2.p + b, &sv_d[0], sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->bands.cost.p + b, &sv_d[1], sizeof(double), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(h->bands.lambda.p + b, &sv_d[2], sizeof(double), hipMemcpyHostToDevice));
   int n = 0;
-  HIPCHK(hipMemcpy(&n, h->n.p + b, sizeof(int), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(&n, h->bands.strips.n.p + b, sizeof(int), hipMemcpyDeviceToHost));
   const int Nt = 4 * n;
   std::vector<double> Hb((size_t)Nt * kBand), bv(Nt);
   HIPCHK(hipMemcpy(Hb.data(), h->dbg_H.p, Hb.size() * sizeof(double), hipMemcpyDeviceToHost));
@@ -3370,7 +3297,6 @@ int teb_amd_debug_distance(teb_amd_handle_t* h, int32_t nq, const int32_t* obst_
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipMemcpy(dist, d_dist.p, nq * sizeof(double), hipMemcpyDeviceToHost));
   if (grad) HIPCHK(hipMemcpy(grad, d_grad.p, 3 * (size_t)nq * sizeof(double), hipMemcpyDeviceToHost));
-  d_oi.free(); d_st.free(); d_x.free(); d_y.free(); d_th.free(); d_t.free(); d_dist.free(); d_grad.free();
   return TEB_AMD_OK;
 }
 
@@ -3466,7 +3392,6 @@ int teb_amd_debug_stream(teb_amd_handle_t* h, int64_t n_doubles, int32_t repeats
     LAUNCH(stream_kernel, dim3(2048), dim3(256), 0, h->stream, a.p, b.p, (size_t)n_doubles);
   }
   HIPCHK(hipStreamSynchronize(h->stream));
-  a.free(); b.free();
   return TEB_AMD_OK;
 }
 
@@ -3476,7 +3401,7 @@ int teb_amd_debug_poke_pose_count(teb_amd_handle_t* h, int32_t b, int32_t n) {
   int rc = check_handle(h);
   if (rc) return rc;
   if (b < 0 || b >= h->max_tebs) return fail(TEB_AMD_ERR_INVALID_ARG, "band index out of range");
-  HIPCHK(hipMemcpyAsync(h->n.p + b, &n, sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->bands.strips.n.p + b, &n, sizeof(int), hipMemcpyHostToDevice, h->stream));
   return synced(h);
 }
 
@@ -3485,7 +3410,7 @@ int teb_amd_debug_poke_pose_count(teb_amd_handle_t* h, int32_t b, int32_t n) {
 int teb_amd_debug_mcu_watchdog(teb_amd_handle_t* h, int32_t milliseconds) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if (milliseconds > 0 && !h->mcu_trace) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->mcu_trace), 1024 * sizeof(unsigned), hipHostMallocMapped));
+  if (milliseconds > 0 && !h->mcu_trace.p) HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h->mcu_trace.p), 1024 * sizeof(unsigned), hipHostMallocMapped));
   h->mcu_watchdog_ms = milliseconds;
   return TEB_AMD_OK;
 }

@@ -1,17 +1,75 @@
 // teb_scene_store.hpp — ONE obstacle table, host side and device side, for the single scene of a handle and for a scene set (fleet
 // batches, teb_fleet.hpp) alike. The host part (HostObst, its parse, the lists derived from it, the segments of a scene set) is plain
-// C++ over include/teb_amd.h: tests/host/scene_table_check.cpp compiles it alone with -DTEB_SCENE_STORE_HOST_ONLY. The device part
-// (DevBuf, DevSceneStore) needs the HIP runtime and SceneDev.
+// C++ over include/teb_amd.h: tests/host/scene_table_check.cpp compiles it alone with -DTEB_SCENE_STORE_HOST_ONLY. So is DevBuf, the
+// owner of every device allocation of the library, over two primitives its includer defines. The device part (DevSceneStore) needs the
+// HIP runtime and SceneDev.
 #pragma once
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <limits>
 #include <vector>
+#ifndef TEB_SCENE_STORE_HOST_ONLY
+#include <hip/hip_runtime.h>
+#endif
 
 #include "../../include/teb_amd.h"
 
 namespace tebamd {
+
+// ---- device memory that owns itself -----------------------------------------------------------------------------------------------
+// The two primitives every DevBuf goes through, DEFINED BY THE INCLUDER: teb_amd.hip with hipMalloc / hipFree, the host check
+// (tests/host/band_store_check.cpp) with counters. DevError is hipError_t, or int without HIP; 0 is success (hipSuccess) in both.
+#ifdef TEB_SCENE_STORE_HOST_ONLY
+using DevError = int;
+#else
+using DevError = hipError_t;
+#endif
+constexpr DevError kDevOk = DevError{};
+DevError device_allocate(void** p, size_t bytes);
+void device_free(void* p);
+
+// `count` elements of device memory, owned: freed by the destructor, by free(), by an alloc() over it and by a move onto it. Move-only,
+// so nothing frees a buffer twice. No DevBuf may have static storage duration: its destructor would run after the runtime's own teardown.
+template <typename T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) { free(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; }
+    return *this;
+  }
+  ~DevBuf() { free(); }
+  // (count 0: one element, so that p is an address; a failure leaves the buffer empty)
+  DevError alloc(size_t count) {
+    free();
+    void* q = nullptr;
+    const DevError e = device_allocate(&q, (count ? count : 1) * sizeof(T));
+    if (e == kDevOk) { p = static_cast<T*>(q); n = count; }
+    return e;
+  }
+  void free() {
+    if (p) device_free(p);
+    p = nullptr; n = 0;
+  }
+};
+// scratch that only grows: b holds at least count elements afterwards (its contents are lost when it grows)
+template <typename T>
+DevError ensure(DevBuf<T>& b, size_t count) {
+  return b.n >= count ? kDevOk : b.alloc(count);
+}
+// A run of allocations that belong together: A(buf.alloc(..)) for each, then ok() / first (the first failure). What to do about a
+// failure - free the set, fail the call - is the caller's.
+struct AllocRun {
+  DevError first = kDevOk;
+  void operator()(DevError e) { if (first == kDevOk) first = e; }
+  bool ok() const { return first == kDevOk; }
+};
 
 // How long a column of an obstacle table is: one entry per row, one per row + 1 (first-vertex offsets), one per polygon vertex.
 enum class ColumnExtent { Rows, Voff, Verts };
@@ -174,36 +232,10 @@ inline std::vector<SceneSegment> scene_segments(const HostObst* tabs, const int*
 }  // namespace tebamd
 
 #ifndef TEB_SCENE_STORE_HOST_ONLY
-#include <hip/hip_runtime.h>
-
 #include "teb_device.hpp"
 #include "teb_costmap_pods.hpp"   // CmoRows
 
 namespace tebamd {
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    n = count;
-    if (count == 0) count = 1;
-    return hipMalloc(reinterpret_cast<void**>(&p), count * sizeof(T));
-  }
-  void free() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-  }
-};
-template <class... Bufs>
-void free_all(Bufs&... bufs) { (bufs.free(), ...); }
-// scratch that only grows: b holds at least count elements afterwards (its contents are lost when it grows)
-template <typename T>
-hipError_t ensure(DevBuf<T>& b, size_t count) {
-  if (b.n >= count) return hipSuccess;
-  b.free();
-  return b.alloc(count);
-}
 
 // count elements to the device on the stream (none: nothing enqueued); src is read until the stream is synchronised
 template <typename T>
@@ -223,18 +255,13 @@ struct DevSceneStore {
   // rows / verts / vias: capacities; voff_extra: offsets beyond one per row (1 for a table, one per scene for a scene set); pad:
   // elements past every buffer, so that the segment of an empty scene at the very end still points at storage
   bool alloc(size_t rows, size_t voff_extra, size_t verts, size_t vias, size_t pad) {
-    bool ok = true;
+    AllocRun A;
     rows += pad;
     for_each_column(*this, *this, [&](auto& c, auto&, ColumnExtent e) {
-      ok = c.alloc(e == ColumnExtent::Rows ? rows : e == ColumnExtent::Voff ? rows + voff_extra : verts + pad) == hipSuccess && ok;
+      A(c.alloc(e == ColumnExtent::Rows ? rows : e == ColumnExtent::Voff ? rows + voff_extra : verts + pad));
     });
-    ok = stat.alloc(rows) == hipSuccess && ok; ok = dynidx.alloc(rows) == hipSuccess && ok; ok = list.alloc(5 * rows) == hipSuccess && ok;
-    ok = viax.alloc(vias + pad) == hipSuccess && ok; ok = viay.alloc(vias + pad) == hipSuccess && ok;
-    return ok;
-  }
-  void free() {
-    for_each_column(*this, *this, [](auto& c, auto&, ColumnExtent) { c.free(); });
-    free_all(stat, dynidx, list, viax, viay);
+    A(stat.alloc(rows)); A(dynidx.alloc(rows)); A(list.alloc(5 * rows)); A(viax.alloc(vias + pad)); A(viay.alloc(vias + pad));
+    return A.ok();
   }
   // Enqueues the columns of t: rows from first_row on, its offsets from first_voff on, its vertices from first_vert on. The copies
   // read t until the stream is synchronised.

@@ -1,4 +1,4 @@
-"""What the refactor benches share (tools/renew_refactor_bench.py): a cell is run three times - the parent's library (TEB_AMD_LIB), this
+"""What the refactor benches share (tools/renew_refactor_bench.py, tools/handle_refactor_bench.py): a cell is run three times - the parent's library (TEB_AMD_LIB), this
 build, the parent's again -, each in a process of its own under a time limit; a cell is level if this build lies no further above the
 parent's slower run than the parent's two runs lie apart; every cell that is not gets a second pass in fresh processes. A process that
 fails or passes its limit ends the run. The table is rewritten after every cell, so what is measured survives a later failure."""
