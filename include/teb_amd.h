@@ -669,12 +669,49 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  * ---- Fleet batches: the bands of many scenes in ONE launch -----------------------------------------------------------------------
  * A handle can hold a SET of scenes (an obstacle table and a via-point list each) and a band -> scene map; teb_amd_optimize_batch then
  * runs every band against its own scene, one workgroup per band, one launch. Many robots with a few candidates each fill the device
- * the way one robot's candidates cannot. Configuration and footprint stay per handle (a homogeneous fleet).
+ * the way one robot's candidates cannot. Without a class map (teb_amd_set_scene_configs, below) every scene runs under the handle's
+ * configuration and footprint; with one, every scene runs under the configuration of its robot class (a heterogeneous fleet).
  *
- * Contract: every band ends with the bits it has in a single-scene handle that holds only its scene, with the same capacities, layout
- * and the options generic_config_path = 1, multi_cu = -1, speculative_trials = -1 - provided that handle runs the same distance path
- * as the fleet: the point-like path iff EVERY scene and the footprint are point-like and the LDS cache of the largest scene fits,
- * the generic one otherwise (a point-like scene inside a generic fleet equals its handle with generic_distance_path = 1).
+ * Contract: every band ends with the bits it has in a single-scene handle that is created with the configuration of the band's scene
+ * (the handle's own without a class map, else that of the scene's class), holds only the band's scene, has the same capacities and
+ * layout and the options generic_config_path = 1, multi_cu = -1, speculative_trials = -1 - provided that handle runs the same
+ * distance path as the fleet: the point-like path iff the rows of EVERY scene and the footprint of EVERY class are point-like and the
+ * LDS cache of the largest scene fits, the generic one otherwise (a point-like scene or robot inside a generic fleet equals its
+ * handle with generic_distance_path = 1).
+ *
+ * Robot classes - a configuration and a footprint per scene. A robot class is one teb_amd_config_t, footprint included; the class map
+ * gives every scene of the set its class. Valid only while scenes are set.
+ *   teb_amd_set_scene_configs  installs n_classes >= 1 configurations and class_of_scene [n_scenes]; n_scenes must be the number of
+ *                            scenes set and every entry lie in [0, n_classes). Every configuration passes the checks of
+ *                            teb_amd_set_config. These fields must agree over the classes of one map, because one decision of the
+ *                            host covers the whole launch: jacobian_mode (TEB_AMD_JACOBIAN_ANALYTIC: fleet kernels exist for
+ *                            closed-form Jacobians) and include_dynamic_obstacles (the 2-D / 3-D kind of the per-scene signature
+ *                            calls is one per launch). What teb_amd_optimize_batch takes as arguments is one value per launch
+ *                            whatever the classes hold: the iteration counts, and for the costs of the bands obst_cost_scale,
+ *                            viapoint_cost_scale and alternative_time_cost - a caller who takes them from a configuration
+ *                            (selection_obst_cost_scale, selection_viapoint_cost_scale, selection_alternative_time_cost) passes
+ *                            ONE class's values, and the costs of every band are scaled by them; the library cannot check this.
+ *                            TEB_AMD_ERR_INVALID_ARG names the class and the field. Everything
+ *                            is checked before anything live is touched: on any error - a layout that cannot be had with the new
+ *                            footprints included - the previous map, or none, stays installed and the handle behaves as if the call
+ *                            had not been made. The lists of every scene are derived from its class; classes need not be used.
+ *                            The map has the lifetime of the scene count, like the remembered best class of a scene: kept across
+ *                            teb_amd_set_scenes and the two costmap routes when they install the same number of scenes (the new
+ *                            tables' lists are derived per class), forgotten by teb_amd_clear_scenes, by a set of another size and
+ *                            by teb_amd_clear_scene_configs. While a map is installed, fleet launches and the per-band rules below
+ *                            ignore the handle's own configuration; teb_amd_set_config still changes it - for single-scene mode
+ *                            and for after the map is cleared - and leaves the map alone.
+ *   teb_amd_clear_scene_configs  back to the handle's configuration for every scene. No map installed: no effect.
+ *   teb_amd_get_scene_configs  *n_classes (0 = no map; may be NULL); class_of_scene NULL: count only, else the class of every scene
+ *                            (capacity < n_scenes: TEB_AMD_ERR_CAPACITY).
+ * One class equal to the handle's configuration gives the bits of the same fleet without a map. What takes the class of the band's
+ * scene: the optimise launch, the lists teb_amd_set_scenes* derives, the consumers (velocity command, profile, full trajectory),
+ * teb_amd_select_best_per_scene (selection_cost_hysteresis, selection_prefer_initial_plan), teb_amd_has_diverged and
+ * teb_amd_get_batch_statistics (divergence_detection_*). A launch may change the pose counts when ANY class has teb_autosize. What
+ * reads nothing else of the configuration and works unchanged: the signature, class-filter, detour and compaction calls per scene.
+ * Limits: while a map with MORE THAN ONE class is installed, teb_amd_explore_candidates_per_scene returns TEB_AMD_ERR_UNSUPPORTED -
+ * its initialisers take max_vel_x, max_vel_theta, acc_lim_x, min_samples and weight_viapoint as scalars of the launch (with one class
+ * it runs under that class). teb_amd_is_trajectory_feasible_per_scene keeps its one footprint per call.
  *
  *   teb_amd_set_scenes       installs n_scenes scenes (1 <= n_scenes <= max_tebs) and enters fleet mode. The fleet storage is a second
  *                            set of device buffers, allocated at the first call and sized by the handle's capacities: sum of the rows
@@ -698,7 +735,8 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  *                            be NULL.
  *
  * A fleet launch has no helper workgroups, is never compiled at run time and follows the layout rules of teb_amd_optimize_batch (the
- * optimistic layout and its repeat use the largest scene). teb_amd_set_config re-derives the lists of every scene. Everything that
+ * optimistic layout and its repeat use the largest scene). teb_amd_set_config re-derives the lists of every scene (without a class map;
+ * with one the lists follow the classes and the call leaves them alone). Everything that
  * works on band b without the scene works unchanged (the three initialisers, update_and_prune, velocities, consumers, feasibility,
  * results, upload / download, snapshot / restore, teb_amd_compact_bands). The calls that read or write THE scene of the handle return
  * TEB_AMD_ERR_INVALID_ARG while scenes are set (call teb_amd_clear_scenes first): teb_amd_set_obstacles, both costmap routes,
@@ -822,6 +860,11 @@ int  teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32
 int  teb_amd_get_band_scenes(teb_amd_handle_t* h, int32_t* scene_of /* [capacity] or NULL */, int32_t capacity, int32_t* count);
 int  teb_amd_clear_scenes(teb_amd_handle_t* h);
 int  teb_amd_get_scene_count(teb_amd_handle_t* h, int32_t* n_scenes);
+int  teb_amd_set_scene_configs(teb_amd_handle_t* h, int32_t n_classes, const teb_amd_config_t* configs /* [n_classes] */,
+                               int32_t n_scenes, const int32_t* class_of_scene /* [n_scenes] */);
+int  teb_amd_clear_scene_configs(teb_amd_handle_t* h);
+int  teb_amd_get_scene_configs(teb_amd_handle_t* h, int32_t* n_classes, int32_t* class_of_scene /* [capacity] or NULL */,
+                               int32_t capacity);
 int  teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best, const int32_t* initial_plan,
                                    int32_t* best /* [n_scenes] */, double* best_cost);
 int  teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler, double* values, int64_t capacity_values,

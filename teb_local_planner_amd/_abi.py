@@ -351,3 +351,30 @@ def pack_scenes(tables, vias=None, max_tebs=None, max_obstacles=None, max_obstac
     for s, t in enumerate(tables):
         C.memmove(C.byref(arr, s * C.sizeof(Obstacles)), C.byref(t.freeze()), C.sizeof(Obstacles))
     return PackedScenes(arr, via_count, via_x, via_y, tables)
+
+
+class PackedSceneConfigs:
+    """What teb_amd_set_scene_configs takes: n_classes Config structs in one array and the class of every scene."""
+
+    def __init__(self, configs, class_of_scene):
+        self.n_classes, self.n_scenes = len(configs), len(class_of_scene)
+        self.configs, self.class_of_scene = configs, class_of_scene
+
+
+def pack_scene_configs(cfgs, class_of_scene, n_scenes=None):
+    """The arguments of teb_amd_set_scene_configs for a list of TebConfig (the robot classes) and the class of every scene. Pure (no
+    library call): no class, a class map whose length is not the number of scenes set (n_scenes, None = unknown) or an entry outside
+    the classes raise ValueError; what a configuration holds is checked by the library."""
+    cfgs = list(cfgs)
+    of = i32(class_of_scene)
+    if len(cfgs) < 1:
+        raise ValueError("pack_scene_configs: needs at least one class")
+    if of.ndim != 1 or (n_scenes is not None and len(of) != n_scenes):
+        raise ValueError("pack_scene_configs: %d class entries for %s scenes" % (of.size, n_scenes))
+    if len(of) and (of.min() < 0 or of.max() >= len(cfgs)):
+        raise ValueError("pack_scene_configs: class_of_scene holds %d .. %d, but there are %d classes" % (of.min(), of.max(), len(cfgs)))
+    arr = (Config * len(cfgs))()
+    for k, c in enumerate(cfgs):
+        one = c.to_c()
+        C.memmove(C.byref(arr, k * C.sizeof(Config)), C.byref(one), C.sizeof(Config))
+    return PackedSceneConfigs(arr, of)

@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libteb_amd.so")
 LIB_MFMA = os.path.join(HERE, "libteb_amd_mfma.so")
 HEADERS = ["teb_device.hpp", "teb_comm.hpp", "teb_feasibility.hpp", "teb_costmap_obstacles.hpp", "teb_costmap_polygons.hpp", "teb_plan_window.hpp", "teb_geometry.hpp", "teb_edges.hpp", "teb_kernel.hpp", "teb_strip.hpp",
-           "teb_hsig.hpp", "teb_graph.hpp", "teb_opt_launch.hpp", "teb_multicu.hpp", "teb_autoresize_chain.hpp", "teb_rtc.hpp", "teb_fleet.hpp", "teb_scene_store.hpp", "teb_band_store.hpp", "teb_hcp_host.hpp", "teb_costmap_host.hpp", "teb_costmap_pods.hpp", "teb_launch_host.hpp",
+           "teb_hsig.hpp", "teb_graph.hpp", "teb_opt_launch.hpp", "teb_multicu.hpp", "teb_autoresize_chain.hpp", "teb_rtc.hpp", "teb_fleet.hpp", "teb_scene_store.hpp", "teb_band_store.hpp", "teb_hcp_host.hpp", "teb_costmap_host.hpp", "teb_costmap_pods.hpp", "teb_launch_host.hpp", "teb_fleet_host.hpp",
            os.path.join("..", "..", "include", "teb_amd.h"), os.path.join("..", "..", "include", "teb_amd_debug.h")]
 
 # -ffp-contract=off: the parity contract is against a plain IEEE mul/add restatement of the reference;

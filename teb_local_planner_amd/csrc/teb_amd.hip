@@ -34,6 +34,7 @@
 #include "teb_hcp_host.hpp"
 #include "teb_costmap_host.hpp"
 #include "teb_launch_host.hpp"
+#include "teb_fleet_host.hpp"
 
 using namespace tebamd;
 
@@ -290,6 +291,10 @@ struct teb_amd_handle {
     DevBuf<int> scene_of, sel_last, sel_init, sel_idx;
     DevBuf<double> sel_cost;
     DevBuf<SceneDev> scenes;
+    // the table of robot classes a fleet launch reads (upload_class_table, the install, and nothing else writes them): the classes of
+    // the map and the class of every scene, or ONE class - the handle's configuration - and zeros [max_tebs]
+    DevBuf<teb_amd_config_t> cfgs;
+    DevBuf<int> class_of_scene;
     // equivalence classes per scene (teb_amd_compute_h_signatures_per_scene): state of the scene set, beside the single scene's
     // (sigs, hs_pre .. above), which the per-scene calls never touch
     DevBuf<double> hs_pre, hs_pim;   // 2-D: prod_l of every row of the set's store, each over the rows of its own scene
@@ -307,7 +312,11 @@ struct teb_amd_handle {
     bool allocated = false;
     std::vector<HostObst> tabs;     // host copy of every scene's table: teb_amd_set_config re-derives the lists from them
     std::vector<int> via_count;
-    std::vector<int> band_scene;    // [max_tebs] scene of every band (teb_amd_set_band_scenes); survives set / clear
+    // the class map (teb_amd_set_scene_configs): a configuration per robot class and the class of every scene; both empty = none, every
+    // scene runs under h->cfg. It has the lifetime of the scene count (forget_classes where new_planners forgets).
+    std::vector<teb_amd_config_t> classes;
+    std::vector<int> class_of;
+    std::vector<int> band_scene;   // [max_tebs] scene of every band (teb_amd_set_band_scenes); survives set / clear
     SceneLayout layout;             // of a fleet launch (the single-scene choice h->layout is not touched)
     bool hs_prod_valid = false;
     SignatureSet sigs;               // of the bands of the set, each as wide as its scene's table
@@ -352,6 +361,31 @@ BatchDev batch_of(teb_amd_handle* h) {
   b.clk = h->clk.p;
   return b;
 }
+
+// The class list something runs under (teb_fleet_host.hpp states the rules over it): the map of teb_amd_set_scene_configs with the class
+// of every scene, or ONE class - the handle's configuration - for every scene (class_of null). The single scene of the handle always
+// runs under own_class.
+struct ClassList {
+  const teb_amd_config_t* cfgs;
+  int n;
+  const int* class_of;   // [n_scenes], null: class 0
+  const teb_amd_config_t& of_scene(size_t s) const { return cfgs[class_of ? class_of[s] : 0]; }
+};
+ClassList own_class(const teb_amd_handle* h) { return ClassList{&h->cfg, 1, nullptr}; }
+ClassList fleet_classes(const teb_amd_handle* h) {
+  const auto& F = h->fleet;
+  return F.classes.empty() ? own_class(h) : ClassList{F.classes.data(), (int)F.classes.size(), F.class_of.data()};
+}
+// what the current mode runs under: the scene set's list in fleet mode, the handle's configuration else
+ClassList live_classes(const teb_amd_handle* h) { return h->fleet.n_scenes > 0 ? fleet_classes(h) : own_class(h); }
+// the configuration band b runs under: that of its scene's class in fleet mode (a band whose scene is not in the set: the handle's)
+const teb_amd_config_t& band_cfg(const teb_amd_handle* h, int b) {
+  const auto& F = h->fleet;
+  if (F.n_scenes <= 0 || (size_t)b >= F.band_scene.size() || F.band_scene[b] >= F.n_scenes) return h->cfg;
+  return fleet_classes(h).of_scene((size_t)F.band_scene[b]);
+}
+// a field the classes of one list agree on (fleet_classes_agree), for the scene set (by_scene) or the single scene
+const teb_amd_config_t& agreed_cfg(const teb_amd_handle* h, bool by_scene) { return by_scene ? fleet_classes(h).cfgs[0] : h->cfg; }
 
 int validate_config(const teb_amd_config_t* c) {
   if (c->footprint_type < TEB_AMD_FOOTPRINT_POINT || c->footprint_type > TEB_AMD_FOOTPRINT_POLYGON)
@@ -424,7 +458,8 @@ const void* fleet_kernel(int solver, int scene) {
   (void)solver; (void)scene;
   return nullptr;
 }
-// one workgroup per band, every band against fleet.scenes[fleet.scene_of[b]]: no helper workgroups, no run-time compilation
+// one workgroup per band, every band against fleet.scenes[fleet.scene_of[b]] under the configuration of that scene's class: no helper
+// workgroups, no run-time compilation
 hipError_t launch_fleet(teb_amd_handle* h, int grid, const BatchDev& bt, const OptArgs& a, int solver, const LdsPlan& plan) {
   const int scene_kind = h->fleet.layout.fast_points ? SCENE_POINTS : SCENE_GENERIC;
   const void* k = fleet_kernel(solver, scene_kind);
@@ -436,7 +471,9 @@ hipError_t launch_fleet(teb_amd_handle* h, int grid, const BatchDev& bt, const O
   fl.scenes = h->fleet.scenes.p; fl.scene_of = h->fleet.scene_of.p;
   McuDev none;
   std::memset(&none, 0, sizeof none);
-  void* params[] = {const_cast<teb_amd_config_t*>(&h->cfg), &fl, const_cast<BatchDev*>(&bt), const_cast<OptArgs*>(&a), const_cast<LdsPlan*>(&plan), &none};
+  const teb_amd_config_t* cfgs = h->fleet.cfgs.p;   // the class table (upload_class_table): the map's, or the handle's configuration alone
+  const int* class_of_scene = h->fleet.class_of_scene.p;
+  void* params[] = {&fl, const_cast<BatchDev*>(&bt), const_cast<OptArgs*>(&a), const_cast<LdsPlan*>(&plan), &none, &cfgs, &class_of_scene};
   return hipLaunchKernel(k, dim3(grid), dim3(kThreads), params, plan.total_bytes, h->stream);
 }
 // one workgroup per band (and its helper workgroups, mcu) against the scene sc, in the layout `solver` with its LDS plan
@@ -663,7 +700,7 @@ int launch(teb_amd_handle* h, const OptArgs& args) {
     }
     h->mcu_last_repeated = step.repeated;
     if (step.nmax_stale) h->nmax_known = -1;
-  } else if (h->cfg.teb_autosize && !args.debug_linearize) {
+  } else if (fleet_any_autosize(live_classes(h).cfgs, live_classes(h).n) && !args.debug_linearize) {
     h->nmax_known = -1;   // asynchronous launch: autoResize may change the pose counts
   }
   h->consumers_valid = false;
@@ -820,9 +857,9 @@ void teb_amd_destroy(teb_amd_handle_t* h) { delete h; }
 namespace {
 // The distance path and the layout of the tables of a scene store, for an obstacle cache of lay.max_cache entries (layout_per_table), and
 // what the answer needs: the HBM band buffer of a handle that was created without one, the LDS plan.
-int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, SceneLayout& lay) {
-  const TableLayout t = layout_per_table(pointlike_rows, h->cfg.footprint_type, h->opt.generic_distance_path != 0, h->solver_created, h->opt.layout,
-                                         lay.max_cache, h->stride, h->lds_limit, plan_bytes_of(h->lds_limit));
+int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, const ClassList& cl, SceneLayout& lay) {
+  const TableLayout t = fleet_layout_per_table(pointlike_rows, cl.cfgs, cl.n, h->opt.generic_distance_path != 0, h->solver_created, h->opt.layout,
+                                               lay.max_cache, h->stride, h->lds_limit, plan_bytes_of(h->lds_limit));
   if (t.hbm_band && h->hband_stride == 0) {
     h->hband_stride = ((size_t)hbo(4 * h->stride) + 2 + 1) & ~(size_t)1;
     HIPCHK(h->Hband.alloc((size_t)h->max_tebs * h->hband_stride));
@@ -832,13 +869,14 @@ int choose_scene_layout(teb_amd_handle* h, bool pointlike_rows, SceneLayout& lay
   lay.plan = make_lds_plan(h->stride, t.layout, t.cache_entries, h->lds_limit);
   return TEB_AMD_OK;
 }
-// (Re)derives everything that depends on BOTH obstacle tables and the configuration, for the ns tables `tabs` whose rows `store` holds
+// (Re)derives everything that depends on BOTH obstacle tables and the configuration, for the ns tables `tabs` - table s under the
+// configuration cl.of_scene(s), the distance path over every class of cl (teb_fleet_host.hpp) - whose rows `store` holds
 // one after the other (scene_segments; ONE table for the single scene of the handle): the lists AddEdgesObstacles /
 // AddEdgesDynamicObstacles visit and the obstacles in cache order, uploaded; the SceneDev of every table - each points at its own
 // segment with indices local to it, so the kernel's arithmetic is the single-scene one - into `scenes` and, for a fleet launch to index,
 // into `scenes_dev`; the distance path (point-like LDS cache, sized for the largest table, or generic) and the layout that goes with it
 // into `lay`; the static list of table 0 into `first_static`. Nothing is touched when the layout cannot be had.
-int commit_tables(teb_amd_handle* h, const HostObst* tabs, const int* via_count, size_t ns, DevSceneStore& store, SceneLayout& lay,
+int commit_tables(teb_amd_handle* h, const ClassList& cl, const HostObst* tabs, const int* via_count, size_t ns, DevSceneStore& store, SceneLayout& lay,
                   std::vector<SceneDev>& scenes, DevBuf<SceneDev>* scenes_dev, std::vector<int>* first_static) {
   const std::vector<SceneSegment> seg = scene_segments(tabs, via_count, ns);
   SceneLists all, d;   // all: the lists of every table at its segment
@@ -848,7 +886,7 @@ int commit_tables(teb_amd_handle* h, const HostObst* tabs, const int* via_count,
   scenes.assign(ns, SceneDev{});
   for (size_t s = 0; s < ns; ++s) {
     const size_t M = tabs[s].rows();
-    derive_scene_lists(h->cfg, tabs[s], d);
+    derive_scene_lists(cl.of_scene(s), tabs[s], d);
     all.st.resize(seg[s].row + M, 0); all.dy.resize(seg[s].row + M, 0);
     std::copy(d.st.begin(), d.st.end(), all.st.begin() + seg[s].row);
     std::copy(d.dy.begin(), d.dy.end(), all.dy.begin() + seg[s].row);
@@ -858,7 +896,7 @@ int commit_tables(teb_amd_handle* h, const HostObst* tabs, const int* via_count,
     scenes[s] = store.view(seg[s], (int)M, via_count[s], (int)d.st.size(), (int)d.dy.size(), d.static_radius_zero, 0);
     if (s == 0) st0 = d.st;
   }
-  if (int rc = choose_scene_layout(h, pointlike, chosen)) return rc;
+  if (int rc = choose_scene_layout(h, pointlike, cl, chosen)) return rc;
   for (auto& q : scenes) q.fast_points = chosen.fast_points;   // one distance path for the whole launch
   HIPCHK(store.upload_lists(h->stream, all));
   if (scenes_dev) HIPCHK(hipMemcpyAsync(scenes_dev->p, scenes.data(), ns * sizeof(SceneDev), hipMemcpyHostToDevice, h->stream));
@@ -870,7 +908,7 @@ int commit_tables(teb_amd_handle* h, const HostObst* tabs, const int* via_count,
 // the single scene: the table held in h->hob
 int commit_obstacles(teb_amd_handle* h) {
   std::vector<SceneDev> one;
-  if (int rc = commit_tables(h, &h->hob, &h->nvia, 1, h->scene, h->layout, one, nullptr, &h->host_static)) return rc;
+  if (int rc = commit_tables(h, own_class(h), &h->hob, &h->nvia, 1, h->scene, h->layout, one, nullptr, &h->host_static)) return rc;
   h->static_radius_zero = one[0].static_radius_zero; h->n_static = one[0].n_static; h->n_dyn = one[0].n_dyn;
   h->signatures_stale();   // signatures depend on the obstacle table and on include_dynamic_obstacles
   return TEB_AMD_OK;
@@ -880,12 +918,12 @@ int commit_fleet(teb_amd_handle* h) {
   auto& F = h->fleet;
   std::vector<SceneDev> views;
   F.sigs.clear(); F.hs_prod_valid = false;   // signatures depend on the tables of the set and on include_dynamic_obstacles
-  return commit_tables(h, F.tabs.data(), F.via_count.data(), F.tabs.size(), F.store, F.layout, views, &F.scenes, nullptr);
+  return commit_tables(h, fleet_classes(h), F.tabs.data(), F.via_count.data(), F.tabs.size(), F.store, F.layout, views, &F.scenes, nullptr);
 }
 // both, as far as they hold anything (teb_amd_set_config)
 int commit_all(teb_amd_handle* h) {
   int rc = h->M > 0 ? commit_obstacles(h) : TEB_AMD_OK;
-  if (!rc && h->fleet.n_scenes > 0) rc = commit_fleet(h);
+  if (!rc && h->fleet.n_scenes > 0 && h->fleet.classes.empty()) rc = commit_fleet(h);   // (with a class map the set's lists follow the classes)
   return rc;
 }
 
@@ -930,6 +968,8 @@ int check_best_per_scene(const BandGroups& G, const int32_t* best, const char* c
 }
 }  // namespace
 
+namespace { int upload_class_table(teb_amd_handle* h); }   // (fleet batches, below)
+
 int teb_amd_set_config(teb_amd_handle_t* h, const teb_amd_config_t* cfg) {
   int rc = check_handle(h);
   if (rc) return rc;
@@ -947,7 +987,9 @@ int teb_amd_set_config(teb_amd_handle_t* h, const teb_amd_config_t* cfg) {
     (void)commit_all(h);
     return fail(rc, why);
   }
-  return TEB_AMD_OK;
+  h->consumers_valid = false;
+  // a fleet without a class map launches under the handle's configuration as its one class (with a map the table is the map's)
+  return h->fleet.classes.empty() && std::memcmp(&previous, cfg, sizeof previous) != 0 ? upload_class_table(h) : TEB_AMD_OK;
 }
 
 namespace {
@@ -998,6 +1040,29 @@ int teb_amd_set_via_points(teb_amd_handle_t* h, int32_t count, const double* x, 
 // ---- fleet batches (teb_amd.h): a set of scenes and a band -> scene map ---------------------------------------------------------------
 namespace {
 constexpr size_t kFleetPad = 8;   // elements past every buffer of the scene set's store: the segment of an empty scene at the very end still points at storage
+// THE install of the class table a fleet launch reads: the classes of the map and the class of every scene, or - without a map - one
+// class, the handle's configuration, and a class array of zeros. Every change of either goes through here; nothing else writes the two
+// buffers. Before the fleet storage exists there is nothing to write (fleet_allocate comes through here).
+int upload_class_table(teb_amd_handle* h) {
+  auto& F = h->fleet;
+  if (!F.class_of_scene.p) return TEB_AMD_OK;
+  const ClassList cl = fleet_classes(h);
+  std::vector<int> of((size_t)h->max_tebs, 0);
+  if (cl.class_of) std::copy(F.class_of.begin(), F.class_of.end(), of.begin());   // (n_scenes <= max_tebs)
+  HIPCHK(ensure(F.cfgs, (size_t)cl.n));
+  HIPCHK(hipMemcpyAsync(F.cfgs.p, cl.cfgs, (size_t)cl.n * sizeof(teb_amd_config_t), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(F.class_of_scene.p, of.data(), of.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));   // `of` goes out of scope, the caller may change its configurations
+  h->consumers_valid = false;   // the consumers read the class of a band's scene
+  return TEB_AMD_OK;
+}
+// the map has the lifetime of the scene count: forgotten where the planners of the scenes are (new_planners)
+int forget_classes(teb_amd_handle* h) {
+  auto& F = h->fleet;
+  if (F.classes.empty()) return TEB_AMD_OK;
+  F.classes.clear(); F.class_of.clear();
+  return upload_class_table(h);
+}
 int fleet_allocate(teb_amd_handle* h) {
   auto& F = h->fleet;
   if (F.allocated) return TEB_AMD_OK;
@@ -1005,7 +1070,7 @@ int fleet_allocate(teb_amd_handle* h) {
   // (every scene has one first-vertex offset more than rows, and there are at most T scenes)
   AllocRun A;
   if (!F.store.alloc((size_t)std::max(h->max_obst, 0), T, (size_t)std::max(h->max_verts, 0), (size_t)std::max(h->max_via, 0), kFleetPad)) A(hipErrorOutOfMemory);
-  A(F.scenes.alloc(T)); A(F.scene_of.alloc(T)); A(F.sel_last.alloc(T)); A(F.sel_init.alloc(T)); A(F.sel_idx.alloc(T)); A(F.sel_cost.alloc(T));
+  A(F.scenes.alloc(T)); A(F.scene_of.alloc(T)); A(F.cfgs.alloc(1)); A(F.class_of_scene.alloc(T)); A(F.sel_last.alloc(T)); A(F.sel_init.alloc(T)); A(F.sel_idx.alloc(T)); A(F.sel_cost.alloc(T));
   const size_t rows = (size_t)std::max(h->max_obst, 0) + kFleetPad;   // one product per row of the set's store
   A(F.hs_pre.alloc(rows)); A(F.hs_pim.alloc(rows)); A(F.hs_pex.alloc(rows)); A(F.hs_off.alloc(T + 1));
 #ifdef TEB_AMD_HAS_FLEET_UNITS
@@ -1022,6 +1087,7 @@ int fleet_allocate(teb_amd_handle* h) {
     return fail(TEB_AMD_ERR_HIP, "teb_amd_set_scenes: device allocation of the fleet storage failed");
   }
   F.allocated = true;
+  if (int rc = upload_class_table(h)) { F.release(); return rc; }
   return TEB_AMD_OK;
 }
 // The tail of teb_amd_set_scenes and teb_amd_set_scenes_from_costmaps: the host tables of the n scenes exist and fit the capacities of the
@@ -1042,13 +1108,14 @@ int install_scene_set(teb_amd_handle* h, std::vector<HostObst>&& tabs, std::vect
   U(F.store.upload_vias(h->stream, via_x, via_y, vias));
   U(hipStreamSynchronize(h->stream));   // the uploads read `all` and the caller's arrays
   if (e != hipSuccess) {
-    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.new_planners(0);
+    F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.new_planners(0); (void)forget_classes(h);
     return fail(TEB_AMD_ERR_HIP, std::string("teb_amd_set_scenes: upload of the scene set -> ") + hipGetErrorString(e));
   }
   F.tabs = std::move(tabs);
   F.via_count = std::move(vc);
-  rc = commit_fleet(h);
-  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.new_planners(0); return rc; }
+  if (F.class_of.size() != (size_t)n_scenes && (rc = forget_classes(h))) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.new_planners(0); return rc; }   // the class map belongs to the scene count, like the planners below
+  rc = commit_fleet(h);   // (the lists of every scene from its class)
+  if (rc) { F.n_scenes = 0; F.tabs.clear(); F.via_count.clear(); F.new_planners(0); (void)forget_classes(h); return rc; }
   F.n_scenes = n_scenes;
   if (F.memory.size() != (size_t)n_scenes) F.new_planners(n_scenes);   // a remembered class belongs to a robot: kept while the fleet keeps its size
   return TEB_AMD_OK;
@@ -1079,6 +1146,7 @@ int teb_amd_set_band_scenes(teb_amd_handle_t* h, const int32_t* scene_of, int32_
   auto& F = h->fleet;
   F.band_scene.assign((size_t)h->max_tebs, 0);   // bands >= count: scene 0
   F.sigs.clear();   // per-scene signatures were computed against the previous map
+  h->consumers_valid = false;   // with a class map the consumers read the class of a band's scene
   std::copy(scene_of, scene_of + count, F.band_scene.begin());
   if (F.allocated) {
     HIPCHK(hipMemcpyAsync(F.scene_of.p, F.band_scene.data(), F.band_scene.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1104,7 +1172,7 @@ int teb_amd_clear_scenes(teb_amd_handle_t* h) {
   h->fleet.tabs.clear(); h->fleet.via_count.clear();
   h->fleet.sigs.clear(); h->fleet.hs_prod_valid = false;
   h->fleet.new_planners(0);
-  return TEB_AMD_OK;
+  return forget_classes(h);
 }
 
 int teb_amd_get_scene_count(teb_amd_handle_t* h, int32_t* n_scenes) {
@@ -1112,6 +1180,75 @@ int teb_amd_get_scene_count(teb_amd_handle_t* h, int32_t* n_scenes) {
   if (rc) return rc;
   if (!n_scenes) return fail(TEB_AMD_ERR_INVALID_ARG, "null output");
   *n_scenes = h->fleet.n_scenes;
+  return TEB_AMD_OK;
+}
+
+int teb_amd_set_scene_configs(teb_amd_handle_t* h, int32_t n_classes, const teb_amd_config_t* configs, int32_t n_scenes, const int32_t* class_of_scene) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_set_scene_configs"))) return rc;
+  auto& F = h->fleet;
+  if (n_classes < 1 || !configs || !class_of_scene) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_set_scene_configs: needs at least one class and a class for every scene");
+  char buf[256];
+  if (n_scenes != F.n_scenes) {
+    std::snprintf(buf, sizeof buf, "teb_amd_set_scene_configs: n_scenes = %d, but %d scenes are set", n_scenes, F.n_scenes);
+    return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+  }
+  // everything is checked before anything live is touched
+  for (int k = 0; k < n_classes; ++k)
+    if ((rc = validate_config(configs + k))) {
+      std::snprintf(buf, sizeof buf, "teb_amd_set_scene_configs: class %d: %s", k, g_last_error.c_str());
+      return fail(rc, buf);
+    }
+  if (const ClassRefusal r = fleet_classes_agree(configs, n_classes); !r.ok()) {
+    std::snprintf(buf, sizeof buf, "teb_amd_set_scene_configs: class %d: %s %s", r.cls, r.field, r.why);
+    return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+  }
+  if (const int s = first_scene_without_class(class_of_scene, n_scenes, n_classes); s >= 0) {
+    std::snprintf(buf, sizeof buf, "teb_amd_set_scene_configs: class_of_scene[%d] = %d is not one of the %d classes", s, class_of_scene[s], n_classes);
+    return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+  }
+  // the lists of every scene, the distance path and the layout under the new classes; a layout that cannot be had leaves nothing touched
+  // (commit_tables), anything later puts the previous map - or none - back together with what is derived from it
+  std::vector<teb_amd_config_t> prev_classes(configs, configs + n_classes);
+  std::vector<int> prev_of(class_of_scene, class_of_scene + n_scenes);
+  F.classes.swap(prev_classes); F.class_of.swap(prev_of);
+  if ((rc = commit_fleet(h)) || (rc = upload_class_table(h))) {
+    const std::string why = g_last_error;
+    F.classes.swap(prev_classes); F.class_of.swap(prev_of);
+    (void)commit_fleet(h);
+    (void)upload_class_table(h);
+    return fail(rc, why);
+  }
+  return TEB_AMD_OK;
+}
+
+int teb_amd_clear_scene_configs(teb_amd_handle_t* h) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  auto& F = h->fleet;
+  if (F.classes.empty()) return TEB_AMD_OK;
+  std::vector<teb_amd_config_t> prev_classes;
+  std::vector<int> prev_of;
+  F.classes.swap(prev_classes); F.class_of.swap(prev_of);
+  if ((F.n_scenes > 0 && (rc = commit_fleet(h))) || (rc = upload_class_table(h))) {   // the handle's footprint may not fit the layout: the map stays
+    const std::string why = g_last_error;
+    F.classes.swap(prev_classes); F.class_of.swap(prev_of);
+    if (F.n_scenes > 0) (void)commit_fleet(h);
+    (void)upload_class_table(h);
+    return fail(rc, why);
+  }
+  return TEB_AMD_OK;
+}
+
+int teb_amd_get_scene_configs(teb_amd_handle_t* h, int32_t* n_classes, int32_t* class_of_scene, int32_t capacity) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  const auto& F = h->fleet;
+  if (n_classes) *n_classes = (int32_t)F.classes.size();
+  if (!class_of_scene || F.classes.empty()) return TEB_AMD_OK;
+  if (capacity < (int32_t)F.class_of.size()) return fail(TEB_AMD_ERR_CAPACITY, "teb_amd_get_scene_configs: more scenes than capacity");
+  std::copy(F.class_of.begin(), F.class_of.end(), class_of_scene);
   return TEB_AMD_OK;
 }
 
@@ -1131,7 +1268,7 @@ int teb_amd_select_best_per_scene(teb_amd_handle_t* h, const int32_t* last_best,
   HIPCHK(hipMemcpyAsync(F.sel_last.p, lb.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemcpyAsync(F.sel_init.p, ip.data(), ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
   LAUNCH(select_best_per_scene_kernel, dim3(ns), dim3(kThreads), 0, h->stream, h->bands.cost.p, F.scene_of.p, h->B, F.sel_last.p, F.sel_init.p,
-         h->cfg.selection_cost_hysteresis, h->cfg.selection_prefer_initial_plan, F.sel_cost.p, F.sel_idx.p);
+         F.cfgs.p, F.class_of_scene.p, F.sel_cost.p, F.sel_idx.p);
   std::vector<double> cst(ns);
   HIPCHK(hipMemcpyAsync(best, F.sel_idx.p, ns * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(cst.data(), F.sel_cost.p, ns * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -1237,7 +1374,7 @@ int teb_amd_optimize_batch(teb_amd_handle_t* h, int32_t inner, int32_t outer, in
 #ifndef TEB_AMD_HAS_FLEET_UNITS
     return fail(TEB_AMD_ERR_UNSUPPORTED, "fleet launches exist in the product library only; this one is the variant built with [" TEB_AMD_VARIANT_DEFINES "]");
 #else
-    if (h->cfg.jacobian_mode != TEB_AMD_JACOBIAN_ANALYTIC)
+    if (!fleet_classes_agree(fleet_classes(h).cfgs, fleet_classes(h).n).ok())   // (a map was checked at its install: this is the handle's own configuration)
       return fail(TEB_AMD_ERR_INVALID_ARG, "fleet launches need jacobian_mode TEB_AMD_JACOBIAN_ANALYTIC");
     for (int b = 0; b < h->B; ++b)
       if (h->fleet.band_scene[b] >= h->fleet.n_scenes) {
@@ -1598,7 +1735,12 @@ int stage(teb_amd_handle* h, int n, const double* px, const double* py, const do
 int run_consumers(teb_amd_handle* h, int look_ahead, int prevent) {
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
   if (h->consumers_valid && h->consumers_la == look_ahead && h->consumers_prevent == prevent) return TEB_AMD_OK;
-  LAUNCH(consumers_kernel, dim3(h->B), dim3(kThreads), 0, h->stream, h->cfg, batch_of(h), look_ahead, prevent, h->out_cmd.p, h->out_prof.p, h->out_traj.p);
+  if (h->fleet.n_scenes > 0 && !h->fleet.classes.empty()) {   // a class map: every band under the configuration of its scene's class
+    if (int rc = check_band_scenes(h, h->B)) return rc;
+    LAUNCH(consumers_fleet_kernel, dim3(h->B), dim3(kThreads), 0, h->stream, h->fleet.cfgs.p, h->fleet.class_of_scene.p, h->fleet.scene_of.p, batch_of(h), look_ahead, prevent,
+           h->out_cmd.p, h->out_prof.p, h->out_traj.p);
+  } else
+    LAUNCH(consumers_kernel, dim3(h->B), dim3(kThreads), 0, h->stream, h->cfg, batch_of(h), look_ahead, prevent, h->out_cmd.p, h->out_prof.p, h->out_traj.p);
   h->consumers_valid = true; h->consumers_la = look_ahead; h->consumers_prevent = prevent;
   return TEB_AMD_OK;
 }
@@ -1761,13 +1903,14 @@ int teb_amd_has_diverged(teb_amd_handle_t* h, int32_t b, int32_t* diverged) {
   if (rc) return rc;
   if (b < 0 || b >= h->B || !diverged) return fail(TEB_AMD_ERR_INVALID_ARG, "TEB index out of range");
   *diverged = 0;
-  if (!h->cfg.divergence_detection_enable) return TEB_AMD_OK;
+  const teb_amd_config_t& c = band_cfg(h, b);   // of the band's class in fleet mode
+  if (!c.divergence_detection_enable) return TEB_AMD_OK;
   double chi2 = 0; int iters = 0, last = 0;
   HIPCHK(hipMemcpyAsync(&chi2, h->bands.chi2.p + b, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(&iters, h->bands.iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipMemcpyAsync(&last, h->bands.last_iters.p + b, sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
-  *diverged = diverged_rule(h->cfg, h->last_inner, iters, last, chi2);
+  *diverged = diverged_rule(c, h->last_inner, iters, last, chi2);
   return TEB_AMD_OK;
 }
 
@@ -1787,7 +1930,7 @@ int teb_amd_get_batch_statistics(teb_amd_handle_t* h, int32_t* available, double
   HIPCHK(hipMemcpyAsync(last.data(), h->bands.last_iters.p, B * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   for (int b = 0; b < B; ++b) {
-    available[b] = h->cfg.divergence_detection_enable && iters[b] > 0 && h->last_inner > 0;
+    available[b] = band_cfg(h, b).divergence_detection_enable && iters[b] > 0 && h->last_inner > 0;
     back_chi2[b] = (available[b] && last[b] == h->last_inner) ? chi2[b] : 0.0;
   }
   return TEB_AMD_OK;
@@ -1863,7 +2006,7 @@ int launch_signatures(teb_amd_handle* h, const FleetHsigDev* fl, const BatchDev&
   int widest = h->M;   // most rows of a table
   if (fl) { widest = 0; for (const HostObst& t : F.tabs) widest = std::max(widest, (int)t.rows()); }
   const size_t strip = (size_t)h->stride * sizeof(double);
-  if (h->cfg.include_dynamic_obstacles) {
+  if (agreed_cfg(h, fl != nullptr).include_dynamic_obstacles) {
     if (n_values == 0) return TEB_AMD_OK;
     const bool wide = hsig3d_wide(h->opt.hsig3d_kernel, (long long)n_values);
     const dim3 grid((widest + (wide ? kThreads : kHsTile) - 1) / (wide ? kThreads : kHsTile), count);
@@ -1889,7 +2032,7 @@ int launch_signatures(teb_amd_handle* h, const FleetHsigDev* fl, const BatchDev&
 // download. by_scene: against the tables of the scene set (the offsets go to the device for the 3-D kernels), else the single scene's.
 int compute_signatures(teb_amd_handle* h, SignatureSet& S, bool by_scene, std::vector<int> off, double prescaler) {
   auto& F = h->fleet;
-  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;   // homotopy_class_planner.hpp:50
+  const int mode = agreed_cfg(h, by_scene).include_dynamic_obstacles ? 3 : 2;   // homotopy_class_planner.hpp:50
   double* host = S.reserve(std::move(off));
   const size_t total = (size_t)S.off.back();
   FleetHsigDev fl;
@@ -1938,7 +2081,7 @@ int teb_amd_compute_h_signatures_per_scene(teb_amd_handle_t* h, double prescaler
   const int B = h->B;
   if ((rc = check_band_scenes(h, B))) return rc;
   std::vector<int> off(B + 1, 0);
-  for (int b = 0; b < B; ++b) off[b + 1] = off[b] + (h->cfg.include_dynamic_obstacles ? (int)F.tabs[F.band_scene[b]].rows() : 2);
+  for (int b = 0; b < B; ++b) off[b + 1] = off[b] + (agreed_cfg(h, true).include_dynamic_obstacles ? (int)F.tabs[F.band_scene[b]].rows() : 2);
   const int64_t total = off[B];
   if (n_values) *n_values = total;
   if (offset) std::copy(off.begin(), off.end(), offset);
@@ -2631,6 +2774,7 @@ struct FleetRoute {
   int per_round;           // paths per scene and round
   std::vector<int> off;    // staging of plans() and lines(): read by the stream until the synchronisation after the signatures
   std::vector<double> px, py, pyaw;
+  const teb_amd_config_t& cfg() const { return agreed_cfg(h, true); }   // the scene set's ONE class (more than one: the call is refused), or the handle's configuration
   int plans(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // addAndInitNewTeb(*initial_plan_, ...) of every scene
     auto& F = h->fleet;
     off.assign(1, 0); px.clear(); py.clear(); pyaw.clear();
@@ -2646,7 +2790,7 @@ struct FleetRoute {
     HIPCHK(hipMemcpyAsync(F.ex_pyaw.p, pyaw.data(), pyaw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
     hipLaunchKernelGGL(init_plan_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
-                       F.ex_pyaw.p, h->cfg.max_vel_x, h->cfg.max_vel_theta, p->global_plan_overwrite_orientation, h->cfg.min_samples,
+                       F.ex_pyaw.p, cfg().max_vel_x, cfg().max_vel_theta, p->global_plan_overwrite_orientation, cfg().min_samples,
                        p->allow_init_with_backwards_motion, h->err_flag.p);
     return TEB_AMD_OK;
   }
@@ -2657,8 +2801,8 @@ struct FleetRoute {
       for (int j = 0; j < 3; ++j) { px[6 * k + j] = P[who[k]].start[j]; px[6 * k + 3 + j] = P[who[k]].goal[j]; }
     HIPCHK(hipMemcpyAsync(F.ex_line.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-    hipLaunchKernelGGL(init_line_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, F.ex_line.p, 0.0, h->cfg.max_vel_x,
-                       h->cfg.min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
+    hipLaunchKernelGGL(init_line_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, F.ex_line.p, 0.0, cfg().max_vel_x,
+                       cfg().min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
     return TEB_AMD_OK;
   }
   int edges(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // every graph in one launch, one download
@@ -2696,7 +2840,7 @@ struct FleetRoute {
     auto& F = h->fleet;
     HIPCHK(hipMemcpyAsync(F.ex_scene.p, who.data(), who.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     hipLaunchKernelGGL(init_path_fleet_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
-                       F.ex_scene.p, F.ex_orient.p, h->cfg.max_vel_x, h->cfg.acc_lim_x, h->cfg.min_samples, p->allow_init_with_backwards_motion,
+                       F.ex_scene.p, F.ex_orient.p, cfg().max_vel_x, cfg().acc_lim_x, cfg().min_samples, p->allow_init_with_backwards_motion,
                        h->err_flag.p);
     return TEB_AMD_OK;
   }
@@ -2706,7 +2850,7 @@ struct FleetRoute {
     HIPCHK(hipMemcpyAsync(F.ex_scene.p, who.data(), who.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     FleetHsigDev fl;
     fl.scenes = F.scenes.p; fl.scene_of = F.ex_scene.p; fl.off = F.ex_soff.p;
-    if (h->cfg.include_dynamic_obstacles && total > 0)
+    if (agreed_cfg(h, true).include_dynamic_obstacles && total > 0)
       HIPCHK(hipMemcpyAsync(F.ex_soff.p, soff.data(), soff.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
     return launch_signatures(h, &fl, sc.cand, (int)who.size(), total, p->h_signature_prescaler, sc.sig);
   }
@@ -2810,14 +2954,14 @@ int explore_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, Route& R, std
 }
 
 // getInitialPlanTEB (:495-536) and updateReferenceTrajectoryViaPoints (:286-315) planner by planner after a tick; one upload of via_en
-int finish_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, std::vector<TickPlanner>& P) {
+int finish_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, std::vector<TickPlanner>& P, const teb_amd_config_t& cfg) {
   std::vector<std::vector<int>> rule(P.size());
   bool any = false;
   for (size_t i = 0; i < P.size(); ++i) {
     TickPlanner& t = P[i];
     const int n = (int)t.bands.size();
     if (t.initial_plan_teb) *t.initial_plan_teb = initial_plan_band(t.ct, *t.mem, n, t.created);
-    if (via_point_rule(t.ct, *t.mem, n, p->viapoints_all_candidates != 0, t.n_plan > 0, t.n_via, h->cfg.weight_viapoint, rule[i])) any = true;
+    if (via_point_rule(t.ct, *t.mem, n, p->viapoints_all_candidates != 0, t.n_plan > 0, t.n_via, cfg.weight_viapoint, rule[i])) any = true;
   }
   if (!any) return TEB_AMD_OK;
   std::vector<int> ve(h->B, 0);
@@ -2881,7 +3025,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
   h->cand.into(R.sc.cand);   // the scratch strips seen as a batch of kCandChunk bands
   if ((rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths))) return rc;
   if (n_total) *n_total = h->B;
-  return finish_tick(h, p, P);
+  return finish_tick(h, p, P, h->cfg);
 }
 
 int teb_amd_get_exploration_graph(teb_amd_handle_t* h, double* vx, double* vy, unsigned char* adjacency, int32_t capacity_vertices,
@@ -2901,6 +3045,8 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
   if ((rc = require_fleet_mode(h, "teb_amd_explore_candidates_per_scene"))) return rc;
   if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
   auto& F = h->fleet;
+  if (F.classes.size() > 1)   // the initialisers take max_vel_x, max_vel_theta, acc_lim_x, min_samples and weight_viapoint as scalars of the launch
+    return fail(TEB_AMD_ERR_UNSUPPORTED, "teb_amd_explore_candidates_per_scene: not available while a class map with more than one class is installed (teb_amd_set_scene_configs)");
   const int ns = F.n_scenes, B0 = h->B;
   std::vector<int> plan_off(ns + 1, 0);
   for (int s = 0; s < ns; ++s) {
@@ -2923,7 +3069,7 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
       return fail(TEB_AMD_ERR_CAPACITY, buf);
     }
   }
-  const int mode = h->cfg.include_dynamic_obstacles ? 3 : 2;
+  const int mode = agreed_cfg(h, true).include_dynamic_obstacles ? 3 : 2;
   int widest = 0;
   for (const HostObst& t : F.tabs) widest = std::max(widest, (int)t.rows());
   const int q = h->explore_quota > 0 ? h->explore_quota : kExploreQuota;
@@ -2968,7 +3114,7 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
   if (n_total) *n_total = h->B;
   for (int s = 0; s < ns; ++s) if (n_bands) n_bands[s] = (int)P[s].bands.size();
   if (rc) return rc;
-  return finish_tick(h, p, P);
+  return finish_tick(h, p, P, agreed_cfg(h, true));   // (one class at most: its weight_viapoint)
 }
 
 int teb_amd_get_exploration_graph_per_scene(teb_amd_handle_t* h, int32_t scene, double* vx, double* vy, unsigned char* adjacency,

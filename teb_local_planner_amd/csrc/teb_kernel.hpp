@@ -2992,9 +2992,9 @@ enum { SCENE_POINTS = 0, SCENE_GENERIC = 1, SCENE_POINTS_SMALL = 2, SCENE_GENERI
        SCENE_POINTS_CUSTOM = 12, SCENE_POINTS_SMALL_CUSTOM = 13, SCENE_GENERIC_CUSTOM = 14, SCENE_GENERIC_SMALL_CUSTOM = 15 };
 template <int SOLVER, int JMODE, int SCENE>
 __global__ void __launch_bounds__(kThreads)
-#ifdef TEB_AMD_FLEET   // fleet units (teb_fleet_inst.hip): a scene per band, picked below once the band index is known
-teb_optimize_kernel(const teb_amd_config_t c, const FleetDev fl, const BatchDev bt, const OptArgs args,
-                    const LdsPlan plan, const McuDev mc) {
+#ifdef TEB_AMD_FLEET   // fleet units (teb_fleet_inst.hip): a scene and a configuration per band, picked below once the band index is known
+teb_optimize_kernel(const FleetDev fl, const BatchDev bt, const OptArgs args, const LdsPlan plan, const McuDev mc,
+                    const teb_amd_config_t* __restrict__ cfgs, const int* __restrict__ class_of_scene) {
 #else
 teb_optimize_kernel(const teb_amd_config_t c, const SceneDev sc, const BatchDev bt, const OptArgs args,
                     const LdsPlan plan, const McuDev mc) {
@@ -3048,6 +3048,9 @@ teb_optimize_kernel(const teb_amd_config_t c, const SceneDev sc, const BatchDev 
 #ifdef TEB_AMD_FLEET   // uniform over the workgroup: the record arrives through scalar loads; nothing is written
   static_assert(!MCU, "fleet units are built for the kinds without helper workgroups");
   const SceneDev sc = fl.scenes[fl.scene_of[b]];
+  // the configuration of the scene's robot class (teb_amd_set_scene_configs; without a map: one class, the handle's configuration).
+  // Read-only kernel parameters, so the compiler may keep every read of the record on the scalar pipe.
+  const teb_amd_config_t& c = cfgs[class_of_scene[fl.scene_of[b]]];
 #endif
   if (b == 0 && tid == 0) { bt.clk[0] = clock64(); bt.clk[1] = wall_clock64(); }   // shader clock of this launch (a slow box is not a regression)
   const Lds l = carve(lds_base, plan, SOLVER == SOLVER_BANDG ? args.Hband + (size_t)b * args.hband_stride : nullptr, SOLVER == SOLVER_BANDG);

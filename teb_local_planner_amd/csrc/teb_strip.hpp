@@ -240,8 +240,8 @@ __device__ __forceinline__ void extract_velocity(const teb_amd_config_t& c, doub
 
 // getVelocityCommand (:1135-1168), getVelocityProfile (:1170-1196), getFullTrajectory (:1198-1247) of every band in one launch.
 // cmd [B][4] = (vx, vy, omega, ok); prof [B][(S+1)*3]; traj [B][S*7] = (x, y, theta, vx, vy, omega, time_from_start)
-__global__ void consumers_kernel(const teb_amd_config_t c, BatchDev bt, int look_ahead_poses, int prevent_near_goal, double* cmd,
-                                 double* prof, double* traj) {
+__device__ __forceinline__ void consumers_of_band(const teb_amd_config_t& c, const BatchDev& bt, int look_ahead_poses, int prevent_near_goal, double* cmd,
+                                                  double* prof, double* traj) {
   const int b = blockIdx.x, S = bt.stride;
   StripDev s = strip_of(bt, b);
   const int n = *s.n;
@@ -289,6 +289,17 @@ __global__ void consumers_kernel(const teb_amd_config_t c, BatchDev bt, int look
     }
     tr[7 * i] = s.x[i]; tr[7 * i + 1] = s.y[i]; tr[7 * i + 2] = s.th[i]; tr[7 * i + 3] = vx; tr[7 * i + 4] = vy; tr[7 * i + 5] = om;
   }
+}
+__global__ void consumers_kernel(const teb_amd_config_t c, BatchDev bt, int look_ahead_poses, int prevent_near_goal, double* cmd,
+                                 double* prof, double* traj) {
+  consumers_of_band(c, bt, look_ahead_poses, prevent_near_goal, cmd, prof, traj);
+}
+// ... of a fleet with a class map (teb_amd_set_scene_configs): band b under the configuration of its scene's class, as the fleet form of
+// teb_optimize_kernel takes it
+__global__ void consumers_fleet_kernel(const teb_amd_config_t* __restrict__ cfgs, const int* __restrict__ class_of_scene,
+                                       const int* __restrict__ scene_of, BatchDev bt, int look_ahead_poses, int prevent_near_goal, double* cmd,
+                                       double* prof, double* traj) {
+  consumers_of_band(cfgs[class_of_scene[scene_of[blockIdx.x]]], bt, look_ahead_poses, prevent_near_goal, cmd, prof, traj);
 }
 
 }  // namespace tebamd

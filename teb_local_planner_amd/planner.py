@@ -120,6 +120,10 @@ def lib():
             L.teb_amd_clear_scenes.argtypes = [vp]
             L.teb_amd_get_scene_count.argtypes = [vp, _abi.p_i32]
             L.teb_amd_select_best_per_scene.argtypes = [vp, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_f64]
+        if hasattr(L, "teb_amd_set_scene_configs"):   # robot classes: a configuration per scene of a fleet batch
+            L.teb_amd_set_scene_configs.argtypes = [vp, i32, C.POINTER(_abi.Config), i32, _abi.p_i32]
+            L.teb_amd_clear_scene_configs.argtypes = [vp]
+            L.teb_amd_get_scene_configs.argtypes = [vp, _abi.p_i32, _abi.p_i32, i32]
         if hasattr(L, "teb_amd_compute_h_signatures_per_scene"):   # equivalence classes per scene of a fleet batch
             L.teb_amd_compute_h_signatures_per_scene.argtypes = [vp, d, _abi.p_f64, C.c_int64, _abi.p_i32, C.POINTER(C.c_int64)]
             L.teb_amd_filter_equivalence_classes_per_scene.argtypes = [vp, d, _abi.p_i32, i32, _abi.p_i32, _abi.p_i32, _abi.p_i32]
@@ -225,6 +229,27 @@ class TebBatchSolver:
         n = C.c_int32(0)
         _chk(lib().teb_amd_get_scene_count(self._h, C.byref(n)), "teb_amd_get_scene_count")
         return n.value
+
+    def set_scene_configs(self, cfgs, class_of_scene):
+        """Installs the robot classes `cfgs` (TebConfig each, footprint included) and the class of every scene of the set
+        (teb_amd_set_scene_configs): every band then runs under the configuration of its scene's class. Lengths are checked here,
+        everything else by the library."""
+        p = _abi.pack_scene_configs(cfgs, class_of_scene, getattr(self, "_n_scenes", 0))
+        _chk(lib().teb_amd_set_scene_configs(self._h, p.n_classes, p.configs, p.n_scenes, _abi._ptr(p.class_of_scene, C.c_int32)),
+             "teb_amd_set_scene_configs")
+
+    def clear_scene_configs(self):
+        _chk(lib().teb_amd_clear_scene_configs(self._h), "teb_amd_clear_scene_configs")
+
+    def scene_configs(self):
+        """(number of classes, class of every scene [n_scenes]) of the installed class map; (0, empty) without one."""
+        n = C.c_int32(0)
+        _chk(lib().teb_amd_get_scene_configs(self._h, C.byref(n), None, 0), "teb_amd_get_scene_configs")
+        if n.value == 0:
+            return 0, np.zeros(0, np.int32)
+        of = np.zeros(max(self.max_tebs, 1), np.int32)
+        _chk(lib().teb_amd_get_scene_configs(self._h, C.byref(n), _abi._ptr(of, C.c_int32), len(of)), "teb_amd_get_scene_configs")
+        return n.value, of[:self.scene_count()].copy()
 
     def select_best_per_scene(self, last_best=None, initial_plan=None):
         """(best [n_scenes] band indices, -1 for a scene without bands; scaled costs [n_scenes]). last_best / initial_plan: band index
@@ -1145,19 +1170,41 @@ class TebOptimalPlanner:
 
 
 class TebFleetPlanner:
-    """TebOptimalPlanner over a homogeneous fleet: one band per robot on ONE handle, every robot with its own obstacles and via-points
-    (a scene each, teb_amd_set_scenes), all bands optimised in one launch. Configuration and footprint are the fleet's. Robot r is band r
-    and scene r. Each robot's band ends with the bits of a single-scene handle that holds only its scene with the options
+    """TebOptimalPlanner over a fleet: one band per robot on ONE handle, every robot with its own obstacles and via-points (a scene
+    each, teb_amd_set_scenes), all bands optimised in one launch. Configuration and footprint are the fleet's - or, with robot_cfgs
+    (the robot classes, a TebConfig each) and class_of_robot, those of every robot's class (teb_amd_set_scene_configs): robot r then
+    takes the trajectory / robot parameters of its class for its warm-start test, initTrajectoryToGoal, updateAndPruneTEB and the
+    look-ahead of its command, and its band runs under its class's configuration. The iteration counts and optimization_activate are
+    one per launch: the classes must agree on them. Robot r is band r and scene r. Each robot's band ends with the bits of a single-scene handle that holds only its scene with the options
     generic_config_path = 1, multi_cu = -1 (no helper workgroups) and speculative_trials = -1, the same max_poses and the distance path
     of the fleet (include/teb_amd.h, fleet batches). A default TebOptimalPlanner of that robot runs a kernel folded on the TebConfig
     defaults, and on scenes that are not point-like it may use helper workgroups: it gives the same bits only as far as those kinds
     equal the generic one - they are held to that for point scenes (tests/test_gpu_fleet.py); for generic scenes DESIGN.md section 8
     lists an open defect of the distance helpers, so compare against a handle with the options above."""
 
-    def __init__(self, cfg, n_robots, max_poses=None, max_obstacles=256, max_obstacle_vertices=256, max_via_points=64, device=0, options=None):
+    def __init__(self, cfg, n_robots, max_poses=None, max_obstacles=256, max_obstacle_vertices=256, max_via_points=64, device=0, options=None,
+                 robot_cfgs=None, class_of_robot=None):
         self.cfg_ = cfg
         self.n_robots = int(n_robots)
-        self.max_poses = max_poses or min(cfg.trajectory.max_samples + 1, _abi.MAX_POSES)
+        if (robot_cfgs is None) != (class_of_robot is None):
+            raise ValueError("TebFleetPlanner: robot_cfgs and class_of_robot come together")
+        self.robot_cfgs = list(robot_cfgs) if robot_cfgs is not None else None
+        self.class_of_robot = None
+        if self.robot_cfgs is not None:
+            self.class_of_robot = [int(k) for k in class_of_robot]
+            if len(self.class_of_robot) != self.n_robots:
+                raise ValueError("TebFleetPlanner: %d class entries for %d robots" % (len(self.class_of_robot), self.n_robots))
+            if not self.robot_cfgs or min(self.class_of_robot) < 0 or max(self.class_of_robot) >= len(self.robot_cfgs):
+                raise ValueError("TebFleetPlanner: class_of_robot does not fit the %d classes" % len(self.robot_cfgs))
+            o0 = self.robot_cfgs[0].optim
+            for k, c in enumerate(self.robot_cfgs):   # one launch: one pair of iteration counts
+                if (c.optim.no_inner_iterations, c.optim.no_outer_iterations, bool(c.optim.optimization_activate)) != \
+                        (o0.no_inner_iterations, o0.no_outer_iterations, bool(o0.optimization_activate)):
+                    raise ValueError("TebFleetPlanner: class %d differs from class 0 in no_inner_iterations / no_outer_iterations / "
+                                     "optimization_activate, which are one per launch" % k)
+        self._classes_installed = None   # the class map as last installed on the handle
+        longest = max(c.trajectory.max_samples for c in (self.robot_cfgs or [cfg]))
+        self.max_poses = max_poses or min(longest + 1, _abi.MAX_POSES)
         self.teb_ = _abi.TebBatchHost(self.n_robots, self.max_poses)
         self.device = device
         self._solver = TebBatchSolver(cfg, self.n_robots, self.max_poses, max(max_obstacles, 1), max(max_obstacle_vertices, 1),
@@ -1174,6 +1221,10 @@ class TebFleetPlanner:
     def teb(self):
         return self.teb_
 
+    def cfg_of(self, r):
+        """the configuration robot r runs under: its class's, or the fleet's"""
+        return self.cfg_ if self.robot_cfgs is None else self.robot_cfgs[self.class_of_robot[r]]
+
     def clearPlanner(self, r=None):
         """clearPlanner() of robot r (None: of every robot): its next plan() initialises a new band."""
         for k in (range(self.n_robots) if r is None else [r]):
@@ -1187,7 +1238,7 @@ class TebFleetPlanner:
         starts / goals: [n_robots] (x, y, theta); start_vels: [n_robots] (vx, vy, omega) or None entries; obstacles_per_robot:
         [n_robots] ObstacleTable; via_per_robot: [n_robots] [(x, y), ...]. Returns [n_robots] bool (optimizeTEB's return)."""
         import math
-        s, t, r = self._solver, self.cfg_.trajectory, self.cfg_.robot
+        s = self._solver
         R = self.n_robots
         if len(starts) != R or len(goals) != R:
             raise ValueError("TebFleetPlanner.plan: %d starts / %d goals for %d robots" % (len(starts), len(goals), R))
@@ -1195,6 +1246,7 @@ class TebFleetPlanner:
         via_per_robot = list(via_per_robot) if via_per_robot is not None else [[] for _ in range(R)]
         for k in range(R):
             start, goal = starts[k], goals[k]
+            t, r = self.cfg_of(k).trajectory, self.cfg_of(k).robot
             n = int(self.teb_.n[k])
             warm = False
             if self._resident[k] and n > 0:
@@ -1215,7 +1267,13 @@ class TebFleetPlanner:
             s.set_velocity_goal(self.teb_.vel_goal[k], bool(self.teb_.has_vel_goal[k]), b=k)
         s.set_config(self.cfg_)
         s.set_scenes(obstacles_per_robot, via_per_robot)
-        o = self.cfg_.optim
+        if self.robot_cfgs is not None:   # the class map survives set_scenes of the same size: installed when it changed
+            want = ([c.to_c() for c in self.robot_cfgs], list(self.class_of_robot))
+            have = self._classes_installed
+            if have is None or have[1] != want[1] or len(have[0]) != len(want[0]) or any(bytes(a) != bytes(b) for a, b in zip(have[0], want[0])):
+                s.set_scene_configs(self.robot_cfgs, self.class_of_robot)
+                self._classes_installed = want
+        o = self.cfg_of(0).optim
         if not o.optimization_activate:
             return np.zeros(R, bool)
         self.optimized_[:] = False
@@ -1228,12 +1286,26 @@ class TebFleetPlanner:
 
     def getVelocityCommands(self, look_ahead_poses=None):
         """[(ok, vx, vy, omega)] of every robot: getVelocityCommand on its resident band."""
-        t = self.cfg_.trajectory
-        la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
-        out = []
+        if self.robot_cfgs is None:
+            t = self.cfg_.trajectory
+            la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
+            out = []
+            for k in range(self.n_robots):
+                ok, v = self._solver.velocity_command(k, la, t.prevent_look_ahead_poses_near_goal)
+                out.append((ok, float(v[0]), float(v[1]), float(v[2])))
+            return out
+        # each robot's own look-ahead parameters. The handle keeps the commands of ONE (look-ahead, prevent) pair: the robots are asked
+        # pair by pair, one launch over all bands per distinct pair and not one per robot where classes that differ in them interleave
+        pairs = {}
         for k in range(self.n_robots):
-            ok, v = self._solver.velocity_command(k, la, t.prevent_look_ahead_poses_near_goal)
-            out.append((ok, float(v[0]), float(v[1]), float(v[2])))
+            t = self.cfg_of(k).trajectory
+            la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
+            pairs.setdefault((int(la), int(t.prevent_look_ahead_poses_near_goal)), []).append(k)
+        out = [None] * self.n_robots
+        for (la, prevent), robots in pairs.items():
+            ok, v = self._solver.velocity_commands(robots, la, prevent)
+            for i, k in enumerate(robots):
+                out[k] = (bool(ok[i]), float(v[i, 0]), float(v[i, 1]), float(v[i, 2]))
         return out
 
     def pose_counts(self):
