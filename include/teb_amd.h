@@ -690,7 +690,8 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  *                            whatever the classes hold: the iteration counts, and for the costs of the bands obst_cost_scale,
  *                            viapoint_cost_scale and alternative_time_cost - a caller who takes them from a configuration
  *                            (selection_obst_cost_scale, selection_viapoint_cost_scale, selection_alternative_time_cost) passes
- *                            ONE class's values, and the costs of every band are scaled by them; the library cannot check this.
+ *                            ONE class's values, and the costs of every band are scaled by them;
+ *                            teb_amd_optimize_batch_per_class reads them from the class of every band instead.
  *                            TEB_AMD_ERR_INVALID_ARG names the class and the field. Everything
  *                            is checked before anything live is touched: on any error - a layout that cannot be had with the new
  *                            footprints included - the previous map, or none, stays installed and the handle behaves as if the call
@@ -710,8 +711,39 @@ int  teb_amd_capacity(teb_amd_handle_t* h, int32_t* lds_bytes, int32_t* max_pose
  * teb_amd_get_batch_statistics (divergence_detection_*). A launch may change the pose counts when ANY class has teb_autosize. What
  * reads nothing else of the configuration and works unchanged: the signature, class-filter, detour and compaction calls per scene.
  * Limits: while a map with MORE THAN ONE class is installed, teb_amd_explore_candidates_per_scene returns TEB_AMD_ERR_UNSUPPORTED -
- * its initialisers take max_vel_x, max_vel_theta, acc_lim_x, min_samples and weight_viapoint as scalars of the launch (with one class
- * it runs under that class). teb_amd_is_trajectory_feasible_per_scene keeps its one footprint per call.
+ * it takes max_vel_x, max_vel_theta, acc_lim_x, min_samples and weight_viapoint from ONE configuration and dist_to_obst as one value
+ * per call (with one class it runs under that class); teb_amd_explore_candidates_per_class takes its place.
+ * teb_amd_is_trajectory_feasible_per_scene keeps its one footprint per call; teb_amd_is_trajectory_feasible_per_class takes one per spec.
+ *
+ * The whole tick per class - the _per_class calls. One naming rule: a _per_class call is its _per_scene sibling (or
+ * teb_amd_optimize_batch) WITHOUT every argument that stands for a configuration field; it reads those fields for scene s from the
+ * configuration of the scene's class, and without a class map from the handle's configuration (the table of one class the fleet launch
+ * uses). Valid only while scenes are set, else TEB_AMD_ERR_INVALID_ARG, like their siblings. Everything the sibling documents holds.
+ *   teb_amd_explore_candidates_per_class  teb_amd_explore_candidates_per_scene without dist_to_obst. For scene s of class k:
+ *                            min_obstacle_dist is the graph's dist_to_obst (vertices and edges); max_vel_x, max_vel_theta, min_samples
+ *                            initialise the bands made from initial plans; max_vel_x, acc_lim_x, min_samples the path bands; max_vel_x,
+ *                            min_samples the at-goal line bands; weight_viapoint decides the via-point rule after the tick.
+ *                            teb_amd_hcp_params_t stays one per call. Contract: the bands of scene s, read in band order, are bit for
+ *                            bit the batch of a single-scene handle that is created with class k's configuration, holds only scene s,
+ *                            held the same bands before the call and ran teb_amd_explore_candidates with dist_to_obst =
+ *                            min_obstacle_dist of class k and the arguments of s - bands, flags, n_vertices, n_paths, graph,
+ *                            initial_plan_teb and the order of the tail of the batch. Generators, remembered classes and last graphs
+ *                            are the per-scene state of teb_amd_explore_candidates_per_scene, shared with it.
+ *   teb_amd_update_and_prune_per_class  teb_amd_update_and_prune_per_scene without min_samples: every band is pruned with min_samples
+ *                            of its scene's class.
+ *   teb_amd_optimize_batch_per_class  teb_amd_optimize_batch where band b takes obst_cost_scale, viapoint_cost_scale and
+ *                            alternative_time_cost from selection_obst_cost_scale, selection_viapoint_cost_scale and
+ *                            selection_alternative_time_cost of its scene's class. Layout, refusals and the repeat after an optimistic
+ *                            layout are those of teb_amd_optimize_batch; the iteration counts stay arguments. Every band ends with the
+ *                            bits of teb_amd_optimize_batch with any triple; its cost has the bits of its single-scene handle (contract
+ *                            above) launched with its class's triple.
+ *   teb_amd_is_trajectory_feasible_per_class  teb_amd_is_trajectory_feasible_per_scene with a teb_amd_feasibility_spec_t - footprint,
+ *                            inscribed radius, angular resolution, look-ahead pair - per scene: spec_of_scene[s] in [0, n_specs), or
+ *                            NULL = the class of scene s, which needs n_specs = the number of classes of the map (1 without a map).
+ *                            Every spec passes the checks of the single call (1 <= n_footprint <= 64, radius and angular resolution
+ *                            > 0); TEB_AMD_ERR_INVALID_ARG names the spec. One launch, one download. The pair of scene s is what
+ *                            teb_amd_is_trajectory_feasible(bands[s]) gives with its spec on a handle whose costmap is grid s. The band,
+ *                            scene and costmap-set refusals and the sample and pose limits are those of the per-scene call.
  *
  *   teb_amd_set_scenes       installs n_scenes scenes (1 <= n_scenes <= max_tebs) and enters fleet mode. The fleet storage is a second
  *                            set of device buffers, allocated at the first call and sized by the handle's capacities: sum of the rows
@@ -911,6 +943,30 @@ int  teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_s
                                         const double* new_goal /* [3 n_scenes] or NULL */, int32_t min_samples,
                                         const double* start_vel /* [3 n_scenes] or NULL */,
                                         const int32_t* has_start_vel /* [n_scenes] or NULL = all */);
+/* the _per_class calls (above: the whole tick per class) */
+typedef struct teb_amd_feasibility_spec {      /* what the adapter passes to isTrajectoryFeasible for one robot class */
+  int32_t n_footprint; const double* footprint_x; const double* footprint_y;
+  double  inscribed_radius, min_resolution_collision_check_angular;
+  int32_t look_ahead_idx; double feasibility_check_lookahead_distance;
+} teb_amd_feasibility_spec_t;
+int  teb_amd_explore_candidates_per_class(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start /* [3 n_scenes] */,
+                                          const double* goal /* [3 n_scenes] */, const double* start_vel /* [3 n_scenes] or NULL */,
+                                          int32_t free_goal_vel, const int32_t* best /* [n_scenes] band of scene s or negative; NULL = none */,
+                                          const double* unit_samples /* [n_scenes][2 roadmap_graph_no_samples] or NULL */,
+                                          int64_t max_paths, int32_t* n_total, int32_t* n_bands /* [n_scenes] */,
+                                          int32_t* n_vertices /* [n_scenes] */, int32_t* n_paths /* [n_scenes] */,
+                                          const int32_t* plan_count /* [n_scenes] or NULL */, const double* plan_x, const double* plan_y,
+                                          const double* plan_yaw /* concatenated */, int32_t* initial_plan_teb /* [n_scenes] */);
+int  teb_amd_update_and_prune_per_class(teb_amd_handle_t* h, const double* new_start /* [3 n_scenes] or NULL */,
+                                        const double* new_goal /* [3 n_scenes] or NULL */,
+                                        const double* start_vel /* [3 n_scenes] or NULL */,
+                                        const int32_t* has_start_vel /* [n_scenes] or NULL = all */);
+int  teb_amd_optimize_batch_per_class(teb_amd_handle_t* h, int32_t iterations_innerloop, int32_t iterations_outerloop,
+                                      int32_t compute_cost_afterwards);
+int  teb_amd_is_trajectory_feasible_per_class(teb_amd_handle_t* h, const int32_t* bands /* [n_scenes] */, int32_t n_specs,
+                                              const teb_amd_feasibility_spec_t* specs,
+                                              const int32_t* spec_of_scene /* [n_scenes]; NULL = the class map's class_of_scene */,
+                                              int32_t* feasible, int32_t* first_infeasible /* [n_scenes] or NULL */);
 int  teb_amd_get_velocity_commands(teb_amd_handle_t* h, int32_t n, const int32_t* bands /* [n], negative = none */,
                                    int32_t look_ahead_poses, int32_t prevent_look_ahead_poses_near_goal, double* cmd /* [n][3] */,
                                    int32_t* ok /* [n] */);

@@ -269,6 +269,7 @@ struct teb_amd_handle {
   // of teb_amd_update_and_prune_per_scene
   DevBuf<int> cms_bands;
   DevBuf<double> prune_msg;
+  DevBuf<FeasSpecDev> cms_specs;   // the record of every scene of teb_amd_is_trajectory_feasible_per_class
   // the global plans (teb_amd_set_global_plans): the plans of every robot one after the other in ONE buffer (x | y | yaw planes of
   // `total` poses), their first poses, counts and pruning cursors, and the scratch of teb_amd_plan_windows: the poses / transforms /
   // thresholds of a call, the per-robot records, the pack buffer of the windows and via-points and its ticket. Beside the costmap set
@@ -1364,10 +1365,12 @@ int teb_amd_download_tebs(teb_amd_handle_t* h, teb_amd_teb_batch_t* bt) {
   return TEB_AMD_OK;
 }
 
-int teb_amd_optimize_batch(teb_amd_handle_t* h, int32_t inner, int32_t outer, int32_t compute_cost, double obst_cost_scale,
-                           double viapoint_cost_scale, int32_t alternative_time_cost) {
-  int rc = check_handle(h);
-  if (rc) return rc;
+namespace {
+// teb_amd_optimize_batch (cost_mode 0 / 1: without / with the costs under the triple of the call) and teb_amd_optimize_batch_per_class
+// (kCostPerClass: the triple of every band's class, read by the fleet units)
+int optimize_batch(teb_amd_handle* h, int32_t inner, int32_t outer, int cost_mode, double obst_cost_scale, double viapoint_cost_scale,
+                   int32_t alternative_time_cost) {
+  int rc = TEB_AMD_OK;
   if (inner < 0 || outer < 0) return fail(TEB_AMD_ERR_INVALID_ARG, "negative iteration count");
   const bool fleet = h->fleet.n_scenes > 0;
   if (fleet) {   // fleet mode (teb_amd_set_scenes): every band against its own scene, in one launch
@@ -1386,7 +1389,7 @@ int teb_amd_optimize_batch(teb_amd_handle_t* h, int32_t inner, int32_t outer, in
   }
   OptArgs a;
   std::memset(&a, 0, sizeof a);
-  a.inner = inner; a.outer = outer; a.compute_cost = compute_cost; a.no_near_cache = h->opt.no_near_cache != 0; a.band_ldlt = (fleet ? h->fleet.layout : h->layout).solver == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
+  a.inner = inner; a.outer = outer; a.compute_cost = cost_mode; a.no_near_cache = h->opt.no_near_cache != 0; a.band_ldlt = (fleet ? h->fleet.layout : h->layout).solver == SOLVER_BANDG ? 0 : h->band_ldlt; a.Hband = h->Hband.p; a.hband_stride = h->hband_stride;
   a.obst_scale = obst_cost_scale; a.via_scale = viapoint_cost_scale; a.alt_time = alternative_time_cost;
   if (h->iter_log_on) { a.iter_log = h->iter_log.p; a.iter_log_cap = TEB_AMD_ITERATION_LOG_ROWS; }
   if (h->phase_log_on) a.phase_log = h->phase_log.p;
@@ -1395,6 +1398,20 @@ int teb_amd_optimize_batch(teb_amd_handle_t* h, int32_t inner, int32_t outer, in
 #endif
   h->last_inner = inner;
   return launch(h, a);
+}
+}  // namespace
+
+int teb_amd_optimize_batch(teb_amd_handle_t* h, int32_t inner, int32_t outer, int32_t compute_cost, double obst_cost_scale,
+                           double viapoint_cost_scale, int32_t alternative_time_cost) {
+  if (int rc = check_handle(h)) return rc;
+  return optimize_batch(h, inner, outer, compute_cost != 0 ? 1 : 0, obst_cost_scale, viapoint_cost_scale, alternative_time_cost);
+}
+
+int teb_amd_optimize_batch_per_class(teb_amd_handle_t* h, int32_t inner, int32_t outer, int32_t compute_cost_afterwards) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_optimize_batch_per_class"))) return rc;
+  return optimize_batch(h, inner, outer, compute_cost_afterwards != 0 ? kCostPerClass : 0, 1.0, 1.0, 0);
 }
 
 // g2o's per-iteration console line ("iteration= i chi2= .. lambda= .. levenbergIter= ..", printed when optimization_verbose sets
@@ -1958,19 +1975,21 @@ int check_feasibility_arguments(bool given, const char* what, double inscribed_r
   if (!(inscribed_radius > 0) || !(min_res_angular > 0)) return fail(TEB_AMD_ERR_INVALID_ARG, "inscribed_radius and the angular resolution must be > 0");
   return TEB_AMD_OK;
 }
-// ... and `count` checks in one launch: the footprint upload, the output block [feasible | first_infeasible] count each + the overflow
+// ... and `count` checks in one launch: the footprint upload (nf entries per plane: one footprint, or those of all specs of
+// teb_amd_is_trajectory_feasible_per_class one after the other), the output block [feasible | first_infeasible] count each + the overflow
 // word with its one download, and the refusal of more than 2^22 samples. launch(fp_x, fp_y, feasible, first_infeasible, overflow) runs
 // the call's kernel on the device arrays.
 extern "C++" template <class Launch>
 int run_feasibility(teb_amd_handle* h, int count, int nf, const double* fx, const double* fy, int32_t* feasible, int32_t* first_infeasible, Launch launch) {
   if (h->stride > 1024) return fail(TEB_AMD_ERR_CAPACITY, "feasibility check supports bands up to 1024 poses");
-  HIPCHK(ensure(h->cm_fp, 2 * (size_t)kMaxFeasFootprint));
+  const size_t plane = std::max<size_t>((size_t)kMaxFeasFootprint, (size_t)nf);
+  HIPCHK(ensure(h->cm_fp, 2 * plane));
   HIPCHK(ensure(h->cm_out, 2 * (size_t)h->max_tebs + 1));
   int* ovf = h->cm_out.p + 2 * (size_t)count;
   HIPCHK(hipMemcpyAsync(h->cm_fp.p, fx, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipMemcpyAsync(h->cm_fp.p + kMaxFeasFootprint, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(h->cm_fp.p + plane, fy, nf * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipMemsetAsync(ovf, 0, sizeof(int), h->stream));
-  if (int rc = launch(h->cm_fp.p, h->cm_fp.p + kMaxFeasFootprint, h->cm_out.p, h->cm_out.p + count, ovf)) return rc;
+  if (int rc = launch(h->cm_fp.p, h->cm_fp.p + plane, h->cm_out.p, h->cm_out.p + count, ovf)) return rc;
   std::vector<int> out(2 * (size_t)count + 1);
   HIPCHK(hipMemcpyAsync(out.data(), h->cm_out.p, out.size() * sizeof(int), hipMemcpyDeviceToHost, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // (the caller's footprint, and what launch() uploaded, are read until here)
@@ -2372,6 +2391,19 @@ int teb_amd_set_scenes_from_costmap_polygons(teb_amd_handle_t* h, int32_t n_scen
                                        PolygonRows::Out{n_obstacles, n_points, out_offset, out_x, out_y, capacity_obstacles, capacity_points});
 }
 
+namespace {
+// bands[s] is a band of scene s, or negative
+int check_feasibility_bands(const teb_amd_handle* h, const char* fn, const int32_t* bands) {
+  for (int s = 0; s < h->fleet.n_scenes; ++s)
+    if (bands[s] >= 0 && (bands[s] >= h->B || h->fleet.band_scene[bands[s]] != s)) {
+      char buf[200];
+      std::snprintf(buf, sizeof buf, "%s: bands[%d] = %d is not a band of scene %d", fn, s, bands[s], s);
+      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+    }
+  return TEB_AMD_OK;
+}
+}  // namespace
+
 int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t* bands, int32_t nf, const double* fx, const double* fy,
                                              double inscribed_radius, double min_res_angular, int32_t look_ahead_idx, double lookahead_distance,
                                              int32_t* feasible, int32_t* first_infeasible) {
@@ -2381,12 +2413,7 @@ int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t*
   const int ns = h->fleet.n_scenes;
   if (h->cms.n != ns) return fail(TEB_AMD_ERR_INVALID_ARG, "teb_amd_is_trajectory_feasible_per_scene: needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
   if ((rc = check_feasibility_arguments(bands && feasible && nf >= 1 && nf <= kMaxFeasFootprint && fx && fy, "bad bands / footprint / output", inscribed_radius, min_res_angular))) return rc;
-  for (int s = 0; s < ns; ++s)
-    if (bands[s] >= 0 && (bands[s] >= h->B || h->fleet.band_scene[bands[s]] != s)) {
-      char buf[200];
-      std::snprintf(buf, sizeof buf, "teb_amd_is_trajectory_feasible_per_scene: bands[%d] = %d is not a band of scene %d", s, bands[s], s);
-      return fail(TEB_AMD_ERR_INVALID_ARG, buf);
-    }
+  if ((rc = check_feasibility_bands(h, "teb_amd_is_trajectory_feasible_per_scene", bands))) return rc;
   return run_feasibility(h, ns, nf, fx, fy, feasible, first_infeasible, [&](double* px, double* py, int* fe, int* fi, int* ovf) {
     if (!h->cms_bands.p) HIPCHK(h->cms_bands.alloc((size_t)h->max_tebs));
     HIPCHK(hipMemcpyAsync(h->cms_bands.p, bands, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -2396,29 +2423,92 @@ int teb_amd_is_trajectory_feasible_per_scene(teb_amd_handle_t* h, const int32_t*
   });
 }
 
-int teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_start, const double* new_goal, int32_t min_samples,
-                                       const double* start_vel, const int32_t* has_start_vel) {
+int teb_amd_is_trajectory_feasible_per_class(teb_amd_handle_t* h, const int32_t* bands, int32_t n_specs, const teb_amd_feasibility_spec_t* specs,
+                                             const int32_t* spec_of_scene, int32_t* feasible, int32_t* first_infeasible) {
   int rc = check_handle(h);
   if (rc) return rc;
-  if ((rc = require_fleet_mode(h, "teb_amd_update_and_prune_per_scene"))) return rc;
+  const char* fn = "teb_amd_is_trajectory_feasible_per_class";
+  if ((rc = require_fleet_mode(h, fn))) return rc;
+  const int ns = h->fleet.n_scenes;
+  if (h->cms.n != ns) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + ": needs a costmap set with one grid per scene (teb_amd_set_costmaps)");
+  if (!bands || !feasible) return fail(TEB_AMD_ERR_INVALID_ARG, std::string(fn) + ": bad bands / output");
+  const ClassList cl = fleet_classes(h);
+  const FeasibilitySpecs fs = check_feasibility_specs(specs, n_specs, spec_of_scene, ns, cl.n, kMaxFeasFootprint);
+  if (!fs.refusal.ok()) {
+    char buf[240];
+    if (fs.refusal.spec >= 0) std::snprintf(buf, sizeof buf, "%s: spec %d: %s", fn, fs.refusal.spec, fs.refusal.why);
+    else if (fs.refusal.scene >= 0) std::snprintf(buf, sizeof buf, "%s: spec_of_scene[%d] = %d with %d specs: %s", fn, fs.refusal.scene, spec_of_scene[fs.refusal.scene], n_specs, fs.refusal.why);
+    else std::snprintf(buf, sizeof buf, "%s: %d specs, %d classes: %s", fn, n_specs, cl.n, fs.refusal.why);
+    return fail(TEB_AMD_ERR_INVALID_ARG, buf);
+  }
+  if ((rc = check_feasibility_bands(h, fn, bands))) return rc;
+  // the footprints of all specs one after the other (x plane, y plane), and the record of every scene
+  const int total = fs.offset.back();
+  std::vector<double> fx((size_t)total), fy((size_t)total);
+  for (int k = 0; k < n_specs; ++k) {
+    std::copy(specs[k].footprint_x, specs[k].footprint_x + specs[k].n_footprint, fx.begin() + fs.offset[k]);
+    std::copy(specs[k].footprint_y, specs[k].footprint_y + specs[k].n_footprint, fy.begin() + fs.offset[k]);
+  }
+  std::vector<FeasSpecDev> recs((size_t)ns);
+  for (int s = 0; s < ns; ++s) {
+    const int k = feasibility_spec_of(spec_of_scene, cl.class_of, s);
+    const teb_amd_feasibility_spec_t& q = specs[k];
+    recs[s] = FeasSpecDev{fs.offset[k], q.n_footprint, q.inscribed_radius, q.min_resolution_collision_check_angular, q.look_ahead_idx,
+                          q.feasibility_check_lookahead_distance};
+  }
+  return run_feasibility(h, ns, total, fx.data(), fy.data(), feasible, first_infeasible, [&](double* px, double* py, int* fe, int* fi, int* ovf) {
+    if (!h->cms_bands.p) HIPCHK(h->cms_bands.alloc((size_t)h->max_tebs));
+    if (!h->cms_specs.p) HIPCHK(h->cms_specs.alloc((size_t)h->max_tebs));
+    HIPCHK(hipMemcpyAsync(h->cms_bands.p, bands, (size_t)ns * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(h->cms_specs.p, recs.data(), (size_t)ns * sizeof(FeasSpecDev), hipMemcpyHostToDevice, h->stream));
+    LAUNCH(feasibility_fleet_class_kernel, dim3(ns), dim3(kFeasThreads), 0, h->stream, h->bands.strips.n.p, h->bands.strips.x.p, h->bands.strips.y.p,
+           h->bands.strips.th.p, h->stride, h->cms_bands.p, h->cms.grids.p, h->cms_specs.p, px, py, 1 << 22, fe, fi, ovf);
+    return (int)TEB_AMD_OK;
+  });
+}
+
+namespace {
+// teb_amd_update_and_prune_per_scene (min_samples: the one value of the call) and teb_amd_update_and_prune_per_class (null: the eleventh
+// column of the message, min_samples of every scene's class)
+int update_and_prune_fleet(teb_amd_handle* h, const char* fn, const double* new_start, const double* new_goal, const int32_t* min_samples,
+                           const double* start_vel, const int32_t* has_start_vel) {
+  int rc = TEB_AMD_OK;
+  if ((rc = require_fleet_mode(h, fn))) return rc;
   if (h->B <= 0) return fail(TEB_AMD_ERR_INVALID_ARG, "no TEBs on the device");
   if ((rc = check_band_scenes(h, h->B))) return rc;
   const size_t ns = (size_t)h->fleet.n_scenes;
-  // one message: [start | goal | start_vel] 3 ns each, [has_start_vel] ns (exact as doubles)
-  std::vector<double> msg(10 * ns, 0.0);
+  // one message: [start | goal | start_vel] 3 ns each, [has_start_vel] ns, [min_samples] ns (exact as doubles)
+  std::vector<double> msg(11 * ns, 0.0);
   if (new_start) std::copy(new_start, new_start + 3 * ns, msg.begin());
   if (new_goal) std::copy(new_goal, new_goal + 3 * ns, msg.begin() + 3 * ns);
   if (start_vel) {
     std::copy(start_vel, start_vel + 3 * ns, msg.begin() + 6 * ns);
     for (size_t s = 0; s < ns; ++s) msg[9 * ns + s] = (!has_start_vel || has_start_vel[s]) ? 1.0 : 0.0;
   }
-  if (!h->prune_msg.p) HIPCHK(h->prune_msg.alloc(10 * (size_t)h->max_tebs));
+  if (!min_samples) {
+    const ClassList cl = fleet_classes(h);
+    for (size_t s = 0; s < ns; ++s) msg[10 * ns + s] = (double)scene_tick_params(cl.cfgs, cl.n, cl.class_of, (int)s).min_samples;
+  }
+  if (!h->prune_msg.p) HIPCHK(h->prune_msg.alloc(11 * (size_t)h->max_tebs));
   HIPCHK(hipMemcpyAsync(h->prune_msg.p, msg.data(), msg.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));   // the upload reads msg; nothing waits for the kernel
   LAUNCH(prune_fleet_kernel, dim3(h->B), dim3(kThreads), 4 * (size_t)h->stride * sizeof(double), h->stream, batch_of(h), h->fleet.scene_of.p, h->prune_msg.p,
-         (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples, h->bands.has_vs.p, h->bands.vs.p);
+         (int)ns, new_start ? 1 : 0, new_goal ? 1 : 0, start_vel ? 1 : 0, min_samples ? *min_samples : 0, min_samples ? 0 : 1, h->bands.has_vs.p, h->bands.vs.p);
   h->bands_changed();
   return TEB_AMD_OK;
+}
+}  // namespace
+
+int teb_amd_update_and_prune_per_scene(teb_amd_handle_t* h, const double* new_start, const double* new_goal, int32_t min_samples,
+                                       const double* start_vel, const int32_t* has_start_vel) {
+  if (int rc = check_handle(h)) return rc;
+  return update_and_prune_fleet(h, "teb_amd_update_and_prune_per_scene", new_start, new_goal, &min_samples, start_vel, has_start_vel);
+}
+
+int teb_amd_update_and_prune_per_class(teb_amd_handle_t* h, const double* new_start, const double* new_goal, const double* start_vel,
+                                       const int32_t* has_start_vel) {
+  if (int rc = check_handle(h)) return rc;
+  return update_and_prune_fleet(h, "teb_amd_update_and_prune_per_class", new_start, new_goal, nullptr, start_vel, has_start_vel);
 }
 
 int teb_amd_get_velocity_commands(teb_amd_handle_t* h, int32_t n, const int32_t* bands, int32_t look_ahead_poses,
@@ -2677,6 +2767,7 @@ struct TickPlanner {
   int n_plan = 0; const double *plan_x = nullptr, *plan_y = nullptr, *plan_yaw = nullptr;   // the initial plan, n_plan <= 0: none
   const double* unit_samples = nullptr;   // [2 * roadmap_graph_no_samples] or NULL: drawn from mem->rnd
   int slots = 0, n_via = 0;        // most bands it may hold; its via-points
+  double dist_to_obst = 0, weight_viapoint = 0;   // of its configuration: the graph's distance, the via-point rule of finish_tick
   int32_t *n_vertices = nullptr, *n_paths = nullptr, *initial_plan_teb = nullptr;   // output slots, NULL: not asked for
   // of the running tick
   int created = -1;                // initial_plan_teb_: the band made from the initial plan, as a position in `bands`
@@ -2774,7 +2865,12 @@ struct FleetRoute {
   int per_round;           // paths per scene and round
   std::vector<int> off;    // staging of plans() and lines(): read by the stream until the synchronisation after the signatures
   std::vector<double> px, py, pyaw;
-  const teb_amd_config_t& cfg() const { return agreed_cfg(h, true); }   // the scene set's ONE class (more than one: the call is refused), or the handle's configuration
+  // The initialisers read their parameters from the class of the candidate's scene (F.cfgs / F.class_of_scene, the table a fleet
+  // launch reads: the map's, or the handle's configuration alone) through the candidate -> scene array F.ex_scene.
+  int candidate_scenes(const std::vector<int>& who) {
+    HIPCHK(hipMemcpyAsync(h->fleet.ex_scene.p, who.data(), who.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return TEB_AMD_OK;
+  }
   int plans(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // addAndInitNewTeb(*initial_plan_, ...) of every scene
     auto& F = h->fleet;
     off.assign(1, 0); px.clear(); py.clear(); pyaw.clear();
@@ -2789,8 +2885,9 @@ struct FleetRoute {
     HIPCHK(hipMemcpyAsync(sc.py, py.data(), py.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(F.ex_pyaw.p, pyaw.data(), pyaw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-    hipLaunchKernelGGL(init_plan_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
-                       F.ex_pyaw.p, cfg().max_vel_x, cfg().max_vel_theta, p->global_plan_overwrite_orientation, cfg().min_samples,
+    if (int rc = candidate_scenes(who)) return rc;
+    hipLaunchKernelGGL(init_plan_fleet_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
+                       F.ex_pyaw.p, F.ex_scene.p, F.cfgs.p, F.class_of_scene.p, p->global_plan_overwrite_orientation,
                        p->allow_init_with_backwards_motion, h->err_flag.p);
     return TEB_AMD_OK;
   }
@@ -2801,8 +2898,9 @@ struct FleetRoute {
       for (int j = 0; j < 3; ++j) { px[6 * k + j] = P[who[k]].start[j]; px[6 * k + 3 + j] = P[who[k]].goal[j]; }
     HIPCHK(hipMemcpyAsync(F.ex_line.p, px.data(), px.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemsetAsync(h->err_flag.p, 0, sizeof(int), h->stream));
-    hipLaunchKernelGGL(init_line_batch_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, F.ex_line.p, 0.0, cfg().max_vel_x,
-                       cfg().min_samples, p->allow_init_with_backwards_motion, h->err_flag.p);
+    if (int rc = candidate_scenes(who)) return rc;
+    hipLaunchKernelGGL(init_line_fleet_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, F.ex_line.p, F.ex_scene.p, F.cfgs.p,
+                       F.class_of_scene.p, 0.0, p->allow_init_with_backwards_motion, h->err_flag.p);
     return TEB_AMD_OK;
   }
   int edges(std::vector<TickPlanner>& P, const std::vector<int>& who) {   // every graph in one launch, one download
@@ -2838,10 +2936,9 @@ struct FleetRoute {
   }
   int paths(std::vector<TickPlanner>&, const std::vector<int>& who) {   // the paths uploaded to sc.off / sc.px / sc.py
     auto& F = h->fleet;
-    HIPCHK(hipMemcpyAsync(F.ex_scene.p, who.data(), who.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (int rc = candidate_scenes(who)) return rc;
     hipLaunchKernelGGL(init_path_fleet_kernel, dim3((unsigned)who.size()), dim3(kThreads), 0, h->stream, sc.cand, sc.off, sc.px, sc.py,
-                       F.ex_scene.p, F.ex_orient.p, cfg().max_vel_x, cfg().acc_lim_x, cfg().min_samples, p->allow_init_with_backwards_motion,
-                       h->err_flag.p);
+                       F.ex_scene.p, F.ex_orient.p, F.cfgs.p, F.class_of_scene.p, p->allow_init_with_backwards_motion, h->err_flag.p);
     return TEB_AMD_OK;
   }
   int signatures(std::vector<TickPlanner>&, const std::vector<int>& who, const std::vector<int>& soff) {
@@ -2858,8 +2955,7 @@ struct FleetRoute {
 
 // plans -> vertices -> edges -> rounds -> at-goal lines for the planners P; their class tables are seeded, their outputs initialised
 extern "C++" template <class Route>
-int explore_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, Route& R, std::vector<TickPlanner>& P, double dist_to_obst, int free_goal_vel,
-                 int64_t max_paths) {
+int explore_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, Route& R, std::vector<TickPlanner>& P, int free_goal_vel, int64_t max_paths) {
   // the candidates of a launch: planner of every candidate, its signature values at sig[soff[k] ..), the accepted ones, the paths of a round
   std::vector<int> who, soff, acc, off;
   std::vector<double> sig, px, py;
@@ -2908,7 +3004,7 @@ int explore_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, Route& R, std
       if (t.bands.empty()) at_goal.push_back((int)i);                         // a line band, and only for a planner without any band
       continue;
     }
-    graph_vertices(*t.tab, t.start, t.goal, start_goal_dist, dist_to_obst, p, t.mem->rnd, t.unit_samples, t.vx, t.vy, t.ga);
+    graph_vertices(*t.tab, t.start, t.goal, start_goal_dist, t.dist_to_obst, p, t.mem->rnd, t.unit_samples, t.vx, t.vy, t.ga);
     if (t.n_vertices) *t.n_vertices = (int32_t)t.vx.size();
     graphs.push_back((int)i);
   }
@@ -2954,14 +3050,14 @@ int explore_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, Route& R, std
 }
 
 // getInitialPlanTEB (:495-536) and updateReferenceTrajectoryViaPoints (:286-315) planner by planner after a tick; one upload of via_en
-int finish_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, std::vector<TickPlanner>& P, const teb_amd_config_t& cfg) {
+int finish_tick(teb_amd_handle* h, const teb_amd_hcp_params_t* p, std::vector<TickPlanner>& P) {
   std::vector<std::vector<int>> rule(P.size());
   bool any = false;
   for (size_t i = 0; i < P.size(); ++i) {
     TickPlanner& t = P[i];
     const int n = (int)t.bands.size();
     if (t.initial_plan_teb) *t.initial_plan_teb = initial_plan_band(t.ct, *t.mem, n, t.created);
-    if (via_point_rule(t.ct, *t.mem, n, p->viapoints_all_candidates != 0, t.n_plan > 0, t.n_via, cfg.weight_viapoint, rule[i])) any = true;
+    if (via_point_rule(t.ct, *t.mem, n, p->viapoints_all_candidates != 0, t.n_plan > 0, t.n_via, t.weight_viapoint, rule[i])) any = true;
   }
   if (!any) return TEB_AMD_OK;
   std::vector<int> ve(h->B, 0);
@@ -3009,6 +3105,7 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
   t.tab = &h->hob; t.mem = &h->memory; t.start = start; t.goal = goal; t.start_vel = start_vel;
   t.n_plan = n_plan; t.plan_x = plan_x; t.plan_y = plan_y; t.plan_yaw = plan_yaw; t.unit_samples = unit_samples;
   t.slots = std::min<int>(p->max_number_classes, h->max_tebs); t.n_via = h->nvia;
+  t.dist_to_obst = dist_to_obst; t.weight_viapoint = h->cfg.weight_viapoint;
   t.n_vertices = n_vertices; t.n_paths = n_paths; t.initial_plan_teb = initial_plan_teb;
   // equivalence_classes_ of the existing bands
   std::vector<const double*> rows;
@@ -3023,9 +3120,9 @@ int teb_amd_explore_candidates(teb_amd_handle_t* h, const teb_amd_hcp_params_t* 
   h->bands_changed();   // the batch is about to change: signatures have to be recomputed before the next filter call
   SingleRoute R{h, p, {batch_of(h), h->cand_map.p, h->cand_off.p, h->cand_px.p, h->cand_py.p, h->cand_sig.p}, kCandChunk};
   h->cand.into(R.sc.cand);   // the scratch strips seen as a batch of kCandChunk bands
-  if ((rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths))) return rc;
+  if ((rc = explore_tick(h, p, R, P, free_goal_vel, max_paths))) return rc;
   if (n_total) *n_total = h->B;
-  return finish_tick(h, p, P, h->cfg);
+  return finish_tick(h, p, P);
 }
 
 int teb_amd_get_exploration_graph(teb_amd_handle_t* h, double* vx, double* vy, unsigned char* adjacency, int32_t capacity_vertices,
@@ -3035,18 +3132,16 @@ int teb_amd_get_exploration_graph(teb_amd_handle_t* h, double* vx, double* vy, u
 }
 
 // ---- candidate generation per scene of a fleet batch (teb_amd.h, fleet batches; kernels: the fleet forms of teb_graph.hpp) ----------
-int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
-                                         double dist_to_obst, const double* start_vel, int32_t free_goal_vel, const int32_t* best,
-                                         const double* unit_samples, int64_t max_paths, int32_t* n_total, int32_t* n_bands,
-                                         int32_t* n_vertices, int32_t* n_paths, const int32_t* plan_count, const double* plan_x,
-                                         const double* plan_y, const double* plan_yaw, int32_t* initial_plan_teb) {
-  int rc = check_handle(h);
-  if (rc) return rc;
-  if ((rc = require_fleet_mode(h, "teb_amd_explore_candidates_per_scene"))) return rc;
-  if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
+namespace {
+// teb_amd_explore_candidates_per_scene (dist_to_obst: the one value of the call) and teb_amd_explore_candidates_per_class (null: every
+// scene takes min_obstacle_dist of its class). Everything else a scene reads from a configuration is that of its class either way.
+int explore_per_scene(teb_amd_handle* h, const char* fn, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
+                      const double* dist_to_obst, const double* start_vel, int32_t free_goal_vel, const int32_t* best,
+                      const double* unit_samples, int64_t max_paths, int32_t* n_total, int32_t* n_bands, int32_t* n_vertices, int32_t* n_paths,
+                      const int32_t* plan_count, const double* plan_x, const double* plan_y, const double* plan_yaw, int32_t* initial_plan_teb) {
+  int rc = TEB_AMD_OK;
   auto& F = h->fleet;
-  if (F.classes.size() > 1)   // the initialisers take max_vel_x, max_vel_theta, acc_lim_x, min_samples and weight_viapoint as scalars of the launch
-    return fail(TEB_AMD_ERR_UNSUPPORTED, "teb_amd_explore_candidates_per_scene: not available while a class map with more than one class is installed (teb_amd_set_scene_configs)");
+  const ClassList cl = fleet_classes(h);
   const int ns = F.n_scenes, B0 = h->B;
   std::vector<int> plan_off(ns + 1, 0);
   for (int s = 0; s < ns; ++s) {
@@ -3057,7 +3152,7 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
     plan_off[s + 1] = plan_off[s] + np;
   }
   BandGroups G;   // the bands of every scene in band order
-  if ((rc = scene_groups(h, B0, G)) || (rc = check_best_per_scene(G, best, "teb_amd_explore_candidates_per_scene"))) return rc;
+  if ((rc = scene_groups(h, B0, G)) || (rc = check_best_per_scene(G, best, fn))) return rc;
   std::vector<std::vector<int>>& of = G.of;
   const int slots = p->max_number_classes;   // per scene (the reference handle of the contract has max_tebs >= max_number_classes)
   {
@@ -3065,7 +3160,7 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
     for (int s = 0; s < ns; ++s) need += std::max<long long>((long long)of[s].size(), slots);
     if (need > h->max_tebs) {
       char buf[200];
-      std::snprintf(buf, sizeof buf, "teb_amd_explore_candidates_per_scene: %d scenes may grow to %lld bands, max_tebs is %d", ns, need, h->max_tebs);
+      std::snprintf(buf, sizeof buf, "%s: %d scenes may grow to %lld bands, max_tebs is %d", fn, ns, need, h->max_tebs);
       return fail(TEB_AMD_ERR_CAPACITY, buf);
     }
   }
@@ -3098,6 +3193,8 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
     if (np > 0) { t.plan_x = plan_x + plan_off[s]; t.plan_y = plan_y + plan_off[s]; t.plan_yaw = plan_yaw + plan_off[s]; }
     t.unit_samples = unit_samples ? unit_samples + (size_t)s * 2 * std::max(p->roadmap_graph_no_samples, 0) : nullptr;
     t.slots = slots; t.n_via = F.via_count[s];
+    const SceneTickParams tp = scene_tick_params(cl.cfgs, cl.n, cl.class_of, s);
+    t.dist_to_obst = dist_to_obst ? *dist_to_obst : tp.dist_to_obst; t.weight_viapoint = tp.weight_viapoint;
     t.n_vertices = n_vertices ? n_vertices + s : nullptr; t.n_paths = n_paths ? n_paths + s : nullptr;
     t.initial_plan_teb = initial_plan_teb ? initial_plan_teb + s : nullptr;
     std::vector<const double*> rows;
@@ -3110,11 +3207,40 @@ int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_
   FleetRoute R{h, p, {batch_of(h), F.ex_map.p, F.ex_off.p, F.ex_px.p, F.ex_py.p, F.ex_sig.p}, q, {}, {}, {}, {}};
   F.ex.into(R.sc.cand);   // the scratch strips of the scene set seen as a batch of K bands (they may hold more)
   R.sc.cand.B = (int)K;
-  rc = explore_tick(h, p, R, P, dist_to_obst, free_goal_vel, max_paths);
+  rc = explore_tick(h, p, R, P, free_goal_vel, max_paths);
   if (n_total) *n_total = h->B;
   for (int s = 0; s < ns; ++s) if (n_bands) n_bands[s] = (int)P[s].bands.size();
   if (rc) return rc;
-  return finish_tick(h, p, P, agreed_cfg(h, true));   // (one class at most: its weight_viapoint)
+  return finish_tick(h, p, P);
+}
+}  // namespace
+
+int teb_amd_explore_candidates_per_scene(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
+                                         double dist_to_obst, const double* start_vel, int32_t free_goal_vel, const int32_t* best,
+                                         const double* unit_samples, int64_t max_paths, int32_t* n_total, int32_t* n_bands,
+                                         int32_t* n_vertices, int32_t* n_paths, const int32_t* plan_count, const double* plan_x,
+                                         const double* plan_y, const double* plan_yaw, int32_t* initial_plan_teb) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_explore_candidates_per_scene"))) return rc;
+  if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
+  if (h->fleet.classes.size() > 1)   // dist_to_obst is one value per call: the classes' min_obstacle_dist have no place in it (teb_amd_explore_candidates_per_class)
+    return fail(TEB_AMD_ERR_UNSUPPORTED, "teb_amd_explore_candidates_per_scene: not available while a class map with more than one class is installed (teb_amd_set_scene_configs)");
+  return explore_per_scene(h, "teb_amd_explore_candidates_per_scene", p, start, goal, &dist_to_obst, start_vel, free_goal_vel, best, unit_samples,
+                           max_paths, n_total, n_bands, n_vertices, n_paths, plan_count, plan_x, plan_y, plan_yaw, initial_plan_teb);
+}
+
+int teb_amd_explore_candidates_per_class(teb_amd_handle_t* h, const teb_amd_hcp_params_t* p, const double* start, const double* goal,
+                                         const double* start_vel, int32_t free_goal_vel, const int32_t* best, const double* unit_samples,
+                                         int64_t max_paths, int32_t* n_total, int32_t* n_bands, int32_t* n_vertices, int32_t* n_paths,
+                                         const int32_t* plan_count, const double* plan_x, const double* plan_y, const double* plan_yaw,
+                                         int32_t* initial_plan_teb) {
+  int rc = check_handle(h);
+  if (rc) return rc;
+  if ((rc = require_fleet_mode(h, "teb_amd_explore_candidates_per_class"))) return rc;
+  if (!p || !start || !goal) return fail(TEB_AMD_ERR_INVALID_ARG, "null argument");
+  return explore_per_scene(h, "teb_amd_explore_candidates_per_class", p, start, goal, nullptr, start_vel, free_goal_vel, best, unit_samples,
+                           max_paths, n_total, n_bands, n_vertices, n_paths, plan_count, plan_x, plan_y, plan_yaw, initial_plan_teb);
 }
 
 int teb_amd_get_exploration_graph_per_scene(teb_amd_handle_t* h, int32_t scene, double* vx, double* vy, unsigned char* adjacency,

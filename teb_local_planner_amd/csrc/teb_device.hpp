@@ -285,8 +285,9 @@ struct BatchDev {
   long long* clk;   // [4] workgroup 0: shader-clock counter and 100 MHz real-time counter at kernel entry, then at exit (teb_amd_last_shader_clock_mhz)
 };
 
+constexpr int kCostPerClass = 2;   // OptArgs::compute_cost of a fleet launch: the cost triple of every band's class (teb_amd_optimize_batch_per_class)
 struct OptArgs {
-  int inner, outer, compute_cost;
+  int inner, outer, compute_cost;   // compute_cost: 0 no, 1 with the triple below; fleet units also kCostPerClass
   double obst_scale, via_scale;
   int alt_time;
   double* Hband;         // SOLVER_BANDG: per-band normal matrix in band form in HBM, hband_stride doubles each

@@ -205,4 +205,30 @@ feasibility_fleet_kernel(const int* __restrict__ n_arr, const double* __restrict
                    max_tests, s, out_feasible, out_first, out_overflow);
 }
 
+// ... with a spec per scene (teb_amd_is_trajectory_feasible_per_class): the footprints of all specs lie in one staged array (x plane
+// fpx, y plane fpy), and every scene has a record - where its spec's footprint starts, its size, the radius, the angle, the look-ahead
+// pair. The record is uniform over the workgroup and selected once, before the single body.
+struct FeasSpecDev {
+  int off, nf;
+  double inscribed_radius, min_res_angular;
+  int look_ahead_idx;
+  double lookahead_distance;
+};
+__global__ void __launch_bounds__(kFeasThreads)
+feasibility_fleet_class_kernel(const int* __restrict__ n_arr, const double* __restrict__ X, const double* __restrict__ Y,
+                               const double* __restrict__ TH, int stride, const int* __restrict__ bands, const GridDev* __restrict__ grids,
+                               const FeasSpecDev* __restrict__ specs, const double* __restrict__ fpx, const double* __restrict__ fpy,
+                               int max_tests, int* __restrict__ out_feasible, int* __restrict__ out_first, int* __restrict__ out_overflow) {
+  __shared__ FeasShared sh;
+  const int s = blockIdx.x, b = bands[s];
+  if (b < 0) {
+    if (threadIdx.x == 0) { out_feasible[s] = -1; out_first[s] = -1; }
+    return;
+  }
+  const GridDev g = grids[s];
+  const FeasSpecDev q = specs[s];
+  feasibility_band(sh, n_arr, X, Y, TH, stride, b, g, q.nf, fpx + q.off, fpy + q.off, q.inscribed_radius, q.min_res_angular, q.look_ahead_idx,
+                   q.lookahead_distance, max_tests, s, out_feasible, out_first, out_overflow);
+}
+
 }  // namespace tebamd

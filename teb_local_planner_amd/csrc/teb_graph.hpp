@@ -170,14 +170,16 @@ __global__ void init_path_batch_kernel(BatchDev bt, const int* off, const double
 }
 
 // the candidates of many scenes: candidate k belongs to scene cand_scene[k] and takes that scene's start / goal orientation
-// (orient [n_scenes][2])
-__global__ void init_path_fleet_kernel(BatchDev bt, const int* off, const double* px, const double* py, const int* cand_scene,
-                                       const double* orient, double max_vel_x, double max_acc_x, int min_samples, int guess_backwards,
-                                       int* err) {
+// (orient [n_scenes][2]) and max_vel_x, acc_lim_x and min_samples from the configuration of the scene's robot class (a fleet without a
+// class map: the table of one class) - uniform over the workgroup, so the record arrives through scalar loads
+__global__ void init_path_fleet_kernel(BatchDev bt, const int* off, const double* px, const double* py, const int* __restrict__ cand_scene,
+                                       const double* orient, const teb_amd_config_t* __restrict__ cfgs,
+                                       const int* __restrict__ class_of_scene, int guess_backwards, int* err) {
   const int k = blockIdx.x;
   const int o = off[k], s = cand_scene[k];
-  init_path_band(strip_of(bt, k), off[k + 1] - o, px + o, py + o, max_vel_x, 1, max_acc_x, 1, orient[2 * s], 1, orient[2 * s + 1],
-                 min_samples, guess_backwards, err);
+  const teb_amd_config_t& c = cfgs[class_of_scene[s]];
+  init_path_band(strip_of(bt, k), off[k + 1] - o, px + o, py + o, c.max_vel_x, 1, c.acc_lim_x, 1, orient[2 * s], 1, orient[2 * s + 1],
+                 c.min_samples, guess_backwards, err);
 }
 
 // dst band blockIdx.x <- src band map[blockIdx.x], with the per-band attributes when attrs != 0

@@ -3051,6 +3051,17 @@ teb_optimize_kernel(const teb_amd_config_t c, const SceneDev sc, const BatchDev 
   // the configuration of the scene's robot class (teb_amd_set_scene_configs; without a map: one class, the handle's configuration).
   // Read-only kernel parameters, so the compiler may keep every read of the record on the scalar pipe.
   const teb_amd_config_t& c = cfgs[class_of_scene[fl.scene_of[b]]];
+  // the cost triple of computeCurrentCost, expanded where the costs are formed: with compute_cost == kCostPerClass
+  // (teb_amd_optimize_batch_per_class) that of the band's class, else the launch's; uniform over the workgroup either way
+#define TEB_COST_TRIPLE(alt, obst, via)                                                              \
+  const bool class_cost = args.compute_cost == kCostPerClass;                                        \
+  const int alt = class_cost ? (c.selection_alternative_time_cost != 0) : args.alt_time;             \
+  const double obst = class_cost ? c.selection_obst_cost_scale : args.obst_scale;                    \
+  const double via = class_cost ? c.selection_viapoint_cost_scale : args.via_scale;
+#else
+#define TEB_COST_TRIPLE(alt, obst, via) \
+  const int alt = args.alt_time;        \
+  const double obst = args.obst_scale, via = args.via_scale;
 #endif
   if (b == 0 && tid == 0) { bt.clk[0] = clock64(); bt.clk[1] = wall_clock64(); }   // shader clock of this launch (a slow box is not a regression)
   const Lds l = carve(lds_base, plan, SOLVER == SOLVER_BANDG ? args.Hband + (size_t)b * args.hband_stride : nullptr, SOLVER == SOLVER_BANDG);
@@ -3426,15 +3437,16 @@ teb_optimize_kernel(const teb_amd_config_t c, const SceneDev sc, const BatchDev 
     // ---- computeCurrentCost (src/optimal_planner.cpp:1041-1094) on the stored errors of the last evaluation
     if (args.compute_cost && outer == args.outer - 1) {
       double cst = 0;
-      if (args.alt_time) {
+      TEB_COST_TRIPLE(alt_time, obst_scale, via_scale)   // of the launch, or of the band's class (fleet units), defined beside `c` above
+      if (alt_time) {
         double s[1] = {0};
         for (int i = tid; i < n - 1; i += kThreads) s[0] += l.sdt[i];
         block_sum<1>(s, l.red);
         cst += s[0];
       }
-      cst += last_cats[CAT_OBST] * args.obst_scale;
-      cst += last_cats[CAT_VIA] * args.via_scale;
-      if (!args.alt_time) cst += last_cats[CAT_TIME];
+      cst += last_cats[CAT_OBST] * obst_scale;
+      cst += last_cats[CAT_VIA] * via_scale;
+      if (!alt_time) cst += last_cats[CAT_TIME];
       cst += last_cats[CAT_OTHER];
       cost = cst;
     }

@@ -65,7 +65,7 @@ __device__ inline int init_tail(StripDev s, int n, double gx, double gy, double 
 }
 
 // initTrajectoryToGoal(start, goal, diststep, max_vel_x, min_samples, guess_backwards_motion), :325-377. One workgroup.
-// The body is shared with the batch form (init_line_batch_kernel): every lane of the workgroup that owns the band calls it.
+// The body is shared with the fleet form (init_line_fleet_kernel): every lane of the workgroup that owns the band calls it.
 __device__ __forceinline__ void init_line_band(StripDev s, double sx, double sy, double sth, double gx, double gy, double gth,
                                                double diststep, double max_vel_x, int min_samples, int guess_backwards, int* err) {
   double timestep = 0.1;
@@ -103,11 +103,16 @@ __global__ void init_line_kernel(BatchDev bt, int b, double sx, double sy, doubl
   init_line_band(strip_of(bt, b), sx, sy, sth, gx, gy, gth, diststep, max_vel_x, min_samples, guess_backwards, err);
 }
 // one workgroup per band k of bt: start (x, y, theta) and goal (x, y, theta) of the band in pose[6 * k .. 6 * k + 6)
-__global__ void init_line_batch_kernel(BatchDev bt, const double* pose, double diststep, double max_vel_x, int min_samples,
+// of a fleet (teb_amd_explore_candidates_per_scene / _per_class): line k belongs to scene cand_scene[k] and takes
+// max_vel_x and min_samples from the configuration of that scene's class - uniform over the workgroup, so the record arrives through
+// scalar loads, as in consumers_fleet_kernel below. A fleet without a map: the table of one class.
+__global__ void init_line_fleet_kernel(BatchDev bt, const double* pose, const int* __restrict__ cand_scene,
+                                       const teb_amd_config_t* __restrict__ cfgs, const int* __restrict__ class_of_scene, double diststep,
                                        int guess_backwards, int* err) {
   const int k = blockIdx.x;
   const double* q = pose + 6 * (size_t)k;
-  init_line_band(strip_of(bt, k), q[0], q[1], q[2], q[3], q[4], q[5], diststep, max_vel_x, min_samples, guess_backwards, err);
+  const teb_amd_config_t& c = cfgs[class_of_scene[cand_scene[k]]];
+  init_line_band(strip_of(bt, k), q[0], q[1], q[2], q[3], q[4], q[5], diststep, c.max_vel_x, c.min_samples, guess_backwards, err);
 }
 
 // initTrajectoryToGoal(plan, max_vel_x, max_vel_theta, estimate_orient, min_samples, guess_backwards_motion), :380-452.
@@ -146,12 +151,15 @@ __global__ void init_plan_kernel(BatchDev bt, int b, int np, const double* px, c
   init_plan_band(strip_of(bt, b), np, px, py, pyaw, max_vel_x, max_vel_theta, estimate_orient, min_samples, guess_backwards, err);
 }
 // one workgroup per plan k: poses [off[k], off[k + 1]) of px / py / pyaw -> band k of bt
-__global__ void init_plan_batch_kernel(BatchDev bt, const int* off, const double* px, const double* py, const double* pyaw,
-                                       double max_vel_x, double max_vel_theta, int estimate_orient, int min_samples,
-                                       int guess_backwards, int* err) {
+// of a fleet: plan k belongs to scene cand_scene[k] and takes max_vel_x, max_vel_theta and min_samples from the
+// configuration of that scene's class (uniform over the workgroup: scalar loads)
+__global__ void init_plan_fleet_kernel(BatchDev bt, const int* off, const double* px, const double* py, const double* pyaw,
+                                       const int* __restrict__ cand_scene, const teb_amd_config_t* __restrict__ cfgs,
+                                       const int* __restrict__ class_of_scene, int estimate_orient, int guess_backwards, int* err) {
   const int k = blockIdx.x;
   const int o = off[k];
-  init_plan_band(strip_of(bt, k), off[k + 1] - o, px + o, py + o, pyaw + o, max_vel_x, max_vel_theta, estimate_orient, min_samples,
+  const teb_amd_config_t& c = cfgs[class_of_scene[cand_scene[k]]];
+  init_plan_band(strip_of(bt, k), off[k + 1] - o, px + o, py + o, pyaw + o, c.max_vel_x, c.max_vel_theta, estimate_orient, c.min_samples,
                  guess_backwards, err);
 }
 
@@ -203,12 +211,14 @@ __global__ void prune_kernel(BatchDev bt, int b0, int has_start, double sx, doub
 // scene_of[b] (uniform over the workgroup) from msg = [start | goal | start_vel] 3 * ns doubles each, then [flag] ns doubles; has_start /
 // has_goal / has_vel say which parts the caller gave. Where the scene has a start velocity (flag != 0) the band's start velocity
 // becomes fixed at it: what teb_amd_set_velocity_start(b, 1, v) leaves. has_vs / vs: the writable has_vel_start / vel_start arrays of
-// the batch (BatchDev carries them as const). Dynamic LDS: 4 * stride doubles.
+// the batch (BatchDev carries them as const). class_min_samples != 0 (teb_amd_update_and_prune_per_class): min_samples is that of the
+// band's scene, the eleventh column of msg - ns doubles after the flags, exact as doubles. Dynamic LDS: 4 * stride doubles.
 __global__ void prune_fleet_kernel(BatchDev bt, const int* __restrict__ scene_of, const double* __restrict__ msg, int ns, int has_start,
-                                   int has_goal, int has_vel, int min_samples, int* has_vs, double* vs) {
+                                   int has_goal, int has_vel, int min_samples, int class_min_samples, int* has_vs, double* vs) {
   extern __shared__ __attribute__((aligned(16))) double sbuf[];
   __shared__ int sh_k;
   const int b = blockIdx.x, sc = scene_of[b];
+  if (class_min_samples) min_samples = (int)msg[10 * (size_t)ns + sc];
   const double* st = msg + 3 * (size_t)sc;
   const double* gl = msg + 3 * (size_t)(ns + sc);
   const double* sv = msg + 3 * (size_t)(2 * ns + sc);

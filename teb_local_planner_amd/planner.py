@@ -26,6 +26,13 @@ class TebAmdError(RuntimeError):
         self.code = code
 
 
+class FeasibilitySpec(C.Structure):
+    """teb_amd_feasibility_spec_t: what the adapter passes to isTrajectoryFeasible for one robot class"""
+    _fields_ = [("n_footprint", C.c_int32), ("footprint_x", _abi.p_f64), ("footprint_y", _abi.p_f64), ("inscribed_radius", C.c_double),
+                ("min_resolution_collision_check_angular", C.c_double), ("look_ahead_idx", C.c_int32),
+                ("feasibility_check_lookahead_distance", C.c_double)]
+
+
 def lib():
     """Loads libteb_amd.so (built in-tree by teb_local_planner_amd.build)."""
     global _LIB
@@ -147,6 +154,13 @@ def lib():
             L.teb_amd_set_scenes_from_costmap_polygons.argtypes = [vp, i32, _abi.p_f64, d, _abi.p_i32, C.POINTER(_abi.Obstacles), _abi.p_i32,
                                                                    _abi.p_f64, _abi.p_f64, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_f64,
                                                                    _abi.p_f64, i32, i32]
+        if hasattr(L, "teb_amd_explore_candidates_per_class"):   # the whole tick per robot class: the _per_scene calls without the configuration fields
+            L.teb_amd_explore_candidates_per_class.argtypes = [vp, C.POINTER(_abi.HcpParams), _abi.p_f64, _abi.p_f64, _abi.p_f64, i32, _abi.p_i32,
+                                                               _abi.p_f64, C.c_int64, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_i32, _abi.p_i32,
+                                                               _abi.p_f64, _abi.p_f64, _abi.p_f64, _abi.p_i32]
+            L.teb_amd_update_and_prune_per_class.argtypes = [vp, _abi.p_f64, _abi.p_f64, _abi.p_f64, _abi.p_i32]
+            L.teb_amd_optimize_batch_per_class.argtypes = [vp, i32, i32, i32]
+            L.teb_amd_is_trajectory_feasible_per_class.argtypes = [vp, _abi.p_i32, i32, C.POINTER(FeasibilitySpec), _abi.p_i32, _abi.p_i32, _abi.p_i32]
         if hasattr(L, "teb_amd_plan_windows"):   # local plan windows per robot from resident global plans
             L.teb_amd_plan_window_params_default.argtypes = [C.POINTER(_abi.PlanWindowParams)]
             L.teb_amd_plan_window_params_default.restype = None
@@ -336,7 +350,19 @@ class TebBatchSolver:
         """Fleet mode: exploreEquivalenceClassesAndInitTebs of every scene with its own start / goal / start velocity / best band /
         unit samples / initial plan ((x, y, yaw) arrays or None per scene): dict(n_total, n_bands [n_scenes], n_vertices, n_paths,
         initial_plan_teb - the position among the bands of the scene, or -1). New bands are appended to the batch."""
-        what = "explore_candidates_per_scene"
+        dist_to_obst = self.cfg.obstacles.min_obstacle_dist if dist_to_obst is None else dist_to_obst
+        return self._explore_fleet("explore_candidates_per_scene", float(dist_to_obst), starts, goals, start_vels, free_goal_vel, best,
+                                   unit_samples, max_paths, params, initial_plans)
+
+    def explore_candidates_per_class(self, starts, goals, start_vels=None, free_goal_vel=False, best=None, unit_samples=None, max_paths=0,
+                                     params=None, initial_plans=None):
+        """explore_candidates_per_scene where every scene reads min_obstacle_dist (the graph's dist_to_obst), max_vel_x, max_vel_theta,
+        acc_lim_x, min_samples and weight_viapoint from the configuration of its robot class (set_scene_configs; without a map the
+        handle's configuration). params stays one per call."""
+        return self._explore_fleet("explore_candidates_per_class", None, starts, goals, start_vels, free_goal_vel, best, unit_samples,
+                                   max_paths, params, initial_plans)
+
+    def _explore_fleet(self, what, dist_to_obst, starts, goals, start_vels, free_goal_vel, best, unit_samples, max_paths, params, initial_plans):
         ns = getattr(self, "_n_scenes", 0)
         p = params if params is not None else self.cfg.hcp_params()
         if starts is None or goals is None:
@@ -352,14 +378,17 @@ class TebBatchSolver:
             pc = _abi.i32([0 if q is None else len(q[0]) for q in initial_plans])
             cat = lambda j: _abi.f64(np.concatenate([np.asarray(q[j], np.float64).ravel() for q in initial_plans if q is not None] + [np.zeros(1)]))
             px, py, pyaw = cat(0), cat(1), cat(2)
-        dist_to_obst = self.cfg.obstacles.min_obstacle_dist if dist_to_obst is None else dist_to_obst
         nt = C.c_int32(0)
         nb = np.zeros(max(ns, 1), np.int32); nv = nb.copy(); npth = nb.copy(); ipt = np.full(max(ns, 1), -1, np.int32)
         D = lambda a: _abi._ptr(a, C.c_double)
         I = lambda a: _abi._ptr(a, C.c_int32)
-        _chk(lib().teb_amd_explore_candidates_per_scene(self._h, C.byref(p), D(st), D(gl), float(dist_to_obst), D(sv), int(bool(free_goal_vel)),
-                                                        I(bp), D(us), int(max_paths), C.byref(nt), I(nb), I(nv), I(npth), I(pc), D(px), D(py),
-                                                        D(pyaw), I(ipt)), "teb_amd_explore_candidates_per_scene")
+        tail = (D(sv), int(bool(free_goal_vel)), I(bp), D(us), int(max_paths), C.byref(nt), I(nb), I(nv), I(npth), I(pc), D(px), D(py), D(pyaw),
+                I(ipt))
+        if dist_to_obst is None:
+            _chk(lib().teb_amd_explore_candidates_per_class(self._h, C.byref(p), D(st), D(gl), *tail), "teb_amd_explore_candidates_per_class")
+        else:
+            _chk(lib().teb_amd_explore_candidates_per_scene(self._h, C.byref(p), D(st), D(gl), dist_to_obst, *tail),
+                 "teb_amd_explore_candidates_per_scene")
         self.count = nt.value
         return dict(n_total=nt.value, n_bands=nb[:ns].copy(), n_vertices=nv[:ns].copy(), n_paths=npth[:ns].copy(),
                     initial_plan_teb=ipt[:ns].copy())
@@ -494,6 +523,44 @@ class TebBatchSolver:
         _chk(lib().teb_amd_update_and_prune_per_scene(self._h, D(st), D(gl), int(min_samples), D(sv), _abi._ptr(hv, C.c_int32)),
              "teb_amd_update_and_prune_per_scene")
 
+    def update_and_prune_per_class(self, new_starts=None, new_goals=None, start_vels=None, has_start_vel=None):
+        """update_and_prune_per_scene where every band is pruned with min_samples of its scene's robot class."""
+        what = "update_and_prune_per_class"
+        st = self._per_scene(what, "starts", new_starts, 3); gl = self._per_scene(what, "goals", new_goals, 3)
+        sv = self._per_scene(what, "start velocities", start_vels, 3)
+        hv = self._per_scene(what, "start velocity flags", has_start_vel)
+        D = lambda a: _abi._ptr(a, C.c_double)
+        _chk(lib().teb_amd_update_and_prune_per_class(self._h, D(st), D(gl), D(sv), _abi._ptr(hv, C.c_int32)), "teb_amd_update_and_prune_per_class")
+
+    def is_trajectory_feasible_per_class(self, bands, specs, spec_of_scene=None):
+        """is_trajectory_feasible_per_scene with a spec per scene. specs: a list of dict(footprint=[(x, y), ...], inscribed_radius=,
+        min_resolution_collision_check_angular=pi, look_ahead_idx=-1, feasibility_check_lookahead_distance=-1.0); spec_of_scene
+        [n_scenes] picks one for every scene, None: the spec of the scene's robot class (one spec per class of the map, one without a
+        map). (feasible [n_scenes], first_infeasible [n_scenes]) as int32."""
+        what = "is_trajectory_feasible_per_class"
+        bd = self._per_scene(what, "bands", bands)
+        if bd is None:
+            raise ValueError(what + ": bands are required")
+        specs = list(specs)
+        if not specs:
+            raise ValueError(what + ": needs at least one spec")
+        so = self._per_scene(what, "spec entries", spec_of_scene)
+        if so is not None and len(so) and (so.min() < 0 or so.max() >= len(specs)):
+            raise ValueError("%s: spec_of_scene does not fit the %d specs" % (what, len(specs)))
+        arr = (FeasibilitySpec * len(specs))()
+        keep = []   # the footprint arrays live until the call returns
+        for k, q in enumerate(specs):
+            fx = _abi.f64([v[0] for v in q["footprint"]]); fy = _abi.f64([v[1] for v in q["footprint"]])
+            keep.append((fx, fy))
+            arr[k] = FeasibilitySpec(len(q["footprint"]), _abi._ptr(fx, C.c_double), _abi._ptr(fy, C.c_double), float(q["inscribed_radius"]),
+                                     float(q.get("min_resolution_collision_check_angular", 3.141592653589793)), int(q.get("look_ahead_idx", -1)),
+                                     float(q.get("feasibility_check_lookahead_distance", -1.0)))
+        ok = np.zeros(max(len(bd), 1), np.int32); first = np.zeros(max(len(bd), 1), np.int32)
+        _chk(lib().teb_amd_is_trajectory_feasible_per_class(self._h, _abi._ptr(bd, C.c_int32), len(specs), arr, _abi._ptr(so, C.c_int32),
+                                                            _abi._ptr(ok, C.c_int32), _abi._ptr(first, C.c_int32)),
+             "teb_amd_is_trajectory_feasible_per_class")
+        return ok[:len(bd)].copy(), first[:len(bd)].copy()
+
     def velocity_commands(self, bands, look_ahead_poses=1, prevent_look_ahead_poses_near_goal=0):
         """getVelocityCommand of many bands after one launch and one download: (ok [n] bool, cmd [n, 3]); a negative band: False, zeros."""
         bd = _abi.i32(bands)
@@ -603,6 +670,11 @@ class TebBatchSolver:
         _chk(lib().teb_amd_optimize_batch(self._h, inner, outer, int(compute_cost), float(obst_cost_scale),
                                           float(viapoint_cost_scale), int(alternative_time_cost)),
              "teb_amd_optimize_batch")
+
+    def optimize_per_class(self, inner, outer, compute_cost=False):
+        """Fleet mode: optimize where band b's cost takes selection_obst_cost_scale, selection_viapoint_cost_scale and
+        selection_alternative_time_cost from the configuration of its scene's robot class."""
+        _chk(lib().teb_amd_optimize_batch_per_class(self._h, int(inner), int(outer), int(bool(compute_cost))), "teb_amd_optimize_batch_per_class")
 
     def synchronize(self):
         _chk(lib().teb_amd_synchronize(self._h), "teb_amd_synchronize")
@@ -1313,8 +1385,16 @@ class TebFleetPlanner:
 
 
 class FleetHomotopyClassPlanner:
-    """HomotopyClassPlanner::plan() of every robot of a homogeneous fleet on ONE handle: robot r is scene r, its candidates are the bands
-    the band -> scene map gives it. A tick is set_config, set_scenes, updateAllTEBs per robot, then renewAndAnalyzeOldTebs
+    """HomotopyClassPlanner::plan() of every robot of a fleet on ONE handle: robot r is scene r, its candidates are the bands
+    the band -> scene map gives it. Configuration and footprint are the fleet's - or, with robot_cfgs (the robot classes, a TebConfig
+    each) and class_of_robot, those of every robot's class (a heterogeneous fleet: set_scene_configs after set_scenes*, installed when
+    it changed, and the four _per_class calls of include/teb_amd.h in place of their _per_scene siblings): robot r then runs under its
+    class from updateAllTEBs to the saturated command - force_reinit_new_goal_dist / _angular, min_samples, the exploration's
+    min_obstacle_dist and initialiser limits, the cost triple of selectBestTeb, switching_blocking_period, the divergence rule, the
+    look-ahead of its command, the feasibility parameters and the saturation limits. What is one per call must agree over the classes
+    (ValueError with the class and the field): every field of hcp_params(), delete_detours_backwards, max_number_classes, the iteration
+    counts, optimization_activate, xy_goal_tolerance, costmap_obstacles_behind_robot_dist unless plan() is given one, and
+    selection_dropping_probability == 0. A tick is set_config, set_scenes, updateAllTEBs per robot, then renewAndAnalyzeOldTebs
     (h_signatures_per_scene, filter_equivalence_classes_per_scene, filter_detours_per_scene, compact_bands_per_scene),
     explore_candidates_per_scene, one optimize over all bands and select_best_per_scene with switching_blocking_period per robot.
     Every robot's bands end with the bits of a HomotopyClassPlanner of its own whose handle follows the fleet contract of
@@ -1325,12 +1405,31 @@ class FleetHomotopyClassPlanner:
     randomlyDropTebs is not carried over (selection_dropping_probability > 0: NotImplementedError)."""
 
     def __init__(self, cfg, n_robots, max_tebs=None, max_poses=None, max_obstacles=256, max_obstacle_vertices=256, max_via_points=64,
-                 device=0, stream=None, options=None):
-        if cfg.hcp.selection_dropping_probability > 0:
-            raise NotImplementedError("FleetHomotopyClassPlanner: randomlyDropTebs (selection_dropping_probability > 0) is not available per scene")
+                 device=0, stream=None, options=None, robot_cfgs=None, class_of_robot=None):
         self.cfg_ = cfg
         self.n_robots = int(n_robots)
-        self.solver = TebBatchSolver(cfg, max_tebs or self.n_robots * max(cfg.hcp.max_number_classes, 1), max_poses or 224, max(max_obstacles, 1),
+        if (robot_cfgs is None) != (class_of_robot is None):
+            raise ValueError("FleetHomotopyClassPlanner: robot_cfgs and class_of_robot come together")
+        self.robot_cfgs = list(robot_cfgs) if robot_cfgs is not None else None
+        self.class_of_robot = None
+        if self.robot_cfgs is not None:
+            self.class_of_robot = [int(k) for k in class_of_robot]
+            if len(self.class_of_robot) != self.n_robots:
+                raise ValueError("FleetHomotopyClassPlanner: %d class entries for %d robots" % (len(self.class_of_robot), self.n_robots))
+            if not self.robot_cfgs or min(self.class_of_robot) < 0 or max(self.class_of_robot) >= len(self.robot_cfgs):
+                raise ValueError("FleetHomotopyClassPlanner: class_of_robot does not fit the %d classes" % len(self.robot_cfgs))
+            for k, c in enumerate(self.robot_cfgs):
+                if c.hcp.selection_dropping_probability > 0:
+                    raise ValueError("FleetHomotopyClassPlanner: class %d has selection_dropping_probability > 0: randomlyDropTebs is "
+                                     "not available per scene" % k)
+                for field, a, b in self._one_per_call(self.robot_cfgs[0], c):
+                    if a != b:
+                        raise ValueError("FleetHomotopyClassPlanner: class %d differs from class 0 in %s, which is one per call" % (k, field))
+        elif cfg.hcp.selection_dropping_probability > 0:
+            raise NotImplementedError("FleetHomotopyClassPlanner: randomlyDropTebs (selection_dropping_probability > 0) is not available per scene")
+        self._shared = self.robot_cfgs[0] if self.robot_cfgs is not None else cfg   # what is one per call: the classes agree on it
+        self._classes_installed = None   # the class map as last installed on the handle
+        self.solver = TebBatchSolver(cfg, max_tebs or self.n_robots * max(self._shared.hcp.max_number_classes, 1), max_poses or 224, max(max_obstacles, 1),
                                      max(max_obstacle_vertices, 1), max(max_via_points, 1), device=device, stream=stream, options=options)
         self.best_teb_ = np.full(self.n_robots, -1, np.int32)
         self.initial_plan_teb_ = np.full(self.n_robots, -1, np.int32)
@@ -1342,6 +1441,36 @@ class FleetHomotopyClassPlanner:
         self._has_costmaps = False
         self._plans = None                                          # setPlans: the global plans as given, resident on the device
         self.no_infeasible_plans_ = np.zeros(self.n_robots, np.int32)   # computeVelocityCommands: failures in a row, robot by robot
+
+    @staticmethod
+    def _one_per_call(c0, c):
+        """(field, value of class 0, value of the class) of everything a tick takes once for the whole fleet"""
+        p0, p = c0.hcp_params(), c.hcp_params()
+        for name, _ in _abi.HcpParams._fields_:
+            yield name, getattr(p0, name), getattr(p, name)
+        yield "delete_detours_backwards", bool(c0.hcp.delete_detours_backwards), bool(c.hcp.delete_detours_backwards)
+        yield "max_number_classes", c0.hcp.max_number_classes, c.hcp.max_number_classes
+        yield "no_inner_iterations", c0.optim.no_inner_iterations, c.optim.no_inner_iterations
+        yield "no_outer_iterations", c0.optim.no_outer_iterations, c.optim.no_outer_iterations
+        yield "optimization_activate", bool(c0.optim.optimization_activate), bool(c.optim.optimization_activate)
+        yield "xy_goal_tolerance", c0.goal_tolerance.xy_goal_tolerance, c.goal_tolerance.xy_goal_tolerance
+
+    def cfg_of(self, r):
+        """the configuration robot r runs under: its class's, or the fleet's"""
+        return self.cfg_ if self.robot_cfgs is None else self.robot_cfgs[self.class_of_robot[r]]
+
+    def _of_class(self, v, k, nested=0):
+        """v as given for class k: one value for all classes, or a sequence with one entry per class (nested: the depth of ONE value)"""
+        if self.robot_cfgs is None:
+            return v
+        probe = v
+        for _ in range(nested):
+            probe = probe[0]
+        if np.ndim(probe) == 0:
+            return v
+        if len(v) != len(self.robot_cfgs):
+            raise ValueError("FleetHomotopyClassPlanner: %d entries for %d classes" % (len(v), len(self.robot_cfgs)))
+        return v[k]
 
     def bands_of(self, r):
         """band indices of robot r, in band order"""
@@ -1362,13 +1491,14 @@ class FleetHomotopyClassPlanner:
     # ---- updateAllTEBs (src/homotopy_class_planner.cpp:539-562) of every robot ---------------------------------------------------------
     def updateAllTEBs(self, starts, goals, start_vels=None):
         import math
-        s, t = self.solver, self.cfg_.trajectory
+        s = self.solver
         if s.count > 0:
             scene_of = s.band_scenes()
             keep = np.ones(s.count, np.int32)
             for r in range(self.n_robots):
                 if self._goal[r] is None or not (scene_of == r).any():
                     continue
+                t = self.cfg_of(r).trajectory
                 d = math.hypot(goals[r][0] - self._goal[r][0], goals[r][1] - self._goal[r][1])
                 a = abs((goals[r][2] - self._goal[r][2] + math.pi) % (2 * math.pi) - math.pi)
                 if d >= t.force_reinit_new_goal_dist or a >= t.force_reinit_new_goal_angular:
@@ -1380,12 +1510,15 @@ class FleetHomotopyClassPlanner:
             if start_vels is not None and any(v is not None for v in start_vels):
                 sv = [(0.0, 0.0, 0.0) if v is None else v for v in start_vels]
                 hv = [0 if v is None else 1 for v in start_vels]
-            s.update_and_prune_per_scene(starts, goals, t.min_samples, sv, hv)
+            if self.robot_cfgs is None:
+                s.update_and_prune_per_scene(starts, goals, self.cfg_.trajectory.min_samples, sv, hv)
+            else:
+                s.update_and_prune_per_class(starts, goals, sv, hv)
         self._goal = [tuple(g) for g in goals]
 
     # ---- exploreEquivalenceClassesAndInitTebs (:318-340) of every robot ---------------------------------------------------------------
     def exploreEquivalenceClassesAndInitTebs(self, starts, goals, dist_to_obst, start_vels=None, free_goal_vel=False, initial_plans=None):
-        s, h = self.solver, self.cfg_.hcp
+        s, h = self.solver, self._shared.hcp
         best = self.best_teb_
         if s.count > 0:
             s.h_signatures_per_scene(h.h_signature_prescaler, values=False)
@@ -1397,8 +1530,12 @@ class FleetHomotopyClassPlanner:
         sv = None
         if start_vels is not None and any(v is not None for v in start_vels):
             sv = [(0.0, 0.0, 0.0) if v is None else v for v in start_vels]   # a new band's default: fixed zero start velocity
-        self.last_exploration = s.explore_candidates_per_scene(starts, goals, dist_to_obst, sv, free_goal_vel, self.best_teb_,
-                                                               initial_plans=initial_plans)
+        if self.robot_cfgs is None:
+            self.last_exploration = s.explore_candidates_per_scene(starts, goals, dist_to_obst, sv, free_goal_vel, self.best_teb_,
+                                                                   initial_plans=initial_plans)
+        else:   # (dist_to_obst: min_obstacle_dist of every robot's class)
+            self.last_exploration = s.explore_candidates_per_class(starts, goals, sv, free_goal_vel, self.best_teb_,
+                                                                   params=self._shared.hcp_params(), initial_plans=initial_plans)
         scene_of = s.band_scenes() if s.count else np.zeros(0, np.int32)
         for r in range(self.n_robots):                            # getInitialPlanTEB() of selectBestTeb, as a band of the batch
             k = int(self.last_exploration["initial_plan_teb"][r])
@@ -1432,10 +1569,15 @@ class FleetHomotopyClassPlanner:
                     starts[r] = (q[0][0], q[1][0], q[2][0]); goals[r] = (q[0][-1], q[1][-1], q[2][-1])
         tables = list(obstacles_per_robot) if obstacles_per_robot is not None else [_abi.ObstacleTable() for _ in range(R)]
         vias = list(via_per_robot) if via_per_robot is not None else [[] for _ in range(R)]
-        o, s = self.cfg_.optim, self.solver
+        o, s = self._shared.optim, self.solver
         s.set_config(self.cfg_)
         if costmaps_per_robot is not None:
-            dist = self.cfg_.obstacles.costmap_obstacles_behind_robot_dist if costmap_obstacles_behind_robot_dist is None else costmap_obstacles_behind_robot_dist
+            if costmap_obstacles_behind_robot_dist is None and self.robot_cfgs is not None:
+                for k, c in enumerate(self.robot_cfgs):
+                    if c.obstacles.costmap_obstacles_behind_robot_dist != self._shared.obstacles.costmap_obstacles_behind_robot_dist:
+                        raise ValueError("FleetHomotopyClassPlanner.plan: class %d differs from class 0 in costmap_obstacles_behind_robot_dist, "
+                                         "which is one per call (or pass costmap_obstacles_behind_robot_dist)" % k)
+            dist = self._shared.obstacles.costmap_obstacles_behind_robot_dist if costmap_obstacles_behind_robot_dist is None else costmap_obstacles_behind_robot_dist
             s.set_costmaps(costmaps_per_robot)
             if costmap_tile_cells is None:
                 s.set_scenes_from_costmaps(starts, dist, tables, vias)
@@ -1443,9 +1585,15 @@ class FleetHomotopyClassPlanner:
                 s.set_scenes_from_costmap_polygons(starts, dist, costmap_tile_cells, tables, vias, return_tables=False)
         else:
             s.set_scenes(tables, vias)
+        if self.robot_cfgs is not None:   # the class map survives set_scenes* of the same size: installed when it changed
+            want = ([c.to_c() for c in self.robot_cfgs], list(self.class_of_robot))
+            have = self._classes_installed
+            if have is None or have[1] != want[1] or len(have[0]) != len(want[0]) or any(bytes(a) != bytes(b) for a, b in zip(have[0], want[0])):
+                s.set_scene_configs(self.robot_cfgs, self.class_of_robot)
+                self._classes_installed = want
         self._has_costmaps = costmaps_per_robot is not None
         self.updateAllTEBs(starts, goals, start_vels)
-        self.exploreEquivalenceClassesAndInitTebs(starts, goals, self.cfg_.obstacles.min_obstacle_dist, start_vels, free_goal_vel, initial_plans)
+        self.exploreEquivalenceClassesAndInitTebs(starts, goals, self._shared.obstacles.min_obstacle_dist, start_vels, free_goal_vel, initial_plans)
         if s.count == 0:
             self.best_teb_[:] = -1
             return self.best_teb_.copy()
@@ -1453,6 +1601,9 @@ class FleetHomotopyClassPlanner:
         return self.selectBestTeb(now)
 
     def optimizeAllTEBs(self, iter_innerloop, iter_outerloop):
+        if self.robot_cfgs is not None:   # the cost triple of every band's class
+            self.solver.optimize_per_class(iter_innerloop, iter_outerloop, True)
+            return
         h = self.cfg_.hcp
         self.solver.optimize(iter_innerloop, iter_outerloop, True, h.selection_obst_cost_scale, h.selection_viapoint_cost_scale,
                              h.selection_alternative_time_cost)
@@ -1466,7 +1617,7 @@ class FleetHomotopyClassPlanner:
         now = time.monotonic() if now is None else now
         for r in range(self.n_robots):
             if last[r] >= 0 and best[r] != last[r]:
-                if now - self._last_switch[r] > self.cfg_.hcp.switching_blocking_period:
+                if now - self._last_switch[r] > self.cfg_of(r).hcp.switching_blocking_period:
                     self._last_switch[r] = now
                 else:
                     best[r] = last[r]        # switching blocked
@@ -1475,18 +1626,39 @@ class FleetHomotopyClassPlanner:
 
     def getVelocityCommands(self, look_ahead_poses=None):
         """[(ok, vx, vy, omega)] of every robot: getVelocityCommand on its best band (:127-139), one call for all."""
-        t = self.cfg_.trajectory
-        la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
-        ok, v = self.solver.velocity_commands(self.best_teb_, la, t.prevent_look_ahead_poses_near_goal)
-        return [(bool(ok[r]), float(v[r, 0]), float(v[r, 1]), float(v[r, 2])) for r in range(self.n_robots)]
+        if self.robot_cfgs is None:
+            t = self.cfg_.trajectory
+            la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
+            ok, v = self.solver.velocity_commands(self.best_teb_, la, t.prevent_look_ahead_poses_near_goal)
+            return [(bool(ok[r]), float(v[r, 0]), float(v[r, 1]), float(v[r, 2])) for r in range(self.n_robots)]
+        # each robot's own look-ahead parameters: one launch over all bands per distinct (look-ahead, prevent) pair, as TebFleetPlanner
+        pairs = {}
+        for r in range(self.n_robots):
+            t = self.cfg_of(r).trajectory
+            la = t.control_look_ahead_poses if look_ahead_poses is None else look_ahead_poses
+            pairs.setdefault((int(la), int(t.prevent_look_ahead_poses_near_goal)), []).append(r)
+        out = [None] * self.n_robots
+        for (la, prevent), robots in pairs.items():
+            ok, v = self.solver.velocity_commands([self.best_teb_[r] for r in robots], la, prevent)
+            for i, r in enumerate(robots):
+                out[r] = (bool(ok[i]), float(v[i, 0]), float(v[i, 1]), float(v[i, 2]))
+        return out
 
     def isTrajectoryFeasible(self, footprint_spec, inscribed_radius, circumscribed_radius=0.0, look_ahead_idx=-1,
                              feasibility_check_lookahead_distance=-1.0):
         """HomotopyClassPlanner::isTrajectoryFeasible (src/homotopy_class_planner.cpp:686-709) of every robot against ITS grid of the
         costmaps plan(costmaps_per_robot=...) installed: a list of bools. Every round checks the best band of every undecided robot in
         one call; an infeasible best band is removed and the robot's next best tried in the next round, unless it was already the best
-        band of the previous tick (then False). A robot without bands: False."""
+        band of the previous tick (then False). A robot without bands: False. With robot classes footprint_spec, inscribed_radius,
+        look_ahead_idx and feasibility_check_lookahead_distance are one value, or one per class; the angular resolution is the class's."""
         s, R = self.solver, self.n_robots
+        specs = None
+        if self.robot_cfgs is not None:
+            specs = [dict(footprint=self._of_class(footprint_spec, k, 2), inscribed_radius=self._of_class(inscribed_radius, k),
+                          min_resolution_collision_check_angular=c.trajectory.min_resolution_collision_check_angular,
+                          look_ahead_idx=self._of_class(look_ahead_idx, k),
+                          feasibility_check_lookahead_distance=self._of_class(feasibility_check_lookahead_distance, k))
+                     for k, c in enumerate(self.robot_cfgs)]
         if not self._has_costmaps:
             raise ValueError("FleetHomotopyClassPlanner.isTrajectoryFeasible: plan(costmaps_per_robot=...) installs the grids the bands are checked against")
         verdict = [None] * R
@@ -1513,8 +1685,11 @@ class FleetHomotopyClassPlanner:
                     verdict[r] = False
             if not (bands >= 0).any():
                 break
-            ok, _ = s.is_trajectory_feasible_per_scene(bands, footprint_spec, inscribed_radius, ang, look_ahead_idx,
-                                                       feasibility_check_lookahead_distance)
+            if specs is None:
+                ok, _ = s.is_trajectory_feasible_per_scene(bands, footprint_spec, inscribed_radius, ang, look_ahead_idx,
+                                                           feasibility_check_lookahead_distance)
+            else:
+                ok, _ = s.is_trajectory_feasible_per_class(bands, specs)   # (spec k belongs to class k: the map picks it)
             keep = np.ones(s.count, np.int32)
             for r in range(R):
                 if bands[r] < 0:
@@ -1536,13 +1711,12 @@ class FleetHomotopyClassPlanner:
     def hasDiverged(self):
         """TebOptimalPlanner::hasDiverged (src/optimal_planner.cpp:1023-1039) of every robot's best band: a list of bools (no best band:
         False), from one download of the batch statistics."""
-        c = self.cfg_
         if self.solver.count == 0:
             return [False] * self.n_robots
         available, back_chi2 = self.solver.batch_statistics()
         out = []
         for r in range(self.n_robots):
-            b = int(self.best_teb_[r])
+            b, c = int(self.best_teb_[r]), self.cfg_of(r)
             out.append(bool(b >= 0 and c.recovery.divergence_detection_enable and available[b]
                             and back_chi2[b] > c.recovery.divergence_detection_max_chi_squared))
         return out
@@ -1608,7 +1782,7 @@ class FleetHomotopyClassPlanner:
         (src/teb_config.cpp:219-223), and a caller does the same in cfg.robot - at 0 saturateVelocity scales vx and vy to 0.
         last_tick holds the windows, the raw commands and the verdicts of the call."""
         import math
-        R, t = self.n_robots, self.cfg_.trajectory
+        R = self.n_robots
         a = adapter if adapter is not None else adapter_defaults()
         if self._plans is None:
             raise ValueError("FleetHomotopyClassPlanner.computeVelocityCommands: setPlans first")
@@ -1632,7 +1806,7 @@ class FleetHomotopyClassPlanner:
             delta_orient = normalize_theta(gg[2] - poses[r][2])
             stopped = (abs(vels[r][2]) <= a.theta_stopped_vel and abs(vels[r][0]) <= a.trans_stopped_vel
                        and abs(vels[r][1]) <= a.trans_stopped_vel)   # base_local_planner::stopped
-            if (abs(math.sqrt(dx * dx + dy * dy)) < self.cfg_.goal_tolerance.xy_goal_tolerance and abs(delta_orient) < a.yaw_goal_tolerance
+            if (abs(math.sqrt(dx * dx + dy * dy)) < self._shared.goal_tolerance.xy_goal_tolerance and abs(delta_orient) < a.yaw_goal_tolerance
                     and (not a.complete_global_plan or win["via_count"][r] == 0) and (stopped or a.free_goal_vel)):
                 status[r] = self.GOAL_REACHED
         active = [status[r] == self.SUCCESS for r in range(R)]
@@ -1644,14 +1818,20 @@ class FleetHomotopyClassPlanner:
                          costmap_obstacles_behind_robot_dist, costmap_tile_cells)
         planned = [bool(best[r] >= 0) for r in range(R)]
         diverged = self.hasDiverged()
-        feasible = self.isTrajectoryFeasible(footprint_spec, inscribed_radius, 0.0, t.feasibility_check_no_poses,
-                                             t.feasibility_check_lookahead_distance)
+        if self.robot_cfgs is None:
+            t = self.cfg_.trajectory
+            feasible = self.isTrajectoryFeasible(footprint_spec, inscribed_radius, 0.0, t.feasibility_check_no_poses,
+                                                 t.feasibility_check_lookahead_distance)
+        else:   # every class's own look-ahead pair
+            feasible = self.isTrajectoryFeasible(footprint_spec, inscribed_radius, 0.0,
+                                                 [c.trajectory.feasibility_check_no_poses for c in self.robot_cfgs],
+                                                 [c.trajectory.feasibility_check_lookahead_distance for c in self.robot_cfgs])
         raw = self.getVelocityCommands()
         cmd = np.zeros((R, 3))
-        rb = self.cfg_.robot
         for r in range(R):
             if not active[r]:
                 continue
+            rb = self.cfg_of(r).robot
             ok = planned[r] and not diverged[r] and feasible[r] and raw[r][0]
             if ok:
                 v = saturate_velocity(raw[r][1], raw[r][2], raw[r][3], rb.max_vel_x, rb.max_vel_y, rb.max_vel_trans, rb.max_vel_theta,
